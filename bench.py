@@ -24,7 +24,10 @@ narrower than the reference's fp32 convolutions (LRPtools/lrp_modules.py:124-150
 The opt-in speed modes are reported beside it as top-level scalars: `value_f16x3`, `value_f16f6` (and `value_fp32_mfma`), each with
 `dev_chain_<mode>` / `dev_step_<mode>` = its worst-map deviation from the fp32-MFMA chain measured in this run on the step's own 320 maps.
 
-Rank 0 prints ONE JSON line.  At N=1 it also carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the --steps steps and prints the headline (`value`, `ms_per_step`,
+`dtype`, ...; `median_ms` from HIP events recorded inside the timed region).  --dump-outputs DIR writes what the last timed step
+returned (dump_outputs).  Everything below, the relevance asserts on the maps and the `value_<mode>` / `dev_*` scalars of the mode
+sweep come with --full only; there, at N=1, the line also carries
   roofline     : MFMA roofline of the dominant kernel = the relevance conv kernel NAME with the largest total time over the
                  12 conv launches of one pass (30.69 GFLOP per map), picked from this run's own per-launch HIP-event times
                  (on the launch stream); `chain_frac`: the same fraction over all 13 layers; `per_layer`: every layer's;
@@ -178,6 +181,41 @@ def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_BUDGET = 48 << 20        # bytes of all the .npy files of one --dump-outputs (the ceiling is 64 MB)
+
+
+def dump_outputs(out_dir, named, seed=0):
+    """--dump-outputs: the tensors the last timed step handed its caller -> <out_dir>/<name>.npy, float32 (float64 stays float64).
+    Small outputs are written whole; the rest of DUMP_BUDGET is shared by the large ones, each written as a fixed, seeded sample of
+    whole rows (dim 0, e.g. complete maps): <name>.npy the sampled rows, <name>_rows.npy their indices, and over EVERY row
+    <name>_row_sum.npy / <name>_row_absmax.npy (float64).  The inputs are seeded, so two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if any(t.is_cuda for _, t in named):
+        torch.cuda.synchronize()
+    whole = {n for n, t in named if t.numel() * 4 <= DUMP_BUDGET // (4 * len(named))}
+    small = [(n, t) for n, t in named if n in whole]
+    large = [(n, t) for n, t in named if n not in whole]
+    share = (DUMP_BUDGET - sum(t.numel() * 4 for _, t in small)) // max(1, len(large))
+
+    def save(name, x):
+        x = x.detach().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), x if x.dtype == np.float64 else x.astype(np.float32))
+
+    for n, t in small:
+        save(n, t)
+    for n, t in large:
+        rows = t.reshape(t.shape[0], -1)
+        k = max(1, min(rows.shape[0], share // (rows.shape[1] * 4)))
+        idx = np.sort(np.random.RandomState(seed).choice(rows.shape[0], k, replace=False))
+        save(n, t[torch.from_numpy(idx).to(t.device)])
+        save(n + "_rows", torch.from_numpy(idx.astype(np.float64)))
+        save(n + "_row_sum", rows.sum(1, dtype=torch.float64))
+        save(n + "_row_absmax", rows.abs().amax(1).double())
+    log(f"outputs of the last timed step -> {out_dir}: " + ", ".join(f"{n} {tuple(t.shape)}" + ("" if n in whole else " (row sample)")
+                                                                      for n, t in named))
+
+
 def cpu_baseline(V, T, words):
     """reference-equivalent CPU path on a bounded sample: 1 image, T words traced, `words` explained."""
     from oracle import lrp_oracle as O, ref_equiv as RE
@@ -327,7 +365,12 @@ def parse(argv=None):
                     help="do not run the two rocprofv3 --pmc child passes that measure roofline.traffic in this run (the committed PMC summary under profiles/ is used)")
     ap.add_argument("--no-configs", action="store_true", help="skip the `configs` block (BASELINE configs 3 / 4 / 5 and the B=64 line, same process)")
     ap.add_argument("--all-heads", action="store_true", help="config 3: explain all 8 heads of every word in the step (8 x B x T maps)")
-    ap.add_argument("--sustain", type=float, default=5.0, help="seconds of the sustained sub-measurement (0 = off)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: live PMC traffic, sustained leg, roofline, mode sweep, CPU baseline, the "
+                         "`configs` block and the relevance asserts (the --no-* options switch single parts of it off again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller to DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--sustain", type=float, default=None, help="seconds of the sustained sub-measurement (0 = off; default 5 with --full, else 0)")
     ap.add_argument("--graph", action="store_true", help="replay the step from a captured HIP graph per batch in flight (config 2 LRP, config 5); measured slower than eager launches with batches in flight in both (DESIGN.md)")
     ap.add_argument("--replay", type=int, default=None, choices=[0, 1],
                     help="config 5: issue the step from its recorded call list (AOAEngine.explain_batch_replay: inputs copied into static buffers, then the "
@@ -356,6 +399,10 @@ def parse(argv=None):
         a.pipeline = 3 if a.config in (2, 5) else 2
     if a.replay is None:
         a.replay = 1 if (a.config == 5 and not a.graph) else 0
+    if a.sustain is None:
+        a.sustain = 5.0 if a.full else 0.0
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     return a
 
 
@@ -385,7 +432,7 @@ def main():
             dist.init_process_group(backend)
     else:
         dist = None
-        if (a.config == 2 and a.explainer == "lrp" and not a.no_configs and not a.graph and a.batch == 16 and not a.no_live_traffic
+        if (a.full and a.config == 2 and a.explainer == "lrp" and not a.no_configs and not a.graph and a.batch == 16 and not a.no_live_traffic
                 and not a.only_dropin and not a.fp32_mfma):
             log("HBM traffic of the chain's kernels: two rocprofv3 --pmc child passes (before this process touches the GPU) ...")
             live_traffic(a.batch, a.batch * a.words, a.conv_mode)
@@ -397,7 +444,7 @@ def main():
         return
     out = run_config(a, dist, rank, world)
     if rank == 0:
-        if world == 1 and a.config == 2 and a.explainer == "lrp" and not a.no_configs and not a.graph and a.batch == 16:
+        if a.full and world == 1 and a.config == 2 and a.explainer == "lrp" and not a.no_configs and not a.graph and a.batch == 16:
             out["configs"] = other_configs(a)
         print(json.dumps(out), flush=True)
     if dist is not None:
@@ -420,7 +467,7 @@ def other_configs(a):
         gc.collect()
         torch.cuda.empty_cache()
         fast_mode = key.endswith("#f16f6")
-        b = parse(argv + ["--steps", str(n), "--warmup", "4", "--sustain", "0", "--no-modes", "--no-cpu-baseline", "--no-configs",
+        b = parse(argv + ["--full", "--steps", str(n), "--warmup", "4", "--sustain", "0", "--no-modes", "--no-cpu-baseline", "--no-configs",
                           "--conv-mode", "3" if fast_mode else str(a.conv_mode)])
         o = run_config(b, None, 0, 1)
         if fast_mode:
@@ -757,7 +804,13 @@ def run_config(a, dist, rank, world):
     events = [ev0]
     dt, outs = timed(a.steps, events)
     maps = outs[0]
-    if not build_flags:                                       # (a timing-experiment build computes garbage on purpose: tools/ab_chain.sh)
+    if a.dump_outputs and rank == 0:          # before anything else runs a step (the --full legs reuse the step's buffers)
+        names = ("r_feat", "r_words") if a.config == 5 else ("maps", "r_words")
+        named = [(names[i] if i < len(names) else f"out{i}", t) for i, t in enumerate(outs) if torch.is_tensor(t)]
+        if guided:
+            named.append(("guided_maps", state["gmaps"]))
+        dump_outputs(a.dump_outputs, named)
+    if a.full and not build_flags:                            # (a timing-experiment build computes garbage on purpose: tools/ab_chain.sh)
         ops.check_relevance(maps, finite=True, nonzero=True)  # the reference's asserts, outside the timed region
     # step completions by HIP events; with n_pipe batches in flight completions come in bursts, so the per-step time is
     # taken over windows of n_pipe consecutive completions: (end[i] - end[i - n_pipe]) / n_pipe, median over the region
@@ -805,7 +858,7 @@ def run_config(a, dist, rank, world):
             out["metric"] = "INVALID (experiment build of liblrpx.so: " + build_flags + ") " + out["metric"]
         out["median_ms_note"] = (f"median over the timed region of (completion[i] - completion[i-{w}]) / {w} by HIP events "
                                  f"({w} batches in flight complete in bursts); hip_event_ms_per_step = last completion / steps")
-        if world == 1 and has_vgg and lens is None:
+        if a.full and world == 1 and has_vgg and lens is None:
             out["roofline"] = roofline(a, lib, eng, state, maps, B, T, mode)
             if a.config == 2 and not guided and not a.no_modes and not a.graph:      # (the sweep switches modes between eager steps)
                 modes = mode_sweep(lib, engines, streams, one_step, state, B, T, mode)
@@ -822,7 +875,7 @@ def run_config(a, dist, rank, world):
                                            "relevance chain of that mode against the fp32-MFMA chain (mode 0) on ONE trace and the step's own decoder relevance; "
                                            "dev_step_<mode>: the same for the whole step (each mode runs its own forward trace: includes max-pool tie flips, "
                                            "DESIGN.md 3)" % (mode, MODE_DTYPE[mode], B * T))
-        elif world == 1 and not has_vgg:
+        elif a.full and world == 1 and not has_vgg:
             # config 5: no CNN stage; HBM-bound projector / v_proj rules.  Algorithmic bytes per map: read F,
             # write R_feat, read the projected features: 3 x 36 x 2048 x 4 B = 0.9 MB (weights amortised over the batch)
             byts = 3.0 * 36 * 2048 * 4 * B * T
@@ -830,7 +883,7 @@ def run_config(a, dist, rank, world):
             out["roofline"] = {"bound": "hbm", "kernel": "whole step (decoder relevance back to 36x2048 region features)",
                                "achieved": round(gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": round(gbs / PEAK_HBM_GBS, 4),
                                "traffic": None}
-        if world == 1 and a.config == 2 and not a.no_cpu_baseline:
+        if a.full and world == 1 and a.config == 2 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(V, T, list(range(T)))       # every word of one image: nothing extrapolated
         return out
     return None

@@ -123,12 +123,38 @@ def test_bench_arguments_of_every_baseline_config():
     a = bench.parse([])
     assert (a.config, a.batch, a.words, a.vocab, a.pipeline, a.explainer, a.gpus) == (2, 16, 20, 9586, 3, "lrp", 1)
     assert (a.steps, a.warmup) == (20, 4) and not a.no_configs
+    # a plain run measures the headline only; everything else (sustained leg, roofline, configs block, ...) is behind --full
+    assert not a.full and a.sustain == 0 and a.dump_outputs is None
+    f = bench.parse(["--full"])
+    assert f.full and f.sustain == 5.0 and not f.no_configs
     for cfg, want in ((3, (64, 11027, 2, "lrp")), (4, (32, 9586, 2, "lrp+guided")), (5, (32, 11027, 3, "lrp"))):
         b = bench.parse(["--config", str(cfg)])
         assert (b.batch, b.vocab, b.pipeline, b.explainer) == want
     b64 = bench.parse(["--config", "2", "--batch", "64", "--pipeline", "2"])
     assert (b64.batch, b64.pipeline, b64.vocab) == (64, 2, 9586)
     assert bench.parse(["--config", "3", "--all-heads"]).all_heads
+
+
+def test_bench_dump_outputs_budget_sample_and_determinism(tmp_path):
+    """bench.py --dump-outputs: small outputs whole, large ones as a seeded sample of whole rows plus per-row sum / max|.| over every
+    row; float32 (float64 kept), all files together within 64 MB, the same files for the same outputs"""
+    import numpy as np
+    import bench
+    g = torch.Generator().manual_seed(0)
+    maps = torch.randn(320, 3, 224, 224, generator=g)
+    r_words = torch.randn(16, 20, 20, generator=g).double()
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), [("maps", maps), ("r_words", r_words)])
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["maps.npy", "maps_row_absmax.npy", "maps_row_sum.npy", "maps_rows.npy", "r_words.npy"]
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 64 << 20
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), f
+    rows = np.load(tmp_path / "a" / "maps_rows.npy").astype(np.int64)
+    assert 1 <= len(rows) < 320 and np.array_equal(np.load(tmp_path / "a" / "maps.npy"), maps[torch.from_numpy(rows)].numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "r_words.npy"), r_words.numpy())
+    assert np.allclose(np.load(tmp_path / "a" / "maps_row_sum.npy"), maps.double().flatten(1).sum(1).numpy())
 
 
 def test_zeros_arena_views_are_zero_disjoint_and_aligned():

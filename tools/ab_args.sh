@@ -2,7 +2,7 @@
 # A/B of bench.py argument sets on ONE box: tools/ab_args.sh "<args A>" "<args B>" ... (env from the caller), twice
 for rep in 1 2; do
 for v in "$@"; do
-  out=$(timeout -k 10 300 python bench.py --no-cpu-baseline --no-modes $v 2>/dev/null)
+  out=$(timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-modes $v 2>/dev/null)
   python - "$v" "$out" <<'PY'
 import json, sys
 d = json.loads(sys.argv[2])

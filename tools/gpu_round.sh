@@ -12,13 +12,13 @@ if [[ $WHAT == *tests* ]]; then
   tail -5 $OUT/tests.log
 fi
 if [[ $WHAT == *bench* ]]; then
-  timeout -k 10 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+  timeout -k 10 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
   cat $OUT/bench.json
 fi
 if [[ $WHAT == *prof* ]]; then
-  (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $ROOT/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-modes --sustain 0 > $OUT/prof.log 2>&1; echo "prof rc=$?")
+  (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $ROOT/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-modes --sustain 0 > $OUT/prof.log 2>&1; echo "prof rc=$?")
   python tools/prof_summary.py stats $OUT/prof > $OUT/kernel_stats.txt 2>&1; head -30 $OUT/kernel_stats.txt
-  (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_serial -- python3 $ROOT/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-modes --sustain 0 --pipeline 1 > $OUT/prof_serial.log 2>&1; echo "prof serial rc=$?")
+  (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_serial -- python3 $ROOT/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-modes --sustain 0 --pipeline 1 > $OUT/prof_serial.log 2>&1; echo "prof serial rc=$?")
   python tools/prof_summary.py stats $OUT/prof_serial > $OUT/kernel_stats_serial.txt 2>&1
   rm -rf $OUT/prof/*/*.db $OUT/prof_serial/*/*.db
 fi

@@ -11,11 +11,11 @@ if [[ $WHAT == *tests* ]]; then
   LRPX_TIE_STATS=1 timeout -k 10 1100 python -m pytest tests -q -m gpu > $OUT/tests.log 2>&1; echo "tests rc=$?"; tail -3 $OUT/tests.log
 fi
 if [[ $WHAT == *bench* ]]; then
-  timeout -k 10 500 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cat $OUT/bench.json | head -c 600; echo
+  timeout -k 10 500 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cat $OUT/bench.json | head -c 600; echo
 fi
 prof() { # name, bench args...
   local name=$1; shift
-  (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$name -- python3 $ROOT/bench.py "$@" --no-cpu-baseline --no-modes --no-configs --sustain 0 > $OUT/prof_$name.log 2>&1; echo "prof $name rc=$?")
+  (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$name -- python3 $ROOT/bench.py --full "$@" --no-cpu-baseline --no-modes --no-configs --sustain 0 > $OUT/prof_$name.log 2>&1; echo "prof $name rc=$?")
   python tools/prof_summary.py stats $OUT/prof_$name > $OUT/kernel_stats_$name.txt 2>&1
   rm -rf $OUT/prof_$name/*/*.db
 }
@@ -45,7 +45,7 @@ if [[ $WHAT == *sq* ]]; then
   python tools/prof_summary.py pipe $OUT/pmc/A $OUT/pmc/E $OUT/pmc/F $OUT/pmc/G > $OUT/pmc_pipe.txt 2>&1; cat $OUT/pmc_pipe.txt
 fi
 if [[ $WHAT == *gloo* ]]; then
-  LRPX_BENCH_BACKEND=gloo LRPX_BENCH_ONE_GPU=1 timeout -k 10 400 python bench.py --gpus 2 --gather --steps 6 --warmup 2 --no-cpu-baseline --no-modes --no-configs --sustain 0 --pipeline 2 > $OUT/bench_2rank_gloo_gather.json 2> $OUT/bench_2rank_gloo_gather.err; echo "gloo gather rc=$?"; cat $OUT/bench_2rank_gloo_gather.json | head -c 500; echo
+  LRPX_BENCH_BACKEND=gloo LRPX_BENCH_ONE_GPU=1 timeout -k 10 400 python bench.py --full --gpus 2 --gather --steps 6 --warmup 2 --no-cpu-baseline --no-modes --no-configs --sustain 0 --pipeline 2 > $OUT/bench_2rank_gloo_gather.json 2> $OUT/bench_2rank_gloo_gather.err; echo "gloo gather rc=$?"; cat $OUT/bench_2rank_gloo_gather.json | head -c 500; echo
 fi
 rm -rf $OUT/pmc/*/*/*.db
 exit 0

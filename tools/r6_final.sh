@@ -11,11 +11,11 @@ if [[ $WHAT == *tests* ]]; then
   LRPX_TIE_STATS=1 timeout -k 10 1100 python -m pytest tests -q -m gpu -s > $OUT/tests.log 2>&1; echo "tests rc=$?"; grep -E "passed|failed" $OUT/tests.log | tail -2
 fi
 if [[ $WHAT == *bench* ]]; then
-  timeout -k 10 700 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cat $OUT/bench.json | head -c 700; echo
+  timeout -k 10 700 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cat $OUT/bench.json | head -c 700; echo
 fi
 prof() { # name, bench args...
   local name=$1; shift
-  (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$name -- python3 $ROOT/bench.py "$@" --no-cpu-baseline --no-modes --no-configs --sustain 0 --no-live-traffic > $OUT/prof_$name.log 2>&1; echo "prof $name rc=$?")
+  (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$name -- python3 $ROOT/bench.py --full "$@" --no-cpu-baseline --no-modes --no-configs --sustain 0 --no-live-traffic > $OUT/prof_$name.log 2>&1; echo "prof $name rc=$?")
   python tools/prof_summary.py stats $OUT/prof_$name > $OUT/kernel_stats_$name.txt 2>&1
   rm -rf $OUT/prof_$name/*/*.db
 }
@@ -54,8 +54,8 @@ if [[ $WHAT == *smoke* ]]; then
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc=$?"; tail -2 $OUT/smoke.log
 fi
 if [[ $WHAT == *gloo* ]]; then
-  LRPX_BENCH_BACKEND=gloo LRPX_BENCH_ONE_GPU=1 timeout -k 10 400 python bench.py --gpus 2 --gather --steps 6 --warmup 2 --no-cpu-baseline --no-modes --no-configs --sustain 0 --pipeline 2 > $OUT/bench_2rank_gloo_gather.json 2> $OUT/bench_2rank_gloo_gather.err; echo "gloo gather rc=$?"; cat $OUT/bench_2rank_gloo_gather.json | head -c 400; echo
-  LRPX_BENCH_BACKEND=gloo LRPX_BENCH_ONE_GPU=1 timeout -k 10 400 python bench.py --gpus 2 --gather heatmap --steps 6 --warmup 2 --no-cpu-baseline --no-modes --no-configs --sustain 0 --pipeline 2 > $OUT/bench_2rank_gloo_heatmap.json 2> $OUT/bench_2rank_gloo_heatmap.err; echo "gloo heatmap rc=$?"; cat $OUT/bench_2rank_gloo_heatmap.json | head -c 300; echo
+  LRPX_BENCH_BACKEND=gloo LRPX_BENCH_ONE_GPU=1 timeout -k 10 400 python bench.py --full --gpus 2 --gather --steps 6 --warmup 2 --no-cpu-baseline --no-modes --no-configs --sustain 0 --pipeline 2 > $OUT/bench_2rank_gloo_gather.json 2> $OUT/bench_2rank_gloo_gather.err; echo "gloo gather rc=$?"; cat $OUT/bench_2rank_gloo_gather.json | head -c 400; echo
+  LRPX_BENCH_BACKEND=gloo LRPX_BENCH_ONE_GPU=1 timeout -k 10 400 python bench.py --full --gpus 2 --gather heatmap --steps 6 --warmup 2 --no-cpu-baseline --no-modes --no-configs --sustain 0 --pipeline 2 > $OUT/bench_2rank_gloo_heatmap.json 2> $OUT/bench_2rank_gloo_heatmap.err; echo "gloo heatmap rc=$?"; cat $OUT/bench_2rank_gloo_heatmap.json | head -c 300; echo
 fi
 rm -rf $OUT/pmc/*/*/*.db
 exit 0
