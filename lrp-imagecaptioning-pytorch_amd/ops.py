@@ -120,8 +120,10 @@ def amax_maps(s, n_maps):
 
 def conv_desc(inp, wpacked, n_maps, hw, cin, n_oc, taps, epi, *, pix_per_map=0, stab=STAB_NONE, oc_split=0,
               relu=0, bias=None, x=None, u=None, zdiv=None, map2img=None, out0=None, out1=None, bf16x6=0,
-              f16x3=0, in_amax=None, out1_amax=None, pool_am=None, out0_amax=None, blocked=0):
-    """the lrpx_conv_desc of one contraction (the tensors must outlive its use: the descriptor holds raw pointers)"""
+              f16x3=0, in_amax=None, out1_amax=None, pool_am=None, out0_amax=None, blocked=0, tile_group=0, out_chunk=0,
+              in_chunked=0):
+    """the lrpx_conv_desc of one contraction (the tensors must outlive its use: the descriptor holds raw pointers).
+    tile_group / out_chunk / in_chunked: the tile-order hint and the K-chunked S layouts the VGG16 chain sets (include/lrpx.h)"""
     d = ConvDesc()
     d.in_, d.wpacked = ptr(_dev(inp)), ptr(_dev(wpacked))
     d.n_maps, d.hw, d.cin, d.n_oc, d.taps, d.pix_per_map = n_maps, hw, cin, n_oc, taps, pix_per_map
@@ -131,6 +133,7 @@ def conv_desc(inp, wpacked, n_maps, hw, cin, n_oc, taps, epi, *, pix_per_map=0, 
     d.bias, d.x, d.u, d.zdiv, d.map2img = ptr(bias), ptr(x), ptr(u), ptr(zdiv), ptr(map2img)
     d.out0, d.out1 = ptr(out0), ptr(out1)
     d.blocked = blocked
+    d.tile_group, d.out_chunk, d.in_chunked = tile_group, out_chunk, in_chunked
     return d
 
 
