@@ -32,6 +32,7 @@ enum {
     LRPX_EZERO = 5        /* all-zero relevance (reference: `assert sample.grad.sum()!=0`, lrp_wrapper.py:81) */
 };
 
+/* 101: the alpha-beta Conv2d rule (LRPX_PACK_*_PN*, lrpx_divide_alpha_beta, lrpx_maxpool2x2_relevance_ab); 100 before it */
 int lrpx_version(void);
 const char* lrpx_last_error_string(void);
 /* "" for a release build.  Otherwise the list of timing-experiment / profiling switches the library was compiled with
@@ -48,9 +49,19 @@ enum {
     LRPX_PACK_DENSE_T = 4,   /* dense: out = in @ W      W is (k, n)   (epsilon rule W^T contraction, gridTDmodel.py:744-765) */
     LRPX_PACK_DENSE = 5,     /* dense: out = in @ W^T    W is (n, k)   (nn.Linear forward) */
     LRPX_PACK_FWD = 6,       /* conv fwd, plain W only */
-    LRPX_PACK_FWD_DUAL_FIRST = 7 /* first conv: the signed input is stored split, channels [0,cin) = x+, [cin,2cin) = x-;
+    LRPX_PACK_FWD_DUAL_FIRST = 7, /* first conv: the signed input is stored split, channels [0,cin) = x+, [cin,2cin) = x-;
                                   plain part = W on both, Z part = W+ on x+ and W- on x-  (Z = conv(x+,W+)+conv(x-,W-),
                                   lrp_modules.py:81-84) */
+    /* The general alpha-beta rule  R = alpha * lrp_backward(PosNetConv) - beta * lrp_backward(NegNetConv)  (lrp_modules.py:124-150,
+     * the two nets at :56-122).  Its two forward convs and its two transposed convs are ONE contraction each with the second
+     * net stacked along the channel axis: Z = [Z+ | Z-] are 2 cout output channels, and with S2 = [alpha S+ | -beta S-]
+     * (lrpx_divide_alpha_beta) the relevance is x * convT(S2, [W+ ; W-]) with K = 2 cout.  fp32 packer only. */
+    LRPX_PACK_FWD_PN = 8,        /* x >= 0, k = cin: channels [0,cout) = W+ (Z+ = conv(x,W+), :66-67), [cout,2cout) = W- (Z- = conv(x,W-), :104-105) */
+    LRPX_PACK_FWD_PN_FIRST = 9,  /* input split [x+ | x-], k = 2cin: [0,cout) = W+ on x+ and W- on x- (Z+, :81-84),
+                                    [cout,2cout) = W- on x+ and W+ on x- (Z-, :116-121) */
+    LRPX_PACK_BWD_PN = 10,       /* k = 2cout, oc = cin, taps flipped: rows [0,cout) (alpha S+) carry W+, rows [cout,2cout) (-beta S-) carry W- */
+    LRPX_PACK_BWD_PN_FIRST = 11  /* as BWD_PN with oc = 2cin for the split multiplicand [x+ | x-]: W+ where (row in the S+ half) ==
+                                    (column in the x+ half), W- otherwise; lrpx_fold_halves joins the halves */
 };
 /* number of floats of the packed image: n_oc/k padded to multiples of 32 / kc */
 size_t lrpx_packed_floats(int n_oc, int k, int taps, int kc);
@@ -161,6 +172,20 @@ int lrpx_maxpool2x2_relevance(const float* x, const float* r_out, const float* z
 /* s[n,p,c] = r[n,p,c] / stab(z[img(n),p,c])   (LRPtools/utils.py:16-18 safe_divide with broadcast) */
 int lrpx_divide_stab(const float* r, const float* z, const int32_t* map2img, float* s, int n_maps, long pix_c,
                      int stab, void* stream);
+/* The divisions of the general alpha-beta Conv2d rule in one pass (lrp_modules.py:136-147: safe_divide of the incoming relevance by
+ * the outputs of PosNetConv and of NegNetConv, then `alpha * R_pos - beta * R_neg` - the two factors are folded into S here):
+ *   s2[n,p,0..c) = alpha * (r[n,p,:] / safe(zpos[img(n),p,:])),   s2[n,p,c..2c) = -beta * (r[n,p,:] / safe(zneg[img(n),p,:]))
+ * r: [n_maps*pix][c]; zpos / zneg: [n_img*pix][c] per IMAGE (map2img, null = identity); s2: [n_maps*pix][2c]; c % 4 == 0.
+ * safe(z) = z + 1e-7 [z == 0] (LRPtools/utils.py:16-18); IEEE division.  Element indices are 64-bit. */
+int lrpx_divide_alpha_beta(const float* r, const float* zpos, const float* zneg, const int32_t* map2img, float* s2,
+                           int n_maps, int pix, int c, float alpha, float beta, void* stream);
+/* lrpx_maxpool2x2_relevance with the two divisors of the alpha-beta rule of the conv below the pool: the Pool2d rule
+ * (lrp_modules.py:182-195; first maximum wins, an all-zero window sends r_out / 1e-7 * 0 = 0 to its first pixel) followed by
+ * lrpx_divide_alpha_beta, without the full-resolution relevance ever reaching memory.
+ * x, zpos, zneg: per IMAGE (n_img,2h,2w,c); r_out: per MAP (n_maps,h,w,c); s2: (n_maps,2h,2w,2c). */
+int lrpx_maxpool2x2_relevance_ab(const float* x, const float* r_out, const float* zpos, const float* zneg,
+                                 const int32_t* map2img, float* s2, int n_maps, int h_out, int w_out, int c, float alpha,
+                                 float beta, void* stream);
 /* Per image, for a 2x2 max-pool with input x (n,2h,2w,c) sitting on a conv with Z+ = z (n,2h,2w,c):
  *   am[n,h,w,c]  = window position (0..3, row-major, first maximum wins as in max_pool2d's backward)
  *   xzw[n,h,w,c] = max / safe(z at the winner): the multiplicand that turns the accumulator of the conv ABOVE the pool

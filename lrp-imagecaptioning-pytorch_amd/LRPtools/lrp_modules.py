@@ -6,14 +6,21 @@ lrp_params)` returns a tuple with the arity of `relevance_input` (:157-170).  `m
 layer input, as the reference's `save_input_hook` leaves it (lrp_wrapper.py:24-25).  Tensors are NCHW on the
 device, as in the reference; layouts are converted at this boundary.
 
+Conv2d follows the reference's alpha-beta rule with the `alpha`, `beta` and `ignore_bias` of `lrp_params` (:124-150):
+alpha = 1, beta = 0 without bias - the preset of lrp_wrapper.py:7-12 - on the tuned path it always had, every other
+combination (alpha2beta1, with bias, ...) on the general path beside it.
+
 Conv2d 3x3/pad 1, MaxPool2d(2,2) and ReLU are the layers VGG16 exercises (kernels for square maps of 224/112/56/28/14
 pixels; any other H x W <= 224 runs zero-embedded in the next larger of those; other kernel sizes / strides raise ValueError).  Linear / BatchNorm2d / BatchNorm1d / Dropout / Add / Flatten / AvgPool2d (SURVEY.md §8(a) M4 and W3's table, only
 reached with the reference's ResNet encoders) are HBM-bound streaming kernels (csrc/lrpx_rules.hip), any shape."""
+import math
+
 import torch
 import torch.nn as nn
 
 from .. import _lib, ops
-from .._lib import EPI_FWD_DUAL, EPI_REL, PACK_BWD_FIRST, PACK_FWD_DUAL_FIRST, STAB_SAFE, check, ptr, stream_ptr
+from .._lib import (EPI_FWD_DUAL, EPI_PLAIN, EPI_REL, PACK_BWD_FIRST, PACK_BWD_PN_FIRST, PACK_FWD_DUAL_FIRST, PACK_FWD_PN_FIRST,
+                    STAB_SAFE, check, ptr, stream_ptr)
 
 _SIZES = (224, 112, 56, 28, 14)
 
@@ -35,14 +42,40 @@ class ReLU:
         raise NotImplementedError("ReLU is always registered with the 'identity' rule (lrp_wrapper.py:51-52)")
 
 
+def alpha_beta_params(lrp_params):
+    """(alpha, beta, ignore_bias) of an `lrp_params` dict; None or a missing key mean the preset's 1 / 0 / True
+    (lrp_wrapper.py:7-12).  ValueError for a non-finite alpha / beta.  Host logic: no device."""
+    p = lrp_params or {}
+    alpha, beta = float(p.get("alpha", 1.)), float(p.get("beta", 0.))
+    _require(math.isfinite(alpha) and math.isfinite(beta), "lrp_params: alpha and beta must be finite, got alpha={} beta={}".format(alpha, beta))
+    return alpha, beta, bool(p.get("ignore_bias", True))
+
+
+def conv_rule_params(module, lrp_params):
+    """`alpha_beta_params` for one conv layer.  ignore_bias=False on a conv WITHOUT bias is refused: the reference's clones of the
+    layer then keep the random bias `nn.Conv2d(...)` gave them (lrp_modules.py:58-76 assign a bias only `if conv.bias is not
+    None`), so its result there is noise, not a rule to reproduce.  Host logic: no device."""
+    alpha, beta, ignore_bias = alpha_beta_params(lrp_params)
+    _require(ignore_bias or getattr(module, "bias", None) is not None,
+             "lrpx Conv2d rule: ignore_bias=False on a conv layer without bias (the reference adds the random bias of a fresh "
+             "nn.Conv2d there: noise) - pass ignore_bias=True or give the layer a bias")
+    return alpha, beta, ignore_bias
+
+
 class Conv2d:
-    """alpha=1, beta=0, ignore_bias rule (lrp_modules.py:124-150) for signed or non-negative inputs:
-    Z = conv(x+,W+) + conv(x-,W-);  S = R/safe(Z);  R_in = x+ * convT(S,W+) + x- * convT(S,W-).
-    The input is stored split [x+ | x-] so one MFMA pass serves both terms."""
+    """The alpha-beta rule (lrp_modules.py:124-150), R = alpha * lrp_backward(PosNetConv) - beta * lrp_backward(NegNetConv), for signed
+    or non-negative inputs, with `alpha`, `beta`, `ignore_bias` from `lrp_params` (None / missing key: 1, 0, True).
+      alpha = 1, beta = 0, ignore_bias (the preset):  Z = conv(x+,W+) + conv(x-,W-);  S = R/safe(Z);
+          R_in = x+ * convT(S,W+) + x- * convT(S,W-).  The input is stored split [x+ | x-] so one MFMA pass serves both terms.
+      anything else:  Z+ as above (+ b), Z- = conv(x-,W+) + conv(x+,W-) (+ b) - with bias BOTH nets add the whole bias, b+ + b- = b
+          (:73-76, :107-110);  S2 = [alpha R/safe(Z+) | -beta R/safe(Z-)] (lrpx_divide_alpha_beta);  R_in = [x+ | x-] * convT(S2, .)
+          with the weight rows [W+ ; W-] stacked like S2 (LRPX_PACK_BWD_PN_FIRST): one contraction with K = 2 cout, fp32 MFMA."""
 
     def propagate_relevance(self, module, relevance_input, relevance_output, lrp_method, lrp_params=None):
         if lrp_method != "alpha_beta":
             raise NotImplementedError('Only adopt alpha 1 rule for conv layer')       # lrp_modules.py:152
+        alpha, beta, ignore_bias = conv_rule_params(module, lrp_params)
+        general = not (alpha == 1. and beta == 0. and ignore_bias)
         x = module.input[0].detach()
         r_out = relevance_output[0].detach()
         _require(isinstance(module, nn.Conv2d) and module.kernel_size == (3, 3) and module.padding == (1, 1)
@@ -68,6 +101,9 @@ class Conv2d:
         gran = 16 if h >= 112 else 32
         c2 = 8 if (h == 224 and 2 * cin <= 8) else _pad_to(2 * cin, gran)   # split input channels [x+ | x- | 0..]
         co_p = _pad_to(cout, 32)
+        if general:
+            R = self._general(module, x, n, cin, cout, h, c2, co_p, r_out, alpha, beta, ignore_bias)
+            return self._result(R, relevance_input, h0, w0, h, w)
         cache = module.__dict__.setdefault("_lrpx_pack", {})
         key = (h, module.weight._version, module.weight.data_ptr())
         if cache.get("key") != key:
@@ -104,6 +140,10 @@ class Conv2d:
         r_half = torch.empty(n, h * w, half, device=dev)
         check(lib.lrpx_fold_halves(ptr(r_split), ptr(r_half), n * h * w, half, st))
         R = ops.nhwc_to_nchw(r_half, cin, h, w)
+        return self._result(R, relevance_input, h0, w0, h, w)
+
+    @staticmethod
+    def _result(R, relevance_input, h0, w0, h, w):
         if (h0, w0) != (h, w):
             R = R[:, :, :h0, :w0].contiguous()
         ops.check_relevance(R)                                      # lrp_modules.py:154-155
@@ -112,6 +152,49 @@ class Conv2d:
         if relevance_input is not None and len(relevance_input) == 2:
             return R, relevance_input[1]
         return (R,)
+
+    @staticmethod
+    def _general(module, x, n, cin, cout, h, c2, co_p, r_out, alpha, beta, ignore_bias):
+        """the general rule on the (zero-embedded) h x h canvas: x (n,cin,h,h), r_out (n,cout,h,h) -> R (n,cin,h,h)"""
+        lib = _lib.load()
+        st = stream_ptr()
+        dev = x.device
+        w = h
+        half = c2 // 2
+        cache = module.__dict__.setdefault("_lrpx_pack_pn", {})     # the packs depend on the weights and the map size, not on
+        key = (h, module.weight._version, module.weight.data_ptr())  # alpha / beta (they travel in S2) or ignore_bias
+        if cache.get("key") != key:
+            wt_h = torch.zeros(co_p, half, 3, 3, device=dev)
+            wt_h[:cout, :cin] = module.weight.detach().to(torch.float32)
+            kc_f = ops.conv_kc(h, 9, c2)
+            pf = torch.zeros(lib.lrpx_packed_floats(2 * co_p, c2, 9, kc_f), device=dev)
+            check(lib.lrpx_pack_weights(ptr(wt_h), co_p, half, 9, PACK_FWD_PN_FIRST, kc_f, ptr(pf), st))
+            kc_b = ops.conv_kc(h, 9, 2 * co_p)
+            pb = torch.zeros(lib.lrpx_packed_floats(_pad_to(c2, 32), 2 * co_p, 9, kc_b), device=dev)
+            check(lib.lrpx_pack_weights(ptr(wt_h), co_p, half, 9, PACK_BWD_PN_FIRST, kc_b, ptr(pb), st))
+            # the pack is channel-block major: the Z- half of the output channels starts at this offset
+            cache.update(key=key, pf=pf, pb=pb, neg=lib.lrpx_packed_floats(co_p, c2, 9, kc_f))
+        xs = torch.empty(n, h * w, c2, device=dev)
+        xsrc = x.to(torch.float32)
+        if half != cin:     # x+ occupies channels [0,half), x- starts at `half`: pad the channel axis with zeros
+            xsrc = torch.cat([xsrc, torch.zeros(n, half - cin, h, w, device=dev)], 1)
+        check(lib.lrpx_nchw_to_nhwc_posneg(ptr(xsrc.contiguous()), ptr(xs), n, half, h * w, c2, st))
+        bias = None
+        if not ignore_bias:     # both nets add b+ + b- = b (on the canvas beyond the map too: R is zero there, so S2 is)
+            bias = torch.zeros(co_p, device=dev)
+            bias[:cout] = module.bias.detach().to(torch.float32)
+        zpos = torch.empty(n, h * w, co_p, device=dev)
+        zneg = torch.empty(n, h * w, co_p, device=dev)
+        pf = cache["pf"]
+        ops.conv_mfma(xs, pf, n, h, c2, co_p, 9, EPI_PLAIN, oc_split=co_p, bias=bias, out0=zpos)
+        ops.conv_mfma(xs, pf[cache["neg"]:], n, h, c2, co_p, 9, EPI_PLAIN, oc_split=co_p, bias=bias, out0=zneg)
+        r_nhwc = ops.nchw_to_nhwc(r_out.to(torch.float32), co_p)
+        s2 = ops.divide_alpha_beta(r_nhwc, zpos, zneg, None, alpha, beta)
+        r_split = torch.empty(n, h * w, c2, device=dev)
+        ops.conv_mfma(s2, cache["pb"], n, h, 2 * co_p, _pad_to(c2, 32), 9, EPI_REL, oc_split=c2, x=xs, out0=r_split)
+        r_half = torch.empty(n, h * w, half, device=dev)
+        check(lib.lrpx_fold_halves(ptr(r_split), ptr(r_half), n * h * w, half, st))
+        return ops.nhwc_to_nchw(r_half, cin, h, w)
 
 
 def _pair(v):

@@ -10,6 +10,9 @@ relevance pass (lrp_wrapper.py:37-87).  Here `add_lrp` validates the same leaf -
     nets): the model's own forward runs once under forward hooks that keep `module.input` (lrp_wrapper.py:24-25) and
     record the call order; the relevance then walks the recorded calls in reverse through this repo's rule classes
     (lrp_modules.py, HIP kernels), summing where a tensor feeds several modules - what autograd does for the reference.
+`add_lrp(model, lrp_params=...)` lays a dict over the preset's parameters (the reference's add_lrp has the comment "Override default
+parameters if provided" and no argument): the VGG16 encoder with another alpha / beta and `ignore_bias=True` runs the batched
+`ops.Vgg16.relevance_alpha_beta`, with `ignore_bias=False` the generic driver.
 Improvement over the reference: `add_lrp` is idempotent (the reference stacks hooks on every call, which
 multiplies its cost without changing the result)."""
 import torch
@@ -54,14 +57,34 @@ def _match_vgg16(leaves):
     return i == len(leaves)
 
 
-def add_lrp(model):
+def merge_lrp_params(lrp_params=None):
+    """`lrp_params` laid over the preset's (lrp_wrapper.py:7-12; the reference's add_lrp carries the comment "Override default
+    parameters if provided" where this happens here).  ValueError for a non-finite alpha / beta.  Host logic: no device."""
+    params = dict(SequentialPresetA().lrp_params)
+    params.update(lrp_params or {})
+    lrp_modules.alpha_beta_params(params)
+    return params
+
+
+def add_lrp(model, lrp_params=None):
     """Attach `model.compute_lrp`.  Leaf -> rule as in lrp_wrapper.py:42-56 (Conv2d/MaxPool2d: alpha_beta,
-    ReLU: identity); unknown leaves raise ValueError like `get_lrp_module`."""
+    ReLU: identity); unknown leaves raise ValueError like `get_lrp_module`.
+    lrp_params: a dict laid over the preset {"alpha": 1., "beta": 0., "ignore_bias": True}, kept on the model and handed to every
+    rule (Conv2d reads all three, Linear `ignore_bias`); `add_lrp(model)` is the preset.  A model that matches the VGG16 encoder:
+    the preset runs the fused chain; ignore_bias=True with any other alpha / beta the batched `ops.Vgg16.relevance_alpha_beta`;
+    ignore_bias=False the generic leaf driver - correct, layer by layer through the rule classes, not fast."""
+    params = merge_lrp_params(lrp_params)
     leaves = _leaves(model)
     for m in leaves:
         lrp_modules.get_lrp_module(m)                     # ValueError("Layer type ... not known.")
-    if not _match_vgg16(leaves):
+        if isinstance(m, nn.Conv2d):
+            lrp_modules.conv_rule_params(m, params)       # ValueError: ignore_bias=False on a conv without bias
+    model._lrpx_params = params
+    if not _match_vgg16(leaves) or not params["ignore_bias"]:
         return _add_lrp_generic(model, leaves)
+    old = model.__dict__.pop("_lrpx_hooks", None)         # (a generic driver installed by an earlier add_lrp(..., ignore_bias=False))
+    for h in old or ():
+        h.remove()
     convs = [m for m in leaves if isinstance(m, nn.Conv2d)]
     dev = convs[0].weight.device
     if dev.type != "cuda":
@@ -90,7 +113,8 @@ def compute_lrp(model, sample, target=None, return_output=False, rectify_logits=
         x = sample.detach().to(torch.float32).contiguous()
         feats = ctx.forward(x)                                   # (N,196,512) NHWC
         t_nhwc = ops.nchw_to_nhwc(target.detach().to(torch.float32))
-        r = ctx.relevance(t_nhwc, None)
+        alpha, beta, _ = lrp_modules.alpha_beta_params(getattr(model, "_lrpx_params", None))
+        r = ctx.relevance(t_nhwc, None) if (alpha, beta) == (1., 0.) else ctx.relevance_alpha_beta(t_nhwc, None, alpha, beta)
     if sample.grad is None:
         sample.grad = r
     else:
@@ -144,7 +168,7 @@ def _compute_lrp_generic(model, sample, target, return_output):
     lib = _lib.load()
     if sample.device.type != "cuda":
         raise _lib.LrpxError("compute_lrp: the sample must live on the GPU (no CPU path)")
-    preset = SequentialPresetA()
+    lrp_params = getattr(model, "_lrpx_params", None) or SequentialPresetA().lrp_params
     tape = model._lrpx_tape
     del tape[:]
     with torch.no_grad():
@@ -167,7 +191,7 @@ def _compute_lrp_generic(model, sample, target, return_output):
         rule = lrp_modules.get_lrp_module(module)
         # `relevance_input` only fixes the arity of the rule's result (lrp_modules.py:157-170): one entry per module input,
         # the incoming relevance first (the identity gradient of Dropout in eval mode, :248-254)
-        r_in = rule.propagate_relevance(module, (r_out,) + (None,) * 2, (r_out,), _rule_name(module), lrp_params=preset.lrp_params)
+        r_in = rule.propagate_relevance(module, (r_out,) + (None,) * 2, (r_out,), _rule_name(module), lrp_params=lrp_params)
         tensors_in = [t for t in inputs if isinstance(t, torch.Tensor)]
         if isinstance(rule, lrp_modules.Linear):          # the reference's Linear returns (grad_bias slot, R, grad_weight slot)
             r_in = (r_in[1],)

@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("LRPX_LIB_PATH") or os.path.join(_HERE, "csrc", "liblr
 
 OK, EINVAL, EARCH, ELAUNCH, ENONFINITE, EZERO = range(6)
 PACK_FWD_DUAL, PACK_BWD_POS, PACK_BWD_FIRST, PACK_BWD_PLAIN, PACK_DENSE_T, PACK_DENSE, PACK_FWD, PACK_FWD_DUAL_FIRST = range(8)
+PACK_FWD_PN, PACK_FWD_PN_FIRST, PACK_BWD_PN, PACK_BWD_PN_FIRST = range(8, 12)      # the general alpha-beta rule (include/lrpx.h)
 EPI_FWD_DUAL, EPI_REL, EPI_FIRST, EPI_PLAIN, EPI_GUIDED, EPI_REL_MUL = range(6)
 STAB_NONE, STAB_SAFE, STAB_EPS = range(3)
 
@@ -103,6 +104,8 @@ SIGNATURES = {
     "lrpx_maxpool2x2_fwd": (_i, [_f, _f, _i, _i, _i, _i, _f]),
     "lrpx_maxpool2x2_relevance": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f]),
     "lrpx_divide_stab": (_i, [_f, _f, _f, _f, _i, _l, _i, _f]),
+    "lrpx_divide_alpha_beta": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, C.c_float, C.c_float, _f]),
+    "lrpx_maxpool2x2_relevance_ab": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, C.c_float, C.c_float, _f]),
     "lrpx_pool_winner": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _f]),
     "lrpx_unpool_winner": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _f]),
     "lrpx_aoa_grad_init": (_i, [C.POINTER(AoaTrace), C.POINTER(AoaGradState), _f, _f, _i, _f]),

@@ -48,6 +48,7 @@ int launch_conv_28_16_1_4_9_guided(const ConvArgs& a, hipStream_t s);
 int launch_conv_28_16_1_4_9_plain(const ConvArgs& a, hipStream_t s);
 int launch_conv_14_16_1_4_9_guided(const ConvArgs& a, hipStream_t s);
 int launch_conv_14_16_1_4_9_plain(const ConvArgs& a, hipStream_t s);
+int launch_conv_224_8_1_4_9_plain(const ConvArgs& a, hipStream_t s);       // Z+ / Z- of the alpha-beta rule at 224 x 224
 
 int launch_x6_56_rel(const ConvArgs& a, hipStream_t s);
 int launch_x6_28_rel(const ConvArgs& a, hipStream_t s);

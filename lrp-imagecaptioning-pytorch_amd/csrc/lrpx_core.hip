@@ -140,6 +140,31 @@ __global__ void pack_weights_kernel(const float* __restrict__ w, float* __restri
         case LRPX_PACK_DENSE_T:    // W is (k = cout rows, n = cin cols): B[k][oc] = W[k][oc]
             if (k < cout && oc < cin) v = w[(long)k * cin + oc];
             break;
+        // the general alpha-beta rule: PosNetConv and NegNetConv (lrp_modules.py:56-122) stacked along the channel axis
+        case LRPX_PACK_FWD_PN:     // x >= 0: oc in [0,cout) = W+ (Z+), [cout,2cout) = W- (Z-)
+            if (k < cin && oc < 2 * cout) {
+                float x = w[((long)(oc < cout ? oc : oc - cout) * cin + k) * taps + tap];
+                v = oc < cout ? fmaxf(x, 0.f) : fminf(x, 0.f);
+            }
+            break;
+        case LRPX_PACK_FWD_PN_FIRST:   // input [x+ | x-]: Z+ = x+ W+ + x- W-, Z- = x+ W- + x- W+
+            if (k < 2 * cin && oc < 2 * cout) {
+                float x = w[((long)(oc < cout ? oc : oc - cout) * cin + (k < cin ? k : k - cin)) * taps + tap];
+                v = ((k < cin) == (oc < cout)) ? fmaxf(x, 0.f) : fminf(x, 0.f);
+            }
+            break;
+        case LRPX_PACK_BWD_PN:     // GEMM k in [0,cout): rows of alpha S+ (W+), [cout,2cout): rows of -beta S- (W-); oc = ci, kernel flipped
+            if (k < 2 * cout && oc < cin) {
+                float x = w[((long)(k < cout ? k : k - cout) * cin + oc) * taps + (taps - 1 - tap)];
+                v = k < cout ? fmaxf(x, 0.f) : fminf(x, 0.f);
+            }
+            break;
+        case LRPX_PACK_BWD_PN_FIRST:   // ... oc in [0,cin): column of x+, [cin,2cin): column of x-
+            if (k < 2 * cout && oc < 2 * cin) {
+                float x = w[((long)(k < cout ? k : k - cout) * cin + (oc < cin ? oc : oc - cin)) * taps + (taps - 1 - tap)];
+                v = ((k < cout) == (oc < cin)) ? fmaxf(x, 0.f) : fminf(x, 0.f);
+            }
+            break;
         case LRPX_PACK_DENSE:      // W is (n = cout rows, k = cin cols): B[k][oc] = W[oc][k]
             if (k < cin && oc < cout) v = w[(long)oc * cin + k];
             break;
@@ -447,6 +472,10 @@ static void pack_dims(int cout, int cin, int mode, int kc, int* n_oc_pad, int* k
         case LRPX_PACK_BWD_POS: case LRPX_PACK_BWD_PLAIN: n_oc = cin; k = cout; break;
         case LRPX_PACK_BWD_FIRST: n_oc = 2 * cin; k = cout; break;
         case LRPX_PACK_DENSE_T: n_oc = cin; k = cout; break;
+        case LRPX_PACK_FWD_PN: n_oc = 2 * cout; k = cin; break;
+        case LRPX_PACK_FWD_PN_FIRST: n_oc = 2 * cout; k = 2 * cin; break;
+        case LRPX_PACK_BWD_PN: n_oc = cin; k = 2 * cout; break;
+        case LRPX_PACK_BWD_PN_FIRST: n_oc = 2 * cin; k = 2 * cout; break;
         default: n_oc = cout; k = cin; break;  // DENSE
     }
     *n_oc_pad = round_up(n_oc, 32);
@@ -701,6 +730,69 @@ __global__ void divide_stab_kernel(const float* __restrict__ r, const float* __r
     if (amax) amax_commit(amax, n, mabs);
 }
 
+// The two divisions of the general alpha-beta rule in one pass: s2[row][0..c) = alpha * (r / safe(z+)), s2[row][c..2c) = -beta * (r / safe(z-)).
+// One thread = one float4 of r (64-bit index: S2 of conv1_2 for 320 maps is 2.06e9 floats); HBM-bound, 16-byte loads and stores.
+// IEEE division and one multiplication per element - the same two roundings as the expression written in fp32 anywhere else.
+__device__ __forceinline__ f32x4 ab_quot(const f32x4 r, const f32x4 z, const float f) {
+    f32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = f * (r[e] / stab_safe(z[e]));
+    return o;
+}
+__global__ void divide_alpha_beta_kernel(const float* __restrict__ r, const float* __restrict__ zpos, const float* __restrict__ zneg,
+                                         const int* __restrict__ map2img, float* __restrict__ s2, long per4, int c4, float alpha,
+                                         float nbeta, long total) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;   // float4 units over n_maps * per4, per4 = pix * c4
+    if (idx >= total) return;
+    const long n = idx / per4;
+    const long zi = (map2img ? (long)map2img[n] : n) * per4 + (idx - n * per4);
+    const long row = idx / c4;
+    const int cc = (int)(idx - row * c4);
+    const f32x4 rv = reinterpret_cast<const f32x4*>(r)[idx];
+    const f32x4 zp = reinterpret_cast<const f32x4*>(zpos)[zi], zn = reinterpret_cast<const f32x4*>(zneg)[zi];
+    f32x4* o = reinterpret_cast<f32x4*>(s2) + row * (2 * c4) + cc;
+    o[0] = ab_quot(rv, zp, alpha);
+    o[c4] = ab_quot(rv, zn, nbeta);
+}
+
+// Pool2d rule + those two divisions by the Z+ / Z- of the conv below the pool (the two-divisor sibling of maxpool_relevance_kernel:
+// same winner rule).  One thread = one hi-res pixel x 4 channels.
+__global__ void maxpool_relevance_ab_kernel(const float* __restrict__ x, const float* __restrict__ r_out, const float* __restrict__ zpos,
+                                            const float* __restrict__ zneg, const int* __restrict__ map2img, float* __restrict__ s2,
+                                            int ho, int wo, int c4, float alpha, float nbeta, long total) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;   // over n_maps*(2ho)*(2wo)*c4
+    if (idx >= total) return;
+    const int wi = 2 * wo, hi = 2 * ho;
+    const int cc = (int)(idx % c4);
+    long t = idx / c4;
+    const long row = t;
+    const int xi = (int)(t % wi); t /= wi;
+    const int yi = (int)(t % hi);
+    const long n = t / hi;
+    const long img = map2img ? (long)map2img[n] : n;
+    const int yo = yi >> 1, xo = xi >> 1;
+    const int pos = (yi & 1) * 2 + (xi & 1);   // position of this pixel inside its window, row-major
+    const f32x4* xb = reinterpret_cast<const f32x4*>(x) + ((img * hi + 2 * yo) * wi + 2 * xo) * c4 + cc;
+    const f32x4 w4[4] = {xb[0], xb[c4], xb[(long)wi * c4], xb[(long)wi * c4 + c4]};
+    const f32x4 ro = reinterpret_cast<const f32x4*>(r_out)[((n * ho + yo) * wo + xo) * c4 + cc];
+    const long zi = ((img * hi + yi) * wi + xi) * c4 + cc;
+    const f32x4 zp = reinterpret_cast<const f32x4*>(zpos)[zi], zn = reinterpret_cast<const f32x4*>(zneg)[zi];
+    f32x4 ri;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        // first maximum in row-major window order wins (strict >), as max_pool2d's backward does
+        float m = w4[0][e];
+        int am = 0;
+        if (w4[1][e] > m) { m = w4[1][e]; am = 1; }
+        if (w4[2][e] > m) { m = w4[2][e]; am = 2; }
+        if (w4[3][e] > m) { m = w4[3][e]; am = 3; }
+        ri[e] = am == pos ? m * (ro[e] / stab_safe(m)) : 0.f;
+    }
+    f32x4* o = reinterpret_cast<f32x4*>(s2) + row * (2 * c4) + cc;
+    o[0] = ab_quot(ri, zp, alpha);
+    o[c4] = ab_quot(ri, zn, nbeta);
+}
+
 // S = R / safe(Z+) at the top of the mode-3 chain, written BLOCKED (blocked.h) with the per-map maxima.
 // r: [n_maps][P][C] NHWC, z: [n_img][P][C].  A wave moves 8 pixels x 32 channels per step: 8 lanes read one pixel's 128 contiguous
 // bytes (whole lines in), and write per (16-channel chunk, 4-channel part) 8 pixels x 16 bytes = one 128-byte run (whole lines out).
@@ -933,7 +1025,7 @@ using namespace lrpx;
 
 extern "C" {
 
-int lrpx_version(void) { return 100; }
+int lrpx_version(void) { return 101; }
 
 const char* lrpx_last_error_string(void) { return g_err; }
 
@@ -946,7 +1038,7 @@ int lrpx_pack_weights(const float* w, int cout, int cin, int taps, int mode, int
     LRPX_REQUIRE(w && packed, "pack_weights: null pointer");
     LRPX_REQUIRE(taps == 9 || taps == 1, "pack_weights: taps must be 1 or 9");
     LRPX_REQUIRE(kc == 8 || kc == 16 || kc == 32, "pack_weights: kc must be 8, 16 or 32");
-    LRPX_REQUIRE(mode >= 0 && mode <= LRPX_PACK_FWD_DUAL_FIRST, "pack_weights: unknown mode %d", mode);
+    LRPX_REQUIRE(mode >= 0 && mode <= LRPX_PACK_BWD_PN_FIRST, "pack_weights: unknown mode %d", mode);
     int n_oc_pad, k_pad;
     pack_dims(cout, cin, mode, kc, &n_oc_pad, &k_pad);
     long total = (long)n_oc_pad * k_pad * taps;
@@ -1077,6 +1169,34 @@ int lrpx_maxpool2x2_relevance(const float* x, const float* r_out, const float* z
     LRPX_CHECK_PTRS("lrpx_maxpool2x2_relevance", {x, "x"}, {r_out, "r_out"}, {zdiv, "zdiv"}, {map2img, "map2img"}, {r_in, "r_in"}, {s_out, "s_out"});
     return maxpool_relevance_amax(x, r_out, zdiv, map2img, r_in, s_out, n_maps, h_out, w_out, c, s_chunk, nullptr,
                                   (hipStream_t)stream);
+}
+
+int lrpx_divide_alpha_beta(const float* r, const float* zpos, const float* zneg, const int32_t* map2img, float* s2,
+                           int n_maps, int pix, int c, float alpha, float beta, void* stream) {
+    LRPX_CHECK_PTRS("lrpx_divide_alpha_beta", {r, "r"}, {zpos, "zpos"}, {zneg, "zneg"}, {map2img, "map2img"}, {s2, "s2"});
+    LRPX_REQUIRE(r && zpos && zneg && s2, "divide_alpha_beta: null pointer");
+    LRPX_REQUIRE(n_maps > 0 && pix > 0 && c > 0 && c % 4 == 0, "divide_alpha_beta: bad sizes (n_maps=%d pix=%d c=%d, c %% 4 == 0)", n_maps, pix, c);
+    LRPX_REQUIRE(isfinite(alpha) && isfinite(beta), "divide_alpha_beta: alpha / beta must be finite");
+    const long per4 = (long)pix * (c / 4), total = (long)n_maps * per4;
+    LRPX_REQUIRE(ceil_div(total, 256) < 0x7fffffffL, "divide_alpha_beta: too many elements for one launch");
+    hipLaunchKernelGGL(divide_alpha_beta_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, r, zpos, zneg, map2img, s2,
+                       per4, c / 4, alpha, -beta, total);
+    return check_launch("divide_alpha_beta");
+}
+
+int lrpx_maxpool2x2_relevance_ab(const float* x, const float* r_out, const float* zpos, const float* zneg,
+                                 const int32_t* map2img, float* s2, int n_maps, int h_out, int w_out, int c, float alpha,
+                                 float beta, void* stream) {
+    LRPX_CHECK_PTRS("lrpx_maxpool2x2_relevance_ab", {x, "x"}, {r_out, "r_out"}, {zpos, "zpos"}, {zneg, "zneg"}, {map2img, "map2img"}, {s2, "s2"});
+    LRPX_REQUIRE(x && r_out && zpos && zneg && s2, "maxpool2x2_relevance_ab: null pointer");
+    LRPX_REQUIRE(n_maps > 0 && h_out > 0 && w_out > 0 && c > 0 && c % 4 == 0,
+                 "maxpool2x2_relevance_ab: bad sizes (n_maps=%d h_out=%d w_out=%d c=%d, c %% 4 == 0)", n_maps, h_out, w_out, c);
+    LRPX_REQUIRE(isfinite(alpha) && isfinite(beta), "maxpool2x2_relevance_ab: alpha / beta must be finite");
+    const long total = (long)n_maps * (2 * h_out) * (2 * w_out) * (c / 4);
+    LRPX_REQUIRE(ceil_div(total, 256) < 0x7fffffffL, "maxpool2x2_relevance_ab: too many elements for one launch");
+    hipLaunchKernelGGL(maxpool_relevance_ab_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, r_out, zpos, zneg,
+                       map2img, s2, h_out, w_out, c / 4, alpha, -beta, total);
+    return check_launch("maxpool2x2_relevance_ab");
 }
 
 size_t lrpx_blocked_floats(long n_pix, int c) { return (size_t)blk_floats(n_pix, c); }

@@ -296,6 +296,7 @@ int conv_dispatch(const lrpx_conv_desc* d, hipStream_t s, int f16_ksplit) {
             if (e == EPI_FWD_DUAL) return launch_conv_224_8_1_4_9_fwd_dual(a, s);
             if (e == EPI_REL) return launch_conv_224_8_2_2_9_rel(a, s);
             if (e == EPI_GUIDED) return launch_conv_224_8_2_2_9_guided(a, s);
+            if (e == EPI_PLAIN) return launch_conv_224_8_1_4_9_plain(a, s);
             break;
         case 112:
             if (e == EPI_FWD_DUAL) return launch_conv_112_8_1_4_9_fwd_dual(a, s);

@@ -33,6 +33,10 @@ def pack_weights(w, cout, cin, taps, mode, kc):
         n_oc, k = cin, cout
     elif mode == PACK_BWD_FIRST:
         n_oc, k = 2 * cin, cout
+    elif mode in (_lib.PACK_FWD_PN, _lib.PACK_FWD_PN_FIRST):
+        n_oc, k = 2 * cout, (cin if mode == _lib.PACK_FWD_PN else 2 * cin)
+    elif mode in (_lib.PACK_BWD_PN, _lib.PACK_BWD_PN_FIRST):
+        n_oc, k = (cin if mode == _lib.PACK_BWD_PN else 2 * cin), 2 * cout
     else:
         n_oc, k = cout, cin
     n = lib.lrpx_packed_floats(n_oc, k, taps, kc)
@@ -223,6 +227,25 @@ def divide_stab(r, z, map2img, stab):
     return s
 
 
+def divide_alpha_beta(r, zpos, zneg, map2img, alpha, beta, out=None):
+    """r (n_maps, pix, c), zpos / zneg (n_img, pix, c) -> s2 (n_maps, pix, 2c) = [alpha r/safe(z+) | -beta r/safe(z-)]: the two divisions
+    of the general alpha-beta Conv2d rule in one pass (lrpx_divide_alpha_beta)"""
+    n, pix, c = r.shape
+    s2 = torch.empty(n, pix, 2 * c, dtype=torch.float32, device=r.device) if out is None else out
+    check(_lib.load().lrpx_divide_alpha_beta(ptr(_dev(r)), ptr(_dev(zpos)), ptr(_dev(zneg)), ptr(map2img), ptr(s2), n, pix, c,
+                                             float(alpha), float(beta), stream_ptr()))
+    return s2
+
+
+def maxpool2x2_relevance_ab(x, r_out, zpos, zneg, map2img, n_maps, h_out, w_out, c, alpha, beta, out=None):
+    """the Pool2d rule fused with `divide_alpha_beta` by the Z+ / Z- of the conv below the pool: x, zpos, zneg (n_img, 4 h_out w_out, c),
+    r_out (n_maps, h_out w_out, c) -> s2 (n_maps, 4 h_out w_out, 2c)  (lrpx_maxpool2x2_relevance_ab)"""
+    s2 = torch.empty(n_maps, 4 * h_out * w_out, 2 * c, dtype=torch.float32, device=x.device) if out is None else out
+    check(_lib.load().lrpx_maxpool2x2_relevance_ab(ptr(_dev(x)), ptr(_dev(r_out)), ptr(_dev(zpos)), ptr(_dev(zneg)), ptr(map2img), ptr(s2),
+                                                   n_maps, h_out, w_out, c, float(alpha), float(beta), stream_ptr()))
+    return s2
+
+
 def cumsum_maps(maps, n_img, t_per_img, out=None):
     """running sums over the words of each image: what `explain_caption` returns (lrp_wrapper.py:64-82 quirk)"""
     if out is None:
@@ -330,6 +353,9 @@ class Vgg16:
         self.trace = None
         self.n_img = 0
         self._ws = None
+        self._weights = ws              # (the model's own fp32 tensors where it has them: the alpha-beta packs are built from these on demand)
+        self._ab = None                 # relevance_alpha_beta: packs, Z+ / Z- of the current trace, workspace
+        self._trace_serial = 0
         # per-context matrix-core mode (None = the process default of lrpx_set_conv_mode / lrpx_set_forward_f16): carried in
         # every call (lrpx_vgg16_opts), so contexts with different modes can be in flight on different streams / threads
         self.conv_mode = None
@@ -364,6 +390,7 @@ class Vgg16:
         import copy
         r = copy.copy(self)
         r.trace, r.n_img, r._ws = None, 0, None
+        r._ab, r._trace_serial = None, 0
         if hasattr(r, "_ws_multi"):
             del r._ws_multi
         return r
@@ -378,6 +405,7 @@ class Vgg16:
         if self.trace is None or self.trace.numel() < need or self.n_img != n:
             self.trace = torch.empty(need, dtype=torch.float32, device=self.device)
         self.n_img = n
+        self._trace_serial += 1         # (Z+ / Z- kept by relevance_alpha_beta belong to the previous trace)
         check(lib.lrpx_vgg16_forward_ex(ptr(self.packed), ptr(img_nchw.contiguous()), n, ptr(self.trace), None,
                                         self._opts(), stream_ptr()))
         off = lib.lrpx_vgg16_trace_features(ptr(self.trace), n) - self.trace.data_ptr()
@@ -442,6 +470,128 @@ class Vgg16:
         check(getattr(lib, _fn)(ptr(self.packed), ptr(self.trace), self.n_img, ptr(d_feat_nhwc.contiguous()),
                                 ptr(map2img), n_maps, ptr(self._ws), ptr(out), self._opts(grad=True), stream_ptr()))
         return out
+
+    # ---- the general alpha-beta rule through the encoder --------------------------------------------------------
+    AB_BLOCK = 8        # maps per pass at 224 x 224; the deeper stages take as many maps as the same workspace holds (relevance_alpha_beta)
+    AB_STAGES = ((16, 15, 14), (12, 11, 10), (8, 7, 6), (4, 3), (1, 0))      # conv layers of one map size, top down (a pool between two stages)
+
+    def _ab_state(self):
+        """packs of the 13 conv layers for the general rule (built once per context) and the workspace of one block of maps"""
+        if self._ab is None:
+            lib = _lib.load()
+            st = {"fwd": {}, "bwd": {}, "neg": {}, "serial": -1, "zpos": {}, "zneg": {}}
+            convs = [l for l in range(17) if self.IS_CONV[l]]
+            for l, w in zip(convs, self._weights):
+                hw, cout, cin = self.ACT_DIMS[l][0], int(w.shape[0]), int(w.shape[1])
+                k_in = self.ACT_DIMS[l][1]                 # channels of act[l]: 8 = [x+ | x- | 0 0] for conv1_1, cin above
+                kc_f, kc_b = conv_kc(hw, 9, k_in), conv_kc(hw, 9, 2 * cout)
+                first = l == 0
+                st["fwd"][l] = pack_weights(w, cout, cin, 9, _lib.PACK_FWD_PN_FIRST if first else _lib.PACK_FWD_PN, kc_f)
+                st["bwd"][l] = pack_weights(w, cout, cin, 9, _lib.PACK_BWD_PN_FIRST if first else _lib.PACK_BWD_PN, kc_b)
+                st["neg"][l] = lib.lrpx_packed_floats(cout, k_in, 9, kc_f)      # channel-block major: where the Z- half starts
+            self._ab = st
+        return self._ab
+
+    def _ab_zpn(self, st):
+        """Z+ = conv(x, W+) and Z- = conv(x, W-) of the 13 conv layers from the trace's activations, per IMAGE (conv1_1 on the split
+        image: Z+ = x+ W+ + x- W-, Z- = x+ W- + x- W+); kept until the next forward()."""
+        if st["serial"] == self._trace_serial:
+            return
+        acts, _ = self.trace_views()
+        n = self.n_img
+        for l in st["fwd"]:
+            hw, k_in = self.ACT_DIMS[l]
+            cout = self.ACT_DIMS[l + 1][1]
+            for name, pk in (("zpos", st["fwd"][l]), ("zneg", st["fwd"][l][st["neg"][l]:])):
+                z = st[name].get(l)
+                if z is None or z.shape[0] != n:
+                    z = st[name][l] = torch.empty(n, hw * hw, cout, dtype=torch.float32, device=self.device)
+                conv_mfma(acts[l], pk, n, hw, k_in, cout, 9, EPI_PLAIN, oc_split=cout, out0=z)
+        st["serial"] = self._trace_serial
+
+    def relevance_alpha_beta(self, r_feat_nhwc, map2img=None, alpha=2., beta=1., out=None, layer_ms=None):
+        """compute_lrp (LRPtools/lrp_wrapper.py:63-87) with the preset's Conv2d rule replaced by the general alpha-beta rule without
+        bias, R = alpha * lrp_backward(PosNetConv) - beta * lrp_backward(NegNetConv) (lrp_modules.py:124-150), for N maps:
+        (N,196,512) -> (N,3,224,224); maps of one image share that image's trace through `map2img` (null = map n on image n), the
+        same contract as `relevance()`.  ReLU passes relevance through, MaxPool2d routes it to the first maximum (:172-195).
+
+        Z+ / Z- of the 13 conv layers come from the trace's activations, one pass per layer per IMAGE at the first call after a
+        `forward()` (about 108 MB per image, kept until the next `forward()`).  Then per layer, top down: [alpha R/safe(Z+) |
+        -beta R/safe(Z-)] in one pass (fused with the Pool2d rule under the four pools), and ONE transposed conv over the stacked
+        K = 2 cout with the activations as multiplicand.  Every contraction is the fp32 MFMA (`lrpx_conv_mfma` without split
+        operands) whatever the process's or the context's conv mode is: the grade of conv mode 0.
+
+        The maps are walked in blocks so that the workspace is bounded whatever N is: AB_BLOCK = 8 maps at 224 x 224, where S2 of
+        conv1_2 is 25.7 MB per map, and at the deeper stages as many maps as fit the same S2 buffer (16 at 112^2, 32 at 56^2, 64 at
+        28^2, 256 at 14^2 - 8 maps of 14 x 14 pixels are 28 workgroups, a launch that leaves most of the chip idle).  A stage hands
+        its blocks on to the stage below, so each of the five stages owns two relevance buffers of 8 x 224^2 x 64 floats beside
+        the one S2 buffer of 8 x 224^2 x 128 floats: 8 x 224^2 x (128 + 10 x 64) x 4 = 1 233 125 376 bytes.  A map's result does
+        not depend on the blocks it travels in.
+        layer_ms: a list of 17 floats - the call then adds each layer's milliseconds (HIP events, one wait per layer: profiling)."""
+        alpha, beta = float(alpha), float(beta)
+        if not (alpha == alpha and beta == beta and abs(alpha) != float("inf") and abs(beta) != float("inf")):
+            raise ValueError("relevance_alpha_beta: alpha and beta must be finite")
+        if self.trace is None:
+            raise ValueError("relevance_alpha_beta: no trace - call forward() first")
+        r_feat_nhwc = _dev(r_feat_nhwc).contiguous()
+        n_maps = r_feat_nhwc.shape[0]
+        if tuple(r_feat_nhwc.shape[1:]) != (196, 512):
+            raise ValueError("relevance_alpha_beta: r_feat_nhwc must be (N, 196, 512)")
+        if map2img is None:
+            if n_maps != self.n_img:
+                raise ValueError("relevance_alpha_beta: without map2img there is one map per image of the trace")
+            map2img = torch.arange(n_maps, dtype=torch.int32, device=self.device)
+        st = self._ab_state()
+        self._ab_zpn(st)
+        if out is None:
+            out = torch.empty(n_maps, 3, 224, 224, dtype=torch.float32, device=self.device)
+        px = int(self.AB_BLOCK) * 224 * 224
+        ws = st.get("ws")
+        if ws is None or ws.numel() != px * (128 + 64 * 2 * len(self.AB_STAGES)):
+            ws = st["ws"] = torch.empty(px * (128 + 64 * 2 * len(self.AB_STAGES)), dtype=torch.float32, device=self.device)
+        self._ab_walk(st, 0, r_feat_nhwc, map2img.contiguous(), out, alpha, beta, layer_ms, self.trace_views()[0], px)
+        return out
+
+    def _ab_walk(self, st, si, r_in, map2img, out, alpha, beta, layer_ms, acts, px):
+        """stage `si` of relevance_alpha_beta for the maps of r_in - the relevance at the output of the stage's top conv or, with a
+        pool above it, behind that pool - block by block, each block handed on to the stage below; the last stage writes `out`"""
+        lib = _lib.load()
+        layers = self.AB_STAGES[si]
+        ws = st["ws"]
+        s2_ws = ws[:px * 128]
+        r_ws = [ws[px * (128 + 64 * (2 * si + k)): px * (128 + 64 * (2 * si + k + 1))] for k in (0, 1)]
+        hw = self.ACT_DIMS[layers[0]][0]
+        block = min(px * 128 // (hw * hw * 2 * self.ACT_DIMS[l + 1][1]) for l in layers)
+        for lo in range(0, r_in.shape[0], block):
+            nb = min(block, r_in.shape[0] - lo)
+            r, m2i = r_in[lo: lo + nb], map2img[lo: lo + nb]
+            cur = 0
+            for l in layers:
+                if layer_ms is not None:
+                    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                    ev[0].record()
+                k_in, cout = self.ACT_DIMS[l][1], self.ACT_DIMS[l + 1][1]
+                s2 = s2_ws[: nb * hw * hw * 2 * cout].view(nb, hw * hw, 2 * cout)
+                if l + 1 < 17 and not self.IS_CONV[l + 1]:          # r is the relevance BEHIND the pool above this conv
+                    maxpool2x2_relevance_ab(acts[l + 1], r, st["zpos"][l], st["zneg"][l], m2i, nb, hw // 2, hw // 2, cout, alpha, beta, out=s2)
+                else:
+                    divide_alpha_beta(r, st["zpos"][l], st["zneg"][l], m2i, alpha, beta, out=s2)
+                r_new = r_ws[cur][: nb * hw * hw * k_in].view(nb, hw * hw, k_in)
+                conv_mfma(s2, st["bwd"][l], nb, hw, 2 * cout, -(-k_in // 32) * 32, 9, EPI_REL, oc_split=k_in, x=acts[l], map2img=m2i, out0=r_new)
+                r, cur = r_new, 1 - cur
+                if layer_ms is not None:
+                    ev[1].record()
+                    ev[1].synchronize()
+                    layer_ms[l] += ev[0].elapsed_time(ev[1])
+            if si + 1 < len(self.AB_STAGES):
+                self._ab_walk(st, si + 1, r, m2i, out[lo: lo + nb], alpha, beta, layer_ms, acts, px)
+                continue
+            # conv1_1 left [x+ convT(.) | x- convT(.) | 0 0] in 8 channels: join the halves into the NCHW result
+            tmp = r_ws[cur][: nb * 3 * 224 * 224].view(nb, 3, 224, 224)
+            o = out[lo: lo + nb]
+            check(lib.lrpx_nhwc_to_nchw(ptr(r), ptr(o), nb, 3, 224 * 224, 8, stream_ptr()))
+            check(lib.lrpx_nhwc_to_nchw(_lib.ptr_at(r, 3), ptr(tmp), nb, 3, 224 * 224, 8, stream_ptr()))
+            check(lib.lrpx_accumulate(ptr(o), ptr(tmp), o.numel(), stream_ptr()))
 
     def relevance(self, r_feat_nhwc, map2img=None, out=None, streams=1, layer_ms=None):
         """compute_lrp (LRPtools/lrp_wrapper.py:63-87) for N maps: (N,196,512) -> (N,3,224,224).
