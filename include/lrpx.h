@@ -32,7 +32,10 @@ enum {
     LRPX_EZERO = 5        /* all-zero relevance (reference: `assert sample.grad.sum()!=0`, lrp_wrapper.py:81) */
 };
 
-/* 101: the alpha-beta Conv2d rule (LRPX_PACK_*_PN*, lrpx_divide_alpha_beta, lrpx_maxpool2x2_relevance_ab); 100 before it */
+/* The runtime-geometry conv engine and the general MaxPool2d rule (lrpx_conv_geom, lrpx_conv_geom_pack,
+ * lrpx_conv_geom_packed_floats, lrpx_maxpool_rule) came WITHOUT a new version number: a caller detects them by the presence
+ * of the symbols (dlsym / hasattr on the loaded library).
+ * 101: the alpha-beta Conv2d rule (LRPX_PACK_*_PN*, lrpx_divide_alpha_beta, lrpx_maxpool2x2_relevance_ab); 100 before it */
 int lrpx_version(void);
 const char* lrpx_last_error_string(void);
 /* "" for a release build.  Otherwise the list of timing-experiment / profiling switches the library was compiled with
@@ -144,6 +147,30 @@ typedef struct lrpx_conv_desc {
  * the fused epilogues of the relevance rules.  Replaces F.conv2d / conv backward inside
  * LRPtools/utils.py:21-31 `lrp_backward` and torch.matmul/sum inside `lrp_linear_eps`. */
 int lrpx_conv_mfma(const lrpx_conv_desc* d, void* stream);
+
+/* ---- the contraction engine at any conv geometry (csrc/conv_geom.hip; the ResNet encoders' 7x7 s2, 1x1, 1x1 s2, 3x3 s2) ------ */
+enum { LRPX_GEOM_FWD = 0,   /* out[n,oh,ow,co] = sum in[n, oh*sh-ph+r, ow*sw-pw+s, ci] * w[co,ci,r,s] (+ bias[co]) */
+       LRPX_GEOM_BWD = 1 }; /* the transposed conv autograd runs inside lrp_backward (LRPtools/utils.py:21-31), times x:
+                               out[n,h,w,ci] = x[n,h,w,ci] * sum in[n,oh,ow,co] * w[co,ci,r,s] over oh*sh-ph+r = h, ow*sw-pw+s = w */
+typedef struct lrpx_conv_geom_desc {
+    const float* in;       /* FWD: [n*h*w][k];  BWD: [n*oh*ow][k] (S of the rule).  16-byte aligned, k %% 4 == 0 */
+    const float* wpacked;  /* lrpx_conv_geom_pack of the same direction */
+    const float* bias;     /* FWD only, [n_oc], may be NULL */
+    const float* x;        /* BWD only, [n*h*w][n_oc]: the multiplicand of the epilogue */
+    float* out;            /* FWD: [n*oh*ow][n_oc];  BWD: [n*h*w][n_oc] */
+    int dir;               /* LRPX_GEOM_FWD / LRPX_GEOM_BWD */
+    int n, h, w, oh, ow;   /* h x w: the conv's INPUT map, oh x ow = (h + 2 ph - kh) / sh + 1, ... its output map, in both directions */
+    int kh, kw, sh, sw, ph, pw;   /* dilation 1, groups 1, zero padding */
+    int k, n_oc;           /* contraction channels (row length of `in`) and output channels (row length of out / x); any n_oc */
+} lrpx_conv_geom_desc;
+/* fp32 MFMA (v_mfma_f32_32x32x2_f32), fp32 accumulation: the arithmetic grade of conv mode 0.  BWD tiles the output by sub-pixel
+ * class (h mod sh, w mod sw) and visits only the taps that reach a class; pixels no window covers are exact zeros. */
+int lrpx_conv_geom(const lrpx_conv_geom_desc* d, void* stream);
+/* floats of the packed image for n_oc output channels, k contraction channels, taps = kh * kw */
+size_t lrpx_conv_geom_packed_floats(int n_oc, int k, int taps);
+/* w: (cout, cin, kh, kw) as nn.Conv2d stores it (the caller stacks W+ / W- along either channel axis first).
+ * FWD: k = cin, n_oc = cout;  BWD: k = cout, n_oc = cin. */
+int lrpx_conv_geom_pack(const float* w, int cout, int cin, int kh, int kw, int dir, float* packed, void* stream);
 
 /* ---- elementwise / layout kernels -------------------------------------------------------------- */
 /* NHWC <-> BLOCKED (csrc/blocked.h): n_groups tensors of pix_per_group pixels x c channels (c %% 16 == 0), each its own block set
@@ -631,6 +658,14 @@ int lrpx_add_rule(const float* x1, const float* x2, const float* r_out, float* r
  * bit-exact against the reference. */
 int lrpx_avgpool_rule(const float* x, const float* r_out, float* s_ws, float* r_in, long planes, int h, int w, int oh, int ow,
                       int kh, int kw, int sh, int sw, int ph, int pw, int count_include_pad, int divisor_override, void* stream);
+/* Pool2d.propagate_relevance for nn.MaxPool2d of any kernel / stride / padding / ceil_mode, dilation 1 (LRPtools/lrp_modules.py:174-175,
+ * 182-195): Z = maxpool(x), S = r_out / (Z + 1e-7 [Z == 0]), r_in = x * maxpool^T(S).  x / r_in: (planes, h, w), r_out: (planes, oh, ow),
+ * planes = N * C of the module's NCHW tensors (ceil_mode travels in oh / ow).  Padding is -inf; a window's winner is its FIRST
+ * maximum in ATen's scan order (kernel rows outer, columns inner; a NaN wins); an input pixel that wins several overlapping windows
+ * collects all of them, added in ascending (oh, ow) order as ATen's backward does.  Written as a gather per input pixel over the
+ * windows that contain it: no atomics, no workspace. */
+int lrpx_maxpool_rule(const float* x, const float* r_out, float* r_in, long planes, int h, int w, int oh, int ow, int kh, int kw,
+                      int sh, int sw, int ph, int pw, void* stream);
 /* max |a - b| into one device float (Dropout.propagate_relevance's check, LRPtools/lrp_modules.py:251; NaN counts as inf) */
 int lrpx_max_abs_diff(const float* a, const float* b, long n, float* out_dev, void* stream);
 

@@ -11,7 +11,11 @@ alpha = 1, beta = 0 without bias - the preset of lrp_wrapper.py:7-12 - on the tu
 combination (alpha2beta1, with bias, ...) on the general path beside it.
 
 Conv2d 3x3/pad 1, MaxPool2d(2,2) and ReLU are the layers VGG16 exercises (kernels for square maps of 224/112/56/28/14
-pixels; any other H x W <= 224 runs zero-embedded in the next larger of those; other kernel sizes / strides raise ValueError).  Linear / BatchNorm2d / BatchNorm1d / Dropout / Add / Flatten / AvgPool2d (SURVEY.md §8(a) M4 and W3's table, only
+pixels; any other H x W <= 224 runs zero-embedded in the next larger of those).  Every other Conv2d geometry - the 7x7 s2 / 1x1 /
+1x1 s2 / 3x3 s2 of the reference's bottleneck ResNets (models/resnet.py:41-49,164), rectangular kernels, strides and maps - runs the
+same rule on the runtime-geometry engine (csrc/conv_geom.hip); dilation, groups and non-zero padding modes raise
+ValueError (`conv_geometry`).  MaxPool2d with any other window (the stem's MaxPool2d(3, 2, 1), ceil_mode, odd maps) is a gather
+kernel in csrc/lrpx_rules.hip.  Linear / BatchNorm2d / BatchNorm1d / Dropout / Add / Flatten / AvgPool2d (SURVEY.md §8(a) M4 and W3's table, only
 reached with the reference's ResNet encoders) are HBM-bound streaming kernels (csrc/lrpx_rules.hip), any shape."""
 import math
 
@@ -62,6 +66,22 @@ def conv_rule_params(module, lrp_params):
     return alpha, beta, ignore_bias
 
 
+def conv_geometry(module):
+    """(kh, kw, sh, sw, ph, pw) of an nn.Conv2d the rule can run: dilation 1, groups 1, zero padding given as numbers.  ValueError
+    otherwise.  Host logic: no device."""
+    _require(isinstance(module, nn.Conv2d), "lrpx Conv2d rule: an nn.Conv2d, got {}".format(type(module)))
+    _require(not isinstance(module.padding, str), "lrpx Conv2d rule: padding={!r} is not supported, give numbers".format(module.padding))
+    _require(_pair(module.dilation) == (1, 1), "lrpx Conv2d rule: dilation {} is not supported".format(module.dilation))
+    _require(module.groups == 1, "lrpx Conv2d rule: groups={} is not supported".format(module.groups))
+    _require(module.padding_mode == "zeros", "lrpx Conv2d rule: padding_mode={!r} is not supported".format(module.padding_mode))
+    geom = tuple(int(v) for v in _pair(module.kernel_size) + _pair(module.stride) + _pair(module.padding))
+    _require(min(geom[:4]) >= 1 and min(geom[4:]) >= 0, "lrpx Conv2d rule: bad kernel / stride / padding {}".format(geom))
+    return geom
+
+
+_VGG_GEOMETRY = (3, 3, 1, 1, 1, 1)
+
+
 class Conv2d:
     """The alpha-beta rule (lrp_modules.py:124-150), R = alpha * lrp_backward(PosNetConv) - beta * lrp_backward(NegNetConv), for signed
     or non-negative inputs, with `alpha`, `beta`, `ignore_bias` from `lrp_params` (None / missing key: 1, 0, True).
@@ -69,7 +89,9 @@ class Conv2d:
           R_in = x+ * convT(S,W+) + x- * convT(S,W-).  The input is stored split [x+ | x-] so one MFMA pass serves both terms.
       anything else:  Z+ as above (+ b), Z- = conv(x-,W+) + conv(x+,W-) (+ b) - with bias BOTH nets add the whole bias, b+ + b- = b
           (:73-76, :107-110);  S2 = [alpha R/safe(Z+) | -beta R/safe(Z-)] (lrpx_divide_alpha_beta);  R_in = [x+ | x-] * convT(S2, .)
-          with the weight rows [W+ ; W-] stacked like S2 (LRPX_PACK_BWD_PN_FIRST): one contraction with K = 2 cout, fp32 MFMA."""
+          with the weight rows [W+ ; W-] stacked like S2 (LRPX_PACK_BWD_PN_FIRST): one contraction with K = 2 cout, fp32 MFMA.
+    3x3 / pad 1 / stride 1 on maps up to 224 pixels runs the VGG16 kernels; any other geometry (`conv_geometry`) the same contractions
+    on `lrpx_conv_geom` (`_geom`), with the W+ / W- stacks built here before packing."""
 
     def propagate_relevance(self, module, relevance_input, relevance_output, lrp_method, lrp_params=None):
         if lrp_method != "alpha_beta":
@@ -78,10 +100,13 @@ class Conv2d:
         general = not (alpha == 1. and beta == 0. and ignore_bias)
         x = module.input[0].detach()
         r_out = relevance_output[0].detach()
-        _require(isinstance(module, nn.Conv2d) and module.kernel_size == (3, 3) and module.padding == (1, 1)
-                 and module.stride == (1, 1) and module.groups == 1, "lrpx Conv2d rule: 3x3 / pad 1 / stride 1 only")
+        geom = conv_geometry(module)
+        _require(x.dim() == 4 and x.shape[1] == module.in_channels, "lrpx Conv2d rule: (N, in_channels, H, W) input")
         n, cin, h0, w0 = x.shape
         cout = module.out_channels
+        if geom != _VGG_GEOMETRY or max(h0, w0) > _SIZES[0]:
+            R = self._geom(module, geom, x, r_out, alpha, beta, ignore_bias)
+            return self._result(R, relevance_input, h0, w0, h0, w0)
         _require(r_out.shape == (n, cout, h0, w0), "relevance_output shape mismatch")
         _require(max(h0, w0) <= _SIZES[0], f"lrpx Conv2d rule: maps of at most {_SIZES[0]}x{_SIZES[0]} pixels, got {h0}x{w0}")
         # The kernels are built for the five square map sizes of VGG16.  Any other H x W runs on the next larger one with
@@ -197,12 +222,84 @@ class Conv2d:
         return ops.nhwc_to_nchw(r_half, cin, h, w)
 
 
+    @staticmethod
+    def _geom(module, geom, x, r_out, alpha, beta, ignore_bias):
+        """the rule at any geometry on `lrpx_conv_geom`: x (n,cin,h,w), r_out (n,cout,oh,ow) -> R (n,cin,h,w).  The input is stored split
+        [x+ | x-] (K = 2 half), the weights stacked to match before packing:
+          preset:  Z = conv([x+ | x-], [W+ | W-]);  S = R / safe(Z);  R_in = fold([x+ | x-] * convT(S, [W+ | W-]))
+          general: Z+ as above (+ b), Z- = conv([x+ | x-], [W- | W+]) (+ b);  S2 = [alpha R/safe(Z+) | -beta R/safe(Z-)];
+                   R_in = fold([x+ | x-] * convT(S2, [[W+ | W-] ; [W- | W+]]))  (K = 2 cout)."""
+        lib = _lib.load()
+        st = stream_ptr()
+        dev = x.device
+        kh, kw, sh, sw, ph, pw = geom
+        n, cin, h, w = x.shape
+        cout = module.out_channels
+        _require(h + 2 * ph >= kh and w + 2 * pw >= kw, "lrpx Conv2d rule: the kernel does not fit the padded input")
+        oh, ow = (h + 2 * ph - kh) // sh + 1, (w + 2 * pw - kw) // sw + 1
+        _require(r_out.shape == (n, cout, oh, ow), "relevance_output shape mismatch")
+        general = not (alpha == 1. and beta == 0. and ignore_bias)
+        half, co_p = _pad_to(cin, 2), _pad_to(cout, 4)      # the engine reads float4s along K; channels beyond are zero weights
+        c2 = 2 * half
+        cache = module.__dict__.setdefault("_lrpx_pack_geom", {})
+        key = (geom, module.weight._version, module.weight.data_ptr())
+        if cache.get("key") != key:
+            cache.clear()
+            cache["key"] = key
+        kind = "general" if general else "preset"
+        if kind not in cache:
+            wt = torch.zeros(co_p, half, kh, kw, device=dev)
+            wt[:cout, :cin] = module.weight.detach().to(torch.float32)
+            wpos, wneg = wt.clamp(min=0), wt.clamp(max=0)
+            zp = torch.cat([wpos, wneg], 1)                  # Z+: W+ on x+, W- on x-  (lrp_modules.py:81-84)
+            if general:
+                zn = torch.cat([wneg, wpos], 1)              # Z-: W- on x+, W+ on x-  (:111-114)
+                cache[kind] = (ops.conv_geom_pack(zp, _lib.GEOM_FWD), ops.conv_geom_pack(zn, _lib.GEOM_FWD),
+                               ops.conv_geom_pack(torch.cat([zp, zn], 0), _lib.GEOM_BWD))
+            else:
+                cache[kind] = (ops.conv_geom_pack(zp, _lib.GEOM_FWD), ops.conv_geom_pack(zp, _lib.GEOM_BWD))
+        xs = torch.empty(n, h * w, c2, device=dev)
+        xsrc = x.to(torch.float32)
+        if half != cin:     # x+ occupies channels [0,half), x- starts at `half`: pad the channel axis with zeros
+            xsrc = torch.cat([xsrc, torch.zeros(n, half - cin, h, w, device=dev)], 1)
+        check(lib.lrpx_nchw_to_nhwc_posneg(ptr(xsrc.contiguous()), ptr(xs), n, half, h * w, c2, st))
+        r_nhwc = ops.nchw_to_nhwc(r_out.to(torch.float32), co_p)
+        fwd = dict(direction=_lib.GEOM_FWD, n=n, hw=(h, w), ohw=(oh, ow), geom=geom, k=c2, n_oc=co_p)
+        if general:
+            pf_pos, pf_neg, pb = cache[kind]
+            bias = None
+            if not ignore_bias:     # both nets add b+ + b- = b (:73-76, :107-110)
+                bias = torch.zeros(co_p, device=dev)
+                bias[:cout] = module.bias.detach().to(torch.float32)
+            zpos = ops.conv_geom(xs, pf_pos, bias=bias, **fwd)
+            zneg = ops.conv_geom(xs, pf_neg, bias=bias, **fwd)
+            s = ops.divide_alpha_beta(r_nhwc, zpos, zneg, None, alpha, beta)
+        else:
+            pf, pb = cache[kind]
+            s = ops.divide_stab(r_nhwc, ops.conv_geom(xs, pf, **fwd), None, STAB_SAFE)
+        r_split = ops.conv_geom(s, pb, _lib.GEOM_BWD, n, (h, w), (oh, ow), geom, s.shape[2], c2, x=xs)
+        r_half = torch.empty(n, h * w, half, device=dev)
+        check(lib.lrpx_fold_halves(ptr(r_split), ptr(r_half), n * h * w, half, st))
+        return ops.nhwc_to_nchw(r_half, cin, h, w)
+
+
 def _pair(v):
     return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
 
 
+def _pool_out(size, k, s, p, ceil_mode):
+    """output length of a pooling window along one axis (ATen's pooling_output_shape, dilation 1)"""
+    num = size + 2 * p - k
+    o = (-(-num // s) if ceil_mode else num // s) + 1
+    if ceil_mode and (o - 1) * s >= size + p:    # the last window must start inside the input or its left padding
+        o -= 1
+    return o
+
+
 class Pool2d:
-    """Pool2d rule (lrp_modules.py:172-195).  MaxPool2d(2,2): winner-take-all routing, first maximum wins.
+    """Pool2d rule (lrp_modules.py:172-195).  MaxPool2d: winner-take-all routing, first maximum wins; MaxPool2d(2,2) on even maps
+    runs the VGG16 kernel, any other kernel / stride / padding / ceil_mode `lrpx_maxpool_rule` (padding is -inf, a pixel that wins several
+    overlapping windows collects all of them); dilation != 1 raises ValueError.
     AvgPool2d (any kernel / stride / padding / count_include_pad / ceil_mode - the attributes the reference clones at :176-177):
     Z = avgpool(X), R = X * avgpool^T(R_out / safe(Z)).  Quirk reproduced: the reference's clone does NOT carry
     `divisor_override`, so its rule divides by the default window size whatever the module says (fixture `k23_div5`)."""
@@ -227,13 +324,20 @@ class Pool2d:
         if isinstance(module, nn.AvgPool2d):
             return self._avgpool(module, relevance_output)
         _require(isinstance(module, nn.MaxPool2d), "lrpx Pool2d rule: MaxPool2d / AvgPool2d only")    # lrp_modules.py:179
-        ks = module.kernel_size if isinstance(module.kernel_size, tuple) else (module.kernel_size,) * 2
-        stq = module.stride if isinstance(module.stride, tuple) else (module.stride,) * 2
-        _require(ks == (2, 2) and stq == (2, 2) and module.padding in (0, (0, 0)), "lrpx Pool2d rule: 2x2 / stride 2 only")
+        ks, pad = _pair(module.kernel_size), _pair(module.padding)
+        stq = _pair(module.stride if module.stride is not None else module.kernel_size)
+        _require(_pair(module.dilation) == (1, 1), "lrpx Pool2d rule: dilation {} is not supported".format(module.dilation))
         x = module.input[0].detach()
         r_out = relevance_output[0].detach()
+        _require(x.dim() == 4 and r_out.dim() == 4, "lrpx Pool2d rule: MaxPool2d on (N, C, H, W) tensors")
         n, c, h, w = x.shape
-        _require(h % 2 == 0 and w % 2 == 0, "lrpx Pool2d rule: even spatial size only")
+        if not (ks == (2, 2) and stq == (2, 2) and pad == (0, 0) and h % 2 == 0 and w % 2 == 0):
+            _require(2 * pad[0] <= ks[0] and 2 * pad[1] <= ks[1], "lrpx Pool2d rule: padding larger than half the kernel")
+            oh, ow = (_pool_out(sz, k, s_, p, module.ceil_mode) for sz, k, s_, p in zip((h, w), ks, stq, pad))
+            _require(r_out.shape == (n, c, oh, ow), "relevance_output shape mismatch")
+            R = ops.maxpool_rule(_f32c(x), _f32c(r_out), ks, stq, pad)
+            ops.check_relevance(R)                                  # lrp_modules.py:192-193
+            return (R,)
         cp = _pad_to(c, 4)
         xs = ops.nchw_to_nhwc(x.to(torch.float32), cp)
         rs = ops.nchw_to_nhwc(r_out.to(torch.float32), cp)

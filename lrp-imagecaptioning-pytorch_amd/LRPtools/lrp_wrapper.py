@@ -10,6 +10,11 @@ relevance pass (lrp_wrapper.py:37-87).  Here `add_lrp` validates the same leaf -
     nets): the model's own forward runs once under forward hooks that keep `module.input` (lrp_wrapper.py:24-25) and
     record the call order; the relevance then walks the recorded calls in reverse through this repo's rule classes
     (lrp_modules.py, HIP kernels), summing where a tensor feeds several modules - what autograd does for the reference.
+    Each rule sees the input of the call it answers for, so one module may be called several times.  This carries the reference's
+    bottleneck ResNets (resnet50 / resnet101: 7x7 s2 stem, MaxPool2d(3, 2, 1), 1x1 / 3x3 s2 / 1x1 blocks with a registered `Add`);
+    their unused `AdaptiveAvgPool2d` leaf is accepted and only refused if a forward reaches it.  `BasicBlock` nets (resnet18 / 34)
+    build an unregistered `Add()` inside `forward` (models/resnet.py:87): no hook sees it, and they stay refused by the
+    "functional code" error below.
 `add_lrp(model, lrp_params=...)` lays a dict over the preset's parameters (the reference's add_lrp has the comment "Override default
 parameters if provided" and no argument): the VGG16 encoder with another alpha / beta and `ignore_bias=True` runs the batched
 `ops.Vgg16.relevance_alpha_beta`, with `ignore_bias=False` the generic driver.
@@ -57,6 +62,12 @@ def _match_vgg16(leaves):
     return i == len(leaves)
 
 
+# The one rule-less leaf type `add_lrp` lets through: the reference's ResNet encoders carry `self.avgpool = nn.AdaptiveAvgPool2d`
+# (models/resnet.py:176) and their forward never calls it (:232-234), so the reference's lazy hooks never notice it.  A recorded forward
+# that does reach one gets the table's ValueError("Layer type ... not known.") from `compute_lrp`.
+_DEFERRED_LEAVES = (nn.AdaptiveAvgPool2d,)
+
+
 def merge_lrp_params(lrp_params=None):
     """`lrp_params` laid over the preset's (lrp_wrapper.py:7-12; the reference's add_lrp carries the comment "Override default
     parameters if provided" where this happens here).  ValueError for a non-finite alpha / beta.  Host logic: no device."""
@@ -76,6 +87,8 @@ def add_lrp(model, lrp_params=None):
     params = merge_lrp_params(lrp_params)
     leaves = _leaves(model)
     for m in leaves:
+        if type(m) in _DEFERRED_LEAVES:
+            continue
         lrp_modules.get_lrp_module(m)                     # ValueError("Layer type ... not known.")
         if isinstance(m, nn.Conv2d):
             lrp_modules.conv_rule_params(m, params)       # ValueError: ignore_bias=False on a conv without bias
@@ -188,7 +201,10 @@ def _compute_lrp_generic(model, sample, target, return_output):
         if r_out is None:
             continue                                      # a leaf whose output does not reach the anchor
         r_out = r_out.view(output.shape)
-        rule = lrp_modules.get_lrp_module(module)
+        rule = lrp_modules.get_lrp_module(module)         # (ValueError for a deferred leaf the forward did reach)
+        # the input of THIS call: a module called several times (the one ReLU of a Bottleneck, models/resnet.py:115-138) otherwise
+        # shows every rule the input of its last call
+        module.input = inputs
         # `relevance_input` only fixes the arity of the rule's result (lrp_modules.py:157-170): one entry per module input,
         # the incoming relevance first (the identity gradient of Dropout in eval mode, :248-254)
         r_in = rule.propagate_relevance(module, (r_out,) + (None,) * 2, (r_out,), _rule_name(module), lrp_params=lrp_params)

@@ -16,6 +16,7 @@ PACK_FWD_DUAL, PACK_BWD_POS, PACK_BWD_FIRST, PACK_BWD_PLAIN, PACK_DENSE_T, PACK_
 PACK_FWD_PN, PACK_FWD_PN_FIRST, PACK_BWD_PN, PACK_BWD_PN_FIRST = range(8, 12)      # the general alpha-beta rule (include/lrpx.h)
 EPI_FWD_DUAL, EPI_REL, EPI_FIRST, EPI_PLAIN, EPI_GUIDED, EPI_REL_MUL = range(6)
 STAB_NONE, STAB_SAFE, STAB_EPS = range(3)
+GEOM_FWD, GEOM_BWD = range(2)                    # directions of lrpx_conv_geom
 
 _f = C.c_void_p      # device pointers travel as void*
 _i = C.c_int
@@ -73,6 +74,13 @@ class ConvDesc(C.Structure):
                 ("out0", _f), ("out1", _f),
                 ("f16x3", _i), ("out_chunk", _i), ("in_amax", _f), ("out1_amax", _f), ("out0_amax", _f), ("pool_am", _f),
                 ("tile_group", _i), ("blocked", _i)]
+
+
+class ConvGeomDesc(C.Structure):
+    """lrpx_conv_geom_desc: the runtime-geometry conv engine (csrc/conv_geom.hip)"""
+    _fields_ = [("in_", _f), ("wpacked", _f), ("bias", _f), ("x", _f), ("out", _f), ("dir", _i),
+                ("n", _i), ("h", _i), ("w", _i), ("oh", _i), ("ow", _i),
+                ("kh", _i), ("kw", _i), ("sh", _i), ("sw", _i), ("ph", _i), ("pw", _i), ("k", _i), ("n_oc", _i)]
 
 
 class VggOpts(C.Structure):
@@ -204,6 +212,10 @@ SIGNATURES = {
     "lrpx_batchnorm_rule": (_i, [_f, _f, _f, _f, _f, _f, C.c_float, _f, _l, _i, _l, _i, _f]),
     "lrpx_add_rule": (_i, [_f, _f, _f, _f, _f, _l, _f]),
     "lrpx_avgpool_rule": (_i, [_f, _f, _f, _f, _l] + [_i] * 12 + [_f]),
+    "lrpx_maxpool_rule": (_i, [_f, _f, _f, _l] + [_i] * 10 + [_f]),
+    "lrpx_conv_geom": (_i, [C.POINTER(ConvGeomDesc), _f]),
+    "lrpx_conv_geom_packed_floats": (_sz, [_i, _i, _i]),
+    "lrpx_conv_geom_pack": (_i, [_f, _i, _i, _i, _i, _i, _f, _f]),
     "lrpx_max_abs_diff": (_i, [_f, _f, _l, _f, _f]),
 }
 

@@ -4,6 +4,7 @@
 //   Add          proportional split, 0.5 / 0.5 on zero sums     LRPtools/lrp_modules.py:256-280
 //   Dropout      |R_out - R_in| < 1e-7 check                    LRPtools/lrp_modules.py:248-254
 //   AvgPool2d    Z = avgpool(X), R = X * avgpool^T(R_out / Z)    LRPtools/lrp_modules.py:172-195 (Pool2d, the nn.AvgPool2d branch)
+//   MaxPool2d    any window: Z = maxpool(X), R = X * maxpool^T(R_out / Z)  LRPtools/lrp_modules.py:172-195 (the 2x2 / stride 2 kernel lives in lrpx_core.hip)
 // (Flatten, :282-291, is a copy: lrpx_scale with factor 1.)
 // All of them are HBM-bound: one streaming pass each, the Linear rule streams W twice (Z = x W^T, then (R/Z) W) with the
 // handful of batch rows held in registers.  Arithmetic follows the reference expression by expression (IEEE division and
@@ -211,6 +212,45 @@ __global__ void avgpool_rule_back_kernel(const float* __restrict__ x, const floa
     r_in[i] = x[i] * grad;
 }
 
+// ---- Pool2d rule for nn.MaxPool2d of any kernel / stride / padding / ceil_mode (lrp_modules.py:174-175 clone, :182-195 rule) ----
+// Z = maxpool(X), S = safe_divide(R_out, Z), Z.backward(S), R = X * X.grad on NCHW planes.  One thread per INPUT pixel: it visits
+// the windows that contain it in ascending (oh, ow) order - the order ATen's backward adds them in - repeats ATen's forward scan of
+// each (padding is skipped = -inf; `val > max || isnan(val)` with kernel rows outer, columns inner: the FIRST maximum wins) and
+// collects S of every window it wins.  A gather: no atomics, overlapping windows need no workspace.
+struct MaxPoolGeom { int H, W, OH, OW, kh, kw, sh, sw, ph, pw; };
+
+__global__ void maxpool_rule_kernel(const float* __restrict__ x, const float* __restrict__ r_out, float* __restrict__ r_in,
+                                    long planes, MaxPoolGeom g) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long per = (long)g.H * g.W;
+    if (i >= planes * per) return;
+    const long pl = i / per;
+    const int p = (int)(i - pl * per), h = p / g.W, w = p - h * g.W;
+    const int oh_lo = max(0, (h + g.ph - g.kh + g.sh) / g.sh), oh_hi = min(g.OH - 1, (h + g.ph) / g.sh);
+    const int ow_lo = max(0, (w + g.pw - g.kw + g.sw) / g.sw), ow_hi = min(g.OW - 1, (w + g.pw) / g.sw);
+    const float* xp = x + pl * per;
+    const float* rp = r_out + pl * g.OH * g.OW;
+    float grad = 0.f;
+    for (int oh = oh_lo; oh <= oh_hi; ++oh) {
+        const int h0 = max(oh * g.sh - g.ph, 0), h1 = min(oh * g.sh - g.ph + g.kh, g.H);
+        for (int ow = ow_lo; ow <= ow_hi; ++ow) {
+            const int w0 = max(ow * g.sw - g.pw, 0), w1 = min(ow * g.sw - g.pw + g.kw, g.W);
+            int win = h0 * g.W + w0;
+            float m = -INFINITY;
+            for (int ih = h0; ih < h1; ++ih)
+                for (int iw = w0; iw < w1; ++iw) {
+                    const float v = xp[ih * g.W + iw];
+                    if (v > m || v != v) {
+                        m = v;
+                        win = ih * g.W + iw;
+                    }
+                }
+            if (win == p) grad += rp[oh * g.OW + ow] / (m + kZEps * (m == 0.f ? 1.f : 0.f));
+        }
+    }
+    r_in[i] = x[i] * grad;
+}
+
 }  // namespace lrpx
 
 using namespace lrpx;
@@ -266,6 +306,22 @@ int lrpx_avgpool_rule(const float* x, const float* r_out, float* s_ws, float* r_
     hipLaunchKernelGGL(avgpool_rule_s_kernel, dim3((unsigned)ceil_div(planes * oh * ow, 256)), dim3(256), 0, st, x, r_out, s_ws, planes, g);
     hipLaunchKernelGGL(avgpool_rule_back_kernel, dim3((unsigned)ceil_div(planes * h * w, 256)), dim3(256), 0, st, x, s_ws, r_in, planes, g);
     return check_launch("avgpool_rule");
+}
+
+int lrpx_maxpool_rule(const float* x, const float* r_out, float* r_in, long planes, int h, int w, int oh, int ow, int kh, int kw,
+                      int sh, int sw, int ph, int pw, void* stream) {
+    LRPX_REQUIRE(x && r_out && r_in, "maxpool_rule: null pointer");
+    LRPX_REQUIRE(planes > 0 && h > 0 && w > 0 && oh > 0 && ow > 0, "maxpool_rule: bad sizes");
+    LRPX_REQUIRE(kh > 0 && kw > 0 && sh > 0 && sw > 0 && ph >= 0 && pw >= 0 && 2 * ph <= kh && 2 * pw <= kw,
+                 "maxpool_rule: bad window (kernel %dx%d stride %dx%d padding %dx%d)", kh, kw, sh, sw, ph, pw);
+    // every window must start inside the image or its left padding (what ATen's output-size rule guarantees, ceil_mode included)
+    LRPX_REQUIRE((long)(oh - 1) * sh < h + ph && (long)(ow - 1) * sw < w + pw, "maxpool_rule: output %dx%d does not fit input %dx%d", oh, ow, h, w);
+    LRPX_REQUIRE((long)h * w < (1L << 31) && planes * (long)h * w < (1L << 40), "maxpool_rule: tensor too large");
+    LRPX_CHECK_PTRS("lrpx_maxpool_rule", {x, "x"}, {r_out, "r_out"}, {r_in, "r_in"});
+    const MaxPoolGeom g = {h, w, oh, ow, kh, kw, sh, sw, ph, pw};
+    hipLaunchKernelGGL(maxpool_rule_kernel, dim3((unsigned)ceil_div(planes * h * w, 256)), dim3(256), 0, (hipStream_t)stream, x, r_out, r_in,
+                       planes, g);
+    return check_launch("maxpool_rule");
 }
 
 int lrpx_max_abs_diff(const float* a, const float* b, long n, float* out_dev, void* stream) {

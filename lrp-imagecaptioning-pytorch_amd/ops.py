@@ -191,6 +191,39 @@ def conv_mfma(inp, wpacked, n_maps, hw, cin, n_oc, taps, epi, **kw):
     check(_lib.load().lrpx_conv_mfma(C.byref(d), stream_ptr()))
 
 
+def conv_geom_pack(w, direction):
+    """w (cout, cin, kh, kw) on the device -> the packed fragments of `lrpx_conv_geom` for that direction (_lib.GEOM_FWD: K = cin,
+    columns = cout; _lib.GEOM_BWD: K = cout, columns = cin).  Stacks of W+ / W- are built by the caller before packing."""
+    lib = _lib.load()
+    cout, cin, kh, kw = _dev(w).shape
+    n_oc, k = (cout, cin) if direction == _lib.GEOM_FWD else (cin, cout)
+    out = torch.empty(lib.lrpx_conv_geom_packed_floats(n_oc, k, kh * kw), dtype=torch.float32, device=w.device)
+    check(lib.lrpx_conv_geom_pack(ptr(w.to(torch.float32).contiguous()), cout, cin, kh, kw, direction, ptr(out), stream_ptr()))
+    return out
+
+
+def conv_geom(inp, wpacked, direction, n, hw, ohw, geom, k, n_oc, bias=None, x=None, out=None):
+    """The runtime-geometry conv engine (csrc/conv_geom.hip), NHWC fp32.  hw = (H, W) the conv's input map, ohw = (OH, OW) its
+    output map, geom = (kh, kw, sh, sw, ph, pw).  GEOM_FWD: inp (n, H W, k) -> out (n, OH OW, n_oc) (+ bias);
+    GEOM_BWD: inp (n, OH OW, k) -> out (n, H W, n_oc) = x * convT(inp)."""
+    pix = hw[0] * hw[1] if direction == _lib.GEOM_BWD else ohw[0] * ohw[1]
+    if out is None:
+        out = torch.empty(n, pix, n_oc, dtype=torch.float32, device=inp.device)
+    d = _lib.ConvGeomDesc(ptr(_dev(inp)), ptr(_dev(wpacked)), ptr(_dev(bias)), ptr(_dev(x)), ptr(_dev(out)), direction,
+                          n, hw[0], hw[1], ohw[0], ohw[1], *geom, k, n_oc)
+    check(_lib.load().lrpx_conv_geom(C.byref(d), stream_ptr()))
+    return out
+
+
+def maxpool_rule(x, r_out, kernel, stride, padding):
+    """Pool2d rule of an nn.MaxPool2d with any window (lrpx_maxpool_rule): x (N, C, H, W), r_out (N, C, OH, OW) contiguous fp32"""
+    n, c, h, w = _dev(x).shape
+    r_in = torch.empty_like(x)
+    check(_lib.load().lrpx_maxpool_rule(ptr(x), ptr(_dev(r_out)), ptr(r_in), n * c, h, w, r_out.shape[2], r_out.shape[3],
+                                        kernel[0], kernel[1], stride[0], stride[1], padding[0], padding[1], stream_ptr()))
+    return r_in
+
+
 def nchw_to_nhwc(src, c_pad=None):
     n, c, h, w = src.shape
     c_pad = c_pad or c

@@ -1,0 +1,121 @@
+#!/usr/bin/env python3
+"""What one `compute_lrp` through a ResNet-50-shaped bottleneck encoder costs on the generic leaf driver: the net of
+tests/golden/make_golden_resnet.py (`bottleneck_net(base=64, blocks=[3, 4, 6, 3])`, seeded weights) on a (4, 3, 224, 224) batch.
+
+    python tools/resnet_lrp_timing.py [--out profiles/resnet_lrp_timing.txt] [--batch 4] [--iters 3]
+
+Reports the whole call, the milliseconds per leaf type (HIP events around each rule call, layout conversions and the rule's checks
+included) and every distinct launch of the runtime-geometry conv engine (csrc/conv_geom.hip) with its flop as issued -
+2 n OH OW kh kw K n_oc with the K and n_oc the launch was given, i.e. with the doubled channels of the split [x+ | x-] storage - as
+achieved TFLOP/s against the 157 TFLOP/s fp32-MFMA peak.  Times are HIP events on one stream after a warm-up call, averaged over
+--iters calls; an interval around one launch on an otherwise idle stream includes that launch's latency.  Nothing is asserted."""
+import argparse
+import collections
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PEAK_TFLOPS = 157.0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=4)
+    ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--out", default=None, help="also write the report to this file")
+    a = ap.parse_args()
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import lrp_amd  # noqa: F401
+    from lrp_amd import _lib, ops
+    from lrp_amd.LRPtools import lrp_modules, lrp_wrapper
+    from make_golden_resnet import bottleneck_net
+    if not torch.cuda.is_available():
+        raise SystemExit("resnet_lrp_timing: no GPU - a time is measured on the device or not at all")
+    net = bottleneck_net(np.random.RandomState(0), lrp_modules.resAdd, 64, [3, 4, 6, 3]).cuda()
+    lrp_wrapper.add_lrp(net)
+    g = torch.Generator().manual_seed(0)
+    x = torch.randn(a.batch, 3, 224, 224, generator=g).cuda()
+    with torch.no_grad():
+        target = torch.randn(net(x).shape, generator=g).cuda()
+
+    events = []                                   # (kind, key, start, end)
+
+    def ev():
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        return e
+    real_get, real_geom = lrp_modules.get_lrp_module, ops.conv_geom
+
+    def get_timed(module):
+        rule = real_get(module)
+        real = rule.propagate_relevance
+
+        def timed(*args, **kw):
+            e0 = ev()
+            out = real(*args, **kw)
+            events.append(("leaf", type(module).__name__, e0, ev()))
+            return out
+        rule.propagate_relevance = timed
+        return rule
+
+    def geom_timed(inp, wpacked, direction, n, hw, ohw, geom, k, n_oc, **kw):
+        e0 = ev()
+        out = real_geom(inp, wpacked, direction, n, hw, ohw, geom, k, n_oc, **kw)
+        events.append(("launch", (direction, geom, hw, k, n_oc, n, ohw), e0, ev()))
+        return out
+
+    def call():
+        e0 = ev()
+        net.compute_lrp(x.clone(), target=target)
+        events.append(("call", "compute_lrp", e0, ev()))
+    call()                                        # warm-up: packs the weights, loads every kernel
+    torch.cuda.synchronize()
+    lrp_modules.get_lrp_module, ops.conv_geom = get_timed, geom_timed
+    try:
+        for _ in range(a.iters):
+            call()
+        torch.cuda.synchronize()
+    finally:
+        lrp_modules.get_lrp_module, ops.conv_geom = real_get, real_geom
+    ms = collections.defaultdict(float)
+    cnt = collections.Counter()
+    for kind, key, e0, e1 in events[1:]:
+        ms[(kind, key)] += e0.elapsed_time(e1) / a.iters
+        cnt[(kind, key)] += 1
+    lines = [f"# tools/resnet_lrp_timing.py --batch {a.batch} --iters {a.iters}",
+             f"== bottleneck_net(base=64, blocks=[3,4,6,3]) on ({a.batch}, 3, 224, 224), {torch.cuda.get_device_name(0)}",
+             f"compute_lrp, whole call : {ms[('call', 'compute_lrp')]:9.2f} ms", "",
+             "per leaf type (rule calls per compute_lrp, ms per compute_lrp)"]
+    for (kind, key), v in sorted(ms.items(), key=lambda kv: -kv[1]):
+        if kind == "leaf":
+            lines.append(f"  {key:<14} {cnt[(kind, key)] // a.iters:4d} calls {v:9.2f} ms")
+    lines += ["", "conv engine launches (per distinct shape: launches per compute_lrp, ms per launch, flop as issued, achieved TFLOP/s, % of "
+              f"{PEAK_TFLOPS:.0f})",
+              f"  {'dir':<3} {'kernel':<6} {'stride':<6} {'map':<9} {'K':>5} {'n_oc':>5} {'launches':>8} {'ms':>8} {'GFLOP':>8} {'TFLOP/s':>8} {'%peak':>6}"]
+    tot_ms = tot_fl = 0.0
+    for (kind, key), v in sorted(ms.items(), key=lambda kv: -kv[1]):
+        if kind != "launch":
+            continue
+        direction, geom, hw, k, n_oc, n, ohw = key
+        c = cnt[(kind, key)] // a.iters
+        per = v / c
+        flop = 2.0 * n * ohw[0] * ohw[1] * geom[0] * geom[1] * k * n_oc
+        tf = flop / (per * 1e-3) / 1e12
+        tot_ms += v
+        tot_fl += flop * c
+        lines.append(f"  {'fwd' if direction == _lib.GEOM_FWD else 'bwd':<3} {geom[0]}x{geom[1]:<4} {geom[2]}x{geom[3]:<4} {hw[0]}x{hw[1]:<5} "
+                     f"{k:5d} {n_oc:5d} {c:8d} {per:8.3f} {flop / 1e9:8.2f} {tf:8.2f} {100 * tf / PEAK_TFLOPS:6.1f}")
+    if tot_ms:
+        lines.append(f"  all conv engine launches: {tot_ms:.2f} ms, {tot_fl / 1e9:.1f} GFLOP, {tot_fl / (tot_ms * 1e-3) / 1e12:.2f} TFLOP/s")
+    report = "\n".join(lines) + "\n"
+    sys.stdout.write(report)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(report)
+
+
+if __name__ == "__main__":
+    main()
