@@ -35,6 +35,7 @@ enum {
 /* The runtime-geometry conv engine and the general MaxPool2d rule (lrpx_conv_geom, lrpx_conv_geom_pack,
  * lrpx_conv_geom_packed_floats, lrpx_maxpool_rule) came WITHOUT a new version number: a caller detects them by the presence
  * of the symbols (dlsym / hasattr on the loaded library).
+ * The same holds for the batched ResNet engine's entries (lrpx_conv_geom_ex, lrpx_resnet_*).
  * 101: the alpha-beta Conv2d rule (LRPX_PACK_*_PN*, lrpx_divide_alpha_beta, lrpx_maxpool2x2_relevance_ab); 100 before it */
 int lrpx_version(void);
 const char* lrpx_last_error_string(void);
@@ -171,6 +172,31 @@ size_t lrpx_conv_geom_packed_floats(int n_oc, int k, int taps);
 /* w: (cout, cin, kh, kw) as nn.Conv2d stores it (the caller stacks W+ / W- along either channel axis first).
  * FWD: k = cin, n_oc = cout;  BWD: k = cout, n_oc = cin. */
 int lrpx_conv_geom_pack(const float* w, int cout, int cin, int kh, int kw, int dir, float* packed, void* stream);
+
+/* ---- the same engine with the operands of a BATCHED relevance pass (csrc/conv_geom_ex.hip; ops.ResNetEncoder) ----
+ * Same tiling, packed weights (lrpx_conv_geom_pack) and arithmetic as lrpx_conv_geom.  FWD is the plain convolution: the trace stacks
+ * [W | W+] along the output columns (the caller, before packing) and gets the conv's output and Z+ of its rule from ONE gather of
+ * the input tile.  BWD answers for the transposed conv inside lrp_backward (LRPtools/utils.py:21-31) with the division
+ * S = R / safe(Z) (utils.py:28) and the BatchNorm rule above the conv (lrp_modules.py:210-215) folded into a per-image multiplier:
+ *   out[m,h,w,ci] = x[img,h,w,ci] * sum (in[m,oh,ow,co] * q[img,oh,ow,co]) * w[co,ci,r,s]  (+ addend[m,h,w,ci]),  img = map2img[m]. */
+typedef struct lrpx_conv_geom_ex_desc {
+    const float* in;       /* FWD: [n*h*w][k];  BWD: [n*oh*ow][k], the relevance at the conv's output, per MAP.  16-byte aligned, k %% 4 == 0 */
+    const float* wpacked;  /* lrpx_conv_geom_pack of the same direction */
+    const float* bias;     /* FWD only, [n_oc], may be NULL */
+    const float* x;        /* BWD only, [n_img*h*w][n_oc]: the multiplicand of the epilogue, per IMAGE */
+    const float* q;        /* BWD only, may be NULL, [n_img*oh*ow][k], 16-byte aligned: multiplies `in` while the tile is gathered */
+    const float* addend;   /* BWD only, may be NULL, [n*h*w][n_oc]: added after the multiplication by x (also where no tap reaches) */
+    const int32_t* map2img;/* BWD only, [n] image of each map, every entry in [0, n_img) - the CALLER validates it, the kernel trusts
+                              it;  NULL: map m reads image m (then n_img == n) */
+    float* out;            /* FWD: [n*oh*ow][n_oc];  BWD: [n*h*w][n_oc] */
+    int dir;               /* LRPX_GEOM_FWD / LRPX_GEOM_BWD */
+    int n, n_img;          /* n: images (FWD) / maps (BWD);  n_img: images behind x and q (BWD; ignored by FWD) */
+    int h, w, oh, ow;      /* as lrpx_conv_geom_desc: the conv's INPUT map and its output map, in both directions */
+    int kh, kw, sh, sw, ph, pw;   /* dilation 1, groups 1, zero padding */
+    int k, n_oc;           /* contraction channels (row length of `in` / q) and output channels (row length of out / x / addend) */
+} lrpx_conv_geom_ex_desc;
+/* fp32 MFMA, fp32 accumulation (the grade of conv mode 0); no atomics: a map's result does not depend on the other maps. */
+int lrpx_conv_geom_ex(const lrpx_conv_geom_ex_desc* d, void* stream);
 
 /* ---- elementwise / layout kernels -------------------------------------------------------------- */
 /* NHWC <-> BLOCKED (csrc/blocked.h): n_groups tensors of pix_per_group pixels x c channels (c %% 16 == 0), each its own block set
@@ -666,6 +692,36 @@ int lrpx_avgpool_rule(const float* x, const float* r_out, float* s_ws, float* r_
  * windows that contain it: no atomics, no workspace. */
 int lrpx_maxpool_rule(const float* x, const float* r_out, float* r_in, long planes, int h, int w, int oh, int ow, int kh, int kw,
                       int sh, int sw, int ph, int pw, void* stream);
+/* ---- elementwise kernels of the batched bottleneck-ResNet engine (csrc/resnet_engine.hip; NHWC fp32, one pass each) -----------
+ * Trace, once per image.  yz: `rows` pixel rows of `ld` >= 2c floats, columns [0,c) the conv's output y, [c,2c) Z of its rule
+ * (conv(x,W+); the stem: conv(x+,W+) + conv(x-,W-), lrp_modules.py:81-84).  w / b [c]: the folded eval-mode BatchNorm scale and
+ * shift (lrp_modules.py:210-211).  act [rows][c] = y w + b (relu != 0: max(., 0), models/resnet.py:122-131);  q [rows][c] =
+ * safe_divide(|y w|, |y w| + |b|) / (Z + 1e-7 [Z == 0]): BatchNorm2d.propagate_relevance (:212-215) times the divisor of
+ * utils.safe_divide inside lrp_backward (utils.py:16-18,28) - everything between R at the BN's output and S of the conv. */
+int lrpx_resnet_bn_act_coef(const float* yz, int ld, const float* w, const float* b, float* act, float* q, long rows, int c, int relu,
+                            void* stream);
+/* out = max(x1 + x2, 0) (models/resnet.py:137-138) and the coefficients of Add.propagate_relevance (lrp_modules.py:262-275):
+ * c_k = x_k / (x1 + x2 + 0.01 sign(x1 + x2)), NaN -> 0, + 0.5 where x1 + x2 == 0, so that R_k = R c_k.  (x1 == -x2 != 0, where the
+ * reference's result is non-finite and its asserts fire, gives 0.5.)  n elements each. */
+int lrpx_resnet_add_relu_coef(const float* x1, const float* x2, float* out, float* c1, float* c2, long n, void* stream);
+/* nn.MaxPool2d forward on NHWC (models/resnet.py:168,225): x [n][h*w][c] -> y [n][oh*ow][c]; padding is -inf, a NaN wins. */
+int lrpx_resnet_maxpool_fwd(const float* x, float* y, int n, int h, int w, int oh, int ow, int c, int kh, int kw, int sh, int sw, int ph,
+                            int pw, void* stream);
+/* Relevance, per map; per-image operands are read from image map2img[m] (int32 [n_maps], entries in [0, n_img) validated by the
+ * caller; NULL: n_maps == n_img, map m on image m).
+ * Pool2d.propagate_relevance for nn.MaxPool2d (lrp_modules.py:182-195) in NHWC: x [n_img][h*w][c], r_out [n_maps][oh*ow][c] ->
+ * r_in [n_maps][h*w][c].  A gather per input element with the winner logic of lrpx_maxpool_rule (first maximum, kernel rows outer;
+ * windows added in ascending (oh, ow) order); the winners are recomputed from x, no atomics, no workspace. */
+int lrpx_resnet_maxpool_rel(const float* x, const float* r_out, const int32_t* map2img, float* r_in, int n_maps, int n_img, int h, int w,
+                            int oh, int ow, int c, int kh, int kw, int sh, int sw, int ph, int pw, void* stream);
+/* Add.propagate_relevance (lrp_modules.py:262-275) behind the block's final ReLU (identity rule, :42-46): r1 = r c1[img],
+ * r2 = r c2[img] with the coefficients of lrpx_resnet_add_relu_coef; r / r1 / r2 [n_maps][per_map], c1 / c2 [n_img][per_map]. */
+int lrpx_resnet_add_split(const float* r, const float* c1, const float* c2, const int32_t* map2img, float* r1, float* r2, int n_maps,
+                          int n_img, long per_map, void* stream);
+/* the stem's signed-input rule R = x+ convT(S,W+) + x- convT(S,W-) (lrp_modules.py:81-84,136-138): r_split [n_maps][pix][ld]
+ * holds the two terms in columns [0,cin) and [half, half+cin), half + cin <= ld (the layout of lrpx_nchw_to_nhwc_posneg: half = cin);
+ * out [n_maps][cin][pix] (NCHW) = their sum. */
+int lrpx_resnet_stem_fold(const float* r_split, float* out, int n_maps, int cin, int half, int ld, long pix, void* stream);
 /* max |a - b| into one device float (Dropout.propagate_relevance's check, LRPtools/lrp_modules.py:251; NaN counts as inf) */
 int lrpx_max_abs_diff(const float* a, const float* b, long n, float* out_dev, void* stream);
 

@@ -18,6 +18,8 @@ relevance pass (lrp_wrapper.py:37-87).  Here `add_lrp` validates the same leaf -
 `add_lrp(model, lrp_params=...)` lays a dict over the preset's parameters (the reference's add_lrp has the comment "Override default
 parameters if provided" and no argument): the VGG16 encoder with another alpha / beta and `ignore_bias=True` runs the batched
 `ops.Vgg16.relevance_alpha_beta`, with `ignore_bias=False` the generic driver.
+For a bottleneck ResNet under the preset `add_lrp` additionally attaches `model.compute_lrp_maps(images, targets, map2img=None)`: the batched
+engine `ops.ResNetEncoder` (one trace per image, one map per target row, no hooks, no `.grad`).  `compute_lrp` is unchanged.
 Improvement over the reference: `add_lrp` is idempotent (the reference stacks hooks on every call, which
 multiplies its cost without changing the result)."""
 import torch
@@ -94,7 +96,9 @@ def add_lrp(model, lrp_params=None):
             lrp_modules.conv_rule_params(m, params)       # ValueError: ignore_bias=False on a conv without bias
     model._lrpx_params = params
     if not _match_vgg16(leaves) or not params["ignore_bias"]:
-        return _add_lrp_generic(model, leaves)
+        _add_lrp_generic(model, leaves)
+        _attach_resnet_engine(model, params)
+        return
     old = model.__dict__.pop("_lrpx_hooks", None)         # (a generic driver installed by an earlier add_lrp(..., ignore_bias=False))
     for h in old or ():
         h.remove()
@@ -107,6 +111,41 @@ def add_lrp(model, lrp_params=None):
                     [c.bias.detach().float() if c.bias is not None else zeros(c.out_channels) for c in convs])
     model._lrpx_ctx = ctx
     model.compute_lrp = lambda sample, **kwargs: compute_lrp(model, sample, **kwargs)
+
+
+def _attach_resnet_engine(model, params):
+    """`model.compute_lrp_maps` for a bottleneck ResNet under the preset (ops.match_bottleneck_resnet); any other model or `lrp_params`:
+    the attribute is absent.  Installs no hooks; the engine (packed weights) is built at the first call."""
+    model.__dict__.pop("compute_lrp_maps", None)
+    model.__dict__.pop("_lrpx_resnet", None)
+    if params != SequentialPresetA().lrp_params:
+        return
+    try:
+        ops.match_bottleneck_resnet(model)
+    except ValueError:
+        return
+    model.compute_lrp_maps = lambda images, targets, map2img=None: compute_lrp_maps(model, images, targets, map2img)
+
+
+def compute_lrp_maps(model, images, targets, map2img=None):
+    """The batched form of `compute_lrp` for the bottleneck ResNet encoders: `images` (B, 3, H, W) are traced ONCE and every row of
+    `targets` (n_maps, C, h, w) NCHW - the relevance at the encoder's output - becomes one map (n_maps, 3, H, W) on the trace of image
+    map2img[m] (int32 tensor on the device; None: n_maps == B, map m on image m).  Runs `ops.ResNetEncoder` (built on first use from
+    the model's weights as they are then; `add_lrp(model)` again after changing them), not the hooks of the generic driver.  Each map
+    equals what `compute_lrp` returns for (that image, that target) on a FRESH sample tensor: this function does not touch `.grad` -
+    it neither reads nor accumulates into `images.grad` - and returns the maps themselves, not a running sum.  Like `compute_lrp` it
+    asserts the result is finite and not all zero (lrp_wrapper.py:81)."""
+    eng = model.__dict__.get("_lrpx_resnet")
+    if eng is None:
+        eng = model._lrpx_resnet = ops.ResNetEncoder(model)
+    feats = eng.forward(images.detach())
+    hw = eng.feat_hw
+    if targets.dim() != 4 or tuple(targets.shape[1:]) != (feats.shape[2], hw[0], hw[1]):
+        raise ValueError("compute_lrp_maps: targets must be (n_maps, {}, {}, {}), got {}".format(feats.shape[2], hw[0], hw[1],
+                                                                                                 tuple(targets.shape)))
+    r = eng.relevance(ops.nchw_to_nhwc(targets.detach().to(torch.float32)), map2img)
+    ops.check_relevance(r, finite=True, nonzero=True)
+    return r
 
 
 def compute_lrp(model, sample, target=None, return_output=False, rectify_logits=False, explain_diff=False):

@@ -83,6 +83,13 @@ class ConvGeomDesc(C.Structure):
                 ("kh", _i), ("kw", _i), ("sh", _i), ("sw", _i), ("ph", _i), ("pw", _i), ("k", _i), ("n_oc", _i)]
 
 
+class ConvGeomExDesc(C.Structure):
+    """lrpx_conv_geom_ex_desc: the runtime-geometry conv engine with map2img, input multiplier and addend (csrc/conv_geom_ex.hip)"""
+    _fields_ = [("in_", _f), ("wpacked", _f), ("bias", _f), ("x", _f), ("q", _f), ("addend", _f), ("map2img", _f), ("out", _f),
+                ("dir", _i), ("n", _i), ("n_img", _i), ("h", _i), ("w", _i), ("oh", _i), ("ow", _i),
+                ("kh", _i), ("kw", _i), ("sh", _i), ("sw", _i), ("ph", _i), ("pw", _i), ("k", _i), ("n_oc", _i)]
+
+
 class VggOpts(C.Structure):
     """lrpx_vgg16_opts: the per-call context of the VGG16 chains (conv mode, forward switch, per-layer timing)"""
     _fields_ = [("conv_mode", _i), ("forward_f16", _i), ("layer_ms", C.POINTER(C.c_float))]
@@ -217,6 +224,13 @@ SIGNATURES = {
     "lrpx_conv_geom_packed_floats": (_sz, [_i, _i, _i]),
     "lrpx_conv_geom_pack": (_i, [_f, _i, _i, _i, _i, _i, _f, _f]),
     "lrpx_max_abs_diff": (_i, [_f, _f, _l, _f, _f]),
+    "lrpx_conv_geom_ex": (_i, [C.POINTER(ConvGeomExDesc), _f]),
+    "lrpx_resnet_bn_act_coef": (_i, [_f, _i, _f, _f, _f, _f, _l, _i, _i, _f]),
+    "lrpx_resnet_add_relu_coef": (_i, [_f, _f, _f, _f, _f, _l, _f]),
+    "lrpx_resnet_maxpool_fwd": (_i, [_f, _f] + [_i] * 12 + [_f]),
+    "lrpx_resnet_maxpool_rel": (_i, [_f, _f, _f, _f] + [_i] * 13 + [_f]),
+    "lrpx_resnet_add_split": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _l, _f]),
+    "lrpx_resnet_stem_fold": (_i, [_f, _f, _i, _i, _i, _i, _l, _f]),
 }
 
 _lib = None

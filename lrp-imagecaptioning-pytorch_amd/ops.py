@@ -671,3 +671,432 @@ class Vgg16:
         for i in range(streams):
             cur.wait_stream(self._side[i])
         return out
+
+
+# ---- the batched bottleneck-ResNet encoder engine ------------------------------------------------------------------
+LAUNCHES = {}        # (wrapper name, direction) -> calls since the process started: the tests' evidence of what a pass launches
+
+
+def _count(name, direction=None):
+    LAUNCHES[(name, direction)] = LAUNCHES.get((name, direction), 0) + 1
+
+
+def check_map2img(map2img, n_maps, n_img):
+    """map2img (n_maps,) int32 on the device with every entry in [0, n_img) - checked on the HOST (one small copy), before any kernel
+    sees it: the kernels index the per-image operands with it unchecked.  LrpxError otherwise."""
+    if not (isinstance(map2img, torch.Tensor) and map2img.dtype == torch.int32 and map2img.dim() == 1 and map2img.shape[0] == n_maps):
+        raise _lib.LrpxError("map2img must be an int32 tensor of n_maps = {} entries (LRPX_EINVAL)".format(n_maps))
+    _dev(map2img)
+    if n_maps:
+        host = map2img.cpu()
+        lo, hi = int(host.min()), int(host.max())
+        if lo < 0 or hi >= n_img:
+            raise _lib.LrpxError("map2img entry {} outside [0, {}) (LRPX_EINVAL)".format(lo if lo < 0 else hi, n_img))
+    return map2img.contiguous()
+
+
+def conv_geom_ex(inp, wpacked, direction, n, hw, ohw, geom, k, n_oc, bias=None, x=None, q=None, addend=None, map2img=None, n_img=None,
+                 out=None, validate=True):
+    """`lrpx_conv_geom_ex` (csrc/conv_geom_ex.hip), NHWC fp32; hw / ohw / geom as `conv_geom`.  GEOM_FWD: inp (n, H W, k) -> out
+    (n, OH OW, n_oc) (+ bias).  GEOM_BWD: inp (n maps, OH OW, k) -> out (n, H W, n_oc) = x[img] * convT(inp * q[img]) + addend with
+    img = map2img[m] (None: identity); x (n_img, H W, n_oc), q (n_img, OH OW, k), addend like out.  validate: check map2img on the host
+    first (`check_map2img`; a caller that already has passes False)."""
+    if direction == _lib.GEOM_BWD:
+        n_img = n if n_img is None else n_img
+        if x is None or tuple(x.shape) != (n_img, hw[0] * hw[1], n_oc):
+            raise ValueError("conv_geom_ex: x must be (n_img, H W, n_oc)")
+        if q is not None and tuple(q.shape) != (n_img, ohw[0] * ohw[1], k):
+            raise ValueError("conv_geom_ex: q must be (n_img, OH OW, k)")
+        if addend is not None and tuple(addend.shape) != (n, hw[0] * hw[1], n_oc):
+            raise ValueError("conv_geom_ex: addend must have the output's shape")
+        if map2img is not None and validate:
+            map2img = check_map2img(map2img, n, n_img)
+    pix_in, pix_out = (ohw[0] * ohw[1], hw[0] * hw[1]) if direction == _lib.GEOM_BWD else (hw[0] * hw[1], ohw[0] * ohw[1])
+    if inp.numel() != n * pix_in * k:
+        raise ValueError("conv_geom_ex: the input must hold n x pixels x k = {} x {} x {} floats".format(n, pix_in, k))
+    if out is None:
+        out = torch.empty(n, pix_out, n_oc, dtype=torch.float32, device=inp.device)
+    elif out.numel() != n * pix_out * n_oc:
+        raise ValueError("conv_geom_ex: the output must hold n x pixels x n_oc floats")
+    d = _lib.ConvGeomExDesc(ptr(_dev(inp)), ptr(_dev(wpacked)), ptr(_dev(bias)), ptr(_dev(x)), ptr(_dev(q)), ptr(_dev(addend)),
+                            ptr(_dev(map2img)), ptr(_dev(out)), direction, n, n_img or 0, hw[0], hw[1], ohw[0], ohw[1], *geom, k, n_oc)
+    _count("conv_geom_ex", direction)
+    check(_lib.load().lrpx_conv_geom_ex(C.byref(d), stream_ptr()))
+    return out
+
+
+def resnet_bn_act_coef(yz, w, b, act, q, relu):
+    """yz (n, pix, 2c) = [conv output | Z of its rule] -> act = BN affine (+ ReLU), q = the conv's relevance coefficient (include/lrpx.h)"""
+    c = w.shape[0]
+    _count("resnet_bn_act_coef")
+    check(_lib.load().lrpx_resnet_bn_act_coef(ptr(_dev(yz)), yz.shape[-1], ptr(_dev(w)), ptr(_dev(b)), ptr(_dev(act)), ptr(_dev(q)),
+                                              yz.numel() // yz.shape[-1], c, 1 if relu else 0, stream_ptr()))
+
+
+def resnet_add_relu_coef(x1, x2, out, c1, c2):
+    _count("resnet_add_relu_coef")
+    check(_lib.load().lrpx_resnet_add_relu_coef(ptr(_dev(x1)), ptr(_dev(x2)), ptr(_dev(out)), ptr(_dev(c1)), ptr(_dev(c2)), x1.numel(),
+                                                stream_ptr()))
+
+
+def resnet_maxpool_fwd(x, y, n, hw, ohw, c, win):
+    _count("resnet_maxpool_fwd")
+    check(_lib.load().lrpx_resnet_maxpool_fwd(ptr(_dev(x)), ptr(_dev(y)), n, hw[0], hw[1], ohw[0], ohw[1], c, *win, stream_ptr()))
+
+
+def resnet_maxpool_rel(x, r_out, map2img, r_in, n_maps, n_img, hw, ohw, c, win):
+    _count("resnet_maxpool_rel")
+    check(_lib.load().lrpx_resnet_maxpool_rel(ptr(_dev(x)), ptr(_dev(r_out)), ptr(map2img), ptr(_dev(r_in)), n_maps, n_img, hw[0], hw[1],
+                                              ohw[0], ohw[1], c, *win, stream_ptr()))
+
+
+def resnet_add_split(r, c1, c2, map2img, r1, r2, n_maps, n_img):
+    _count("resnet_add_split")
+    check(_lib.load().lrpx_resnet_add_split(ptr(_dev(r)), ptr(_dev(c1)), ptr(_dev(c2)), ptr(map2img), ptr(_dev(r1)), ptr(_dev(r2)), n_maps,
+                                            n_img, r.numel() // n_maps, stream_ptr()))
+
+
+def resnet_stem_fold(r_split, out, n_maps, cin, half, ld, pix):
+    _count("resnet_stem_fold")
+    check(_lib.load().lrpx_resnet_stem_fold(ptr(_dev(r_split)), ptr(_dev(out)), n_maps, cin, half, ld, pix, stream_ptr()))
+
+
+def _pair(v):
+    return tuple(int(a) for a in v) if isinstance(v, (tuple, list)) else (int(v), int(v))
+
+
+def _conv_out(size, k, s, p):
+    return (size + 2 * p - k) // s + 1
+
+
+class ResNetPlan(object):
+    """What `match_bottleneck_resnet` found.  `convs`: one dict per conv in forward order - name, module, bn, cin, cout, geom = (kh, kw,
+    sh, sw, ph, pw), producer ('image' | 'maxpool(relu)' | 'relu') and nonneg = the producer is a ReLU or the pool of a ReLU (all but the
+    stem: what licenses K = cin and W+ alone).  `blocks`: one dict per bottleneck block - name, conv1 / conv2 / conv3 / downsample (indices
+    into `convs`, downsample None for an identity shortcut).  `pool` = (kh, kw, sh, sw, ph, pw) of the stem's MaxPool2d."""
+
+    def __init__(self, convs, blocks, pool):
+        self.convs, self.blocks, self.pool = convs, blocks, pool
+
+
+def match_bottleneck_resnet(model):
+    """Recognise a bottleneck ResNet by STRUCTURE (not by class): direct children Conv2d -> BatchNorm2d -> ReLU -> MaxPool2d (the stem,
+    models/resnet.py:164-168), then nn.Sequential containers (`layer1..layer4` or one `layers`) of blocks with conv1 / bn1 / conv2 / bn2 /
+    conv3 / bn3 / relu / add members and an optional downsample = Sequential(Conv2d, BatchNorm2d) (:93-140); an AdaptiveAvgPool2d / Linear
+    head the forward never calls may follow (:176-177).  Returns a `ResNetPlan`; ValueError naming the reason otherwise.  The
+    non-negativity of every conv input but the stem's follows from this structure - its producer is the ReLU member or the pool behind
+    the stem's ReLU - never from data.  Host logic: no device."""
+    import torch.nn as nn
+
+    def fail(msg):
+        raise ValueError("not a bottleneck ResNet the engine runs: " + msg)
+    kids = list(model.named_children())
+    stem_types = (nn.Conv2d, nn.BatchNorm2d, nn.ReLU, nn.MaxPool2d)
+    if len(kids) < 5 or not all(isinstance(kids[i][1], t) for i, t in enumerate(stem_types)):
+        fail("the stem must be Conv2d -> BatchNorm2d -> ReLU -> MaxPool2d followed by containers of blocks, got " +
+             ", ".join(type(m).__name__ for _, m in kids[:5]))
+
+    def conv_entry(name, conv, bn, producer):
+        if not isinstance(conv, nn.Conv2d) or not isinstance(bn, nn.BatchNorm2d):
+            fail("{}: a Conv2d followed by a BatchNorm2d, got {} / {}".format(name, type(conv).__name__, type(bn).__name__))
+        if _pair(conv.dilation) != (1, 1):
+            fail("{}: dilation {} is not supported".format(name, conv.dilation))
+        if conv.groups != 1:
+            fail("{}: groups={} is not supported".format(name, conv.groups))
+        if conv.bias is not None:
+            fail("{}: a conv with bias is not supported (the preset ignores it, the trace would not)".format(name))
+        if isinstance(conv.padding, str) or conv.padding_mode != "zeros":
+            fail("{}: padding {!r} / padding_mode {!r} is not supported".format(name, conv.padding, conv.padding_mode))
+        if bn.training:
+            fail("{}: its BatchNorm2d is in training mode (call .eval(): the rule uses the running statistics)".format(name))
+        if bn.running_mean is None or bn.running_var is None or not bn.affine:
+            fail("{}: its BatchNorm2d has no running statistics / affine parameters".format(name))
+        if bn.num_features != conv.out_channels:
+            fail("{}: BatchNorm2d({}) after {} output channels".format(name, bn.num_features, conv.out_channels))
+        if conv.out_channels % 4:
+            fail("{}: {} output channels - the engine reads channels in fours".format(name, conv.out_channels))
+        geom = _pair(conv.kernel_size) + _pair(conv.stride) + _pair(conv.padding)
+        return dict(name=name, module=conv, bn=bn, cin=conv.in_channels, cout=conv.out_channels, geom=geom, producer=producer,
+                    nonneg=producer in ("relu", "maxpool(relu)"))
+
+    pool = kids[3][1]
+    if _pair(pool.dilation) != (1, 1) or pool.ceil_mode:
+        fail("{}: MaxPool2d with dilation / ceil_mode is not supported".format(kids[3][0]))
+    pk, ps, pp = _pair(pool.kernel_size), _pair(pool.stride if pool.stride is not None else pool.kernel_size), _pair(pool.padding)
+    convs = [conv_entry(kids[0][0], kids[0][1], kids[1][1], "image")]
+    blocks = []
+    cin = convs[0]["cout"]
+    producer = "maxpool(relu)"
+    head = False
+    for cname, cont in kids[4:]:
+        if isinstance(cont, (nn.AdaptiveAvgPool2d, nn.Linear)):
+            head = True
+            continue
+        if head or not isinstance(cont, nn.Sequential) or len(cont) == 0:
+            fail("{}: expected a Sequential of bottleneck blocks (or the unused AdaptiveAvgPool2d / Linear head), got {}".format(
+                cname, type(cont).__name__))
+        for bname, blk in cont.named_children():
+            name = "{}.{}".format(cname, bname)
+            get = lambda a: getattr(blk, a, None)
+            if not all(isinstance(get(a), nn.Module) for a in ("conv1", "bn1", "conv2", "bn2")):
+                fail("{}: not a residual block (no conv1 / bn1 / conv2 / bn2 members)".format(name))
+            if get("conv3") is None or get("bn3") is None:
+                fail("{}: a BasicBlock (two convs, no conv3 / bn3) - only bottleneck blocks are supported; BasicBlock nets also build "
+                     "their Add inside forward (models/resnet.py:87)".format(name))
+            if not isinstance(get("relu"), nn.ReLU):
+                fail("{}: no `relu` member of type nn.ReLU".format(name))
+            if not isinstance(get("add"), nn.Module):
+                fail("{}: no registered `add` module (models/resnet.py:118)".format(name))
+            i0 = len(convs)
+            convs.append(conv_entry(name + ".conv1", blk.conv1, blk.bn1, producer))
+            convs.append(conv_entry(name + ".conv2", blk.conv2, blk.bn2, "relu"))
+            convs.append(conv_entry(name + ".conv3", blk.conv3, blk.bn3, "relu"))
+            down = None
+            ds = get("downsample")
+            if ds is not None:
+                if not (isinstance(ds, nn.Sequential) and len(ds) == 2):
+                    fail("{}.downsample: expected Sequential(Conv2d, BatchNorm2d)".format(name))
+                down = len(convs)
+                convs.append(conv_entry(name + ".downsample.0", ds[0], ds[1], producer))
+            chain = [(convs[i0], cin), (convs[i0 + 1], convs[i0]["cout"]), (convs[i0 + 2], convs[i0 + 1]["cout"])]
+            if down is not None:
+                chain.append((convs[down], cin))
+            for cv, want in chain:
+                if cv["cin"] != want:
+                    fail("{}: {} input channels where its producer has {}".format(cv["name"], cv["cin"], want))
+            cout = convs[i0 + 2]["cout"]
+            if down is not None and convs[down]["cout"] != cout:
+                fail("{}: the shortcut has {} channels, the residual branch {}".format(name, convs[down]["cout"], cout))
+            if down is None and (cin != cout or any(cv["geom"][2:4] != (1, 1) for cv in convs[i0:i0 + 3])):
+                fail("{}: an identity shortcut needs equal channels and stride 1".format(name))
+            blocks.append(dict(name=name, conv1=i0, conv2=i0 + 1, conv3=i0 + 2, downsample=down))
+            cin, producer = cout, "relu"
+    if not blocks:
+        fail("no bottleneck blocks found")
+    if 2 * convs[0]["cin"] > 8:
+        fail("{}: {} image channels (at most 4)".format(convs[0]["name"], convs[0]["cin"]))
+    return ResNetPlan(convs, blocks, pk + ps + pp)
+
+
+class ResNetEncoder:
+    """The reference's bottleneck ResNet encoders (models/resnet.py resnet50 / resnet101, any `layers`) as a device-resident, batched LRP
+    engine in the pattern of `Vgg16`: `forward` traces B images once - activations and, per conv, the relevance coefficient q that folds
+    the BatchNorm rule and the division by Z+ (per Add, its two split coefficients) - and `relevance` turns n_maps relevance tensors at
+    the feature map into image-sized maps, each on the trace of image map2img[m], as a chain of transposed convs (`lrpx_conv_geom_ex`,
+    K = cout, W+ only) with NHWC tensors throughout.  The preset only: alpha 1, beta 0, ignore_bias, BatchNorm epsilon rule, ReLU
+    identity, winner-take-all pool (lrp_wrapper.py:7-12,42-56).  DESIGN.md 5.8."""
+
+    def __init__(self, module):
+        plan = match_bottleneck_resnet(module)
+        tensors = list(module.parameters()) + list(module.buffers())
+        if not tensors or any(t.device.type != "cuda" for t in tensors):
+            raise ValueError("ResNetEncoder: the model must live on the GPU (no CPU path)")
+        self.device = tensors[0].device
+        self.plan = plan
+        self.cin = plan.convs[0]["cin"]
+        self.c2 = 8                                   # the split image [x+ | x- | 0..] (lrpx_nchw_to_nhwc_posneg)
+        self.packs = []
+        for cv in plan.convs:
+            wt = cv["module"].weight.detach().to(torch.float32)
+            bn = cv["bn"]
+            sd = torch.sqrt(bn.running_var.detach().float() + bn.eps)
+            w = (bn.weight.detach().float() / sd).contiguous()                                       # lrp_modules.py:210
+            b = (bn.bias.detach().float() - (bn.running_mean.detach().float() * bn.weight.detach().float()) / sd).contiguous()   # :211
+            wpos = wt.clamp(min=0)
+            if cv["nonneg"]:            # x >= 0: Z+ = conv(x, W+), K = cin;  columns [W | W+] share one gather of the input tile
+                fwd = conv_geom_pack(torch.cat([wt, wpos], 0), _lib.GEOM_FWD)
+                bwd = conv_geom_pack(wpos, _lib.GEOM_BWD)
+                k_in = cv["cin"]
+            else:                       # the stem on the split image: y = [x+ | x-] [W | W], Z = [x+ | x-] [W+ | W-]  (lrp_modules.py:81-84)
+                pad = torch.zeros(wt.shape[0], self.c2 - 2 * self.cin, *wt.shape[2:], device=self.device)
+                zrow = torch.cat([wpos, wt.clamp(max=0), pad], 1)
+                fwd = conv_geom_pack(torch.cat([torch.cat([wt, wt, pad], 1), zrow], 0), _lib.GEOM_FWD)
+                bwd = conv_geom_pack(zrow, _lib.GEOM_BWD)
+                k_in = self.c2
+            self.packs.append(dict(fwd=fwd, bwd=bwd, w=w, b=b, k_in=k_in, cout=cv["cout"], geom=cv["geom"]))
+        torch.cuda.current_stream().synchronize()
+        self._reset()
+
+    def _reset(self):
+        self.trace, self.shape, self._ws, self.n_img = None, None, {}, 0
+
+    def replica(self):
+        """Same packed weights, own trace / workspace buffers (for a second batch in flight on another stream)."""
+        import copy
+        r = copy.copy(self)
+        r._reset()
+        return r
+
+    # ---- shapes ------------------------------------------------------------------------------------------------------------------------
+    def _layout(self, H, W):
+        """[(hw_in, hw_out)] per conv, the pool's (hw_in, hw_out) and the feature map's size for an H x W image; ValueError where a
+        window does not fit or a block's two branches disagree"""
+        convs, dims = self.plan.convs, [None] * len(self.plan.convs)
+
+        def out_of(i, hw):
+            kh, kw, sh, sw, ph, pw = convs[i]["geom"]
+            if hw[0] + 2 * ph < kh or hw[1] + 2 * pw < kw:
+                raise ValueError("ResNetEncoder: {}: the {}x{} kernel does not fit its {}x{} input".format(convs[i]["name"], kh, kw, *hw))
+            dims[i] = (hw, (_conv_out(hw[0], kh, sh, ph), _conv_out(hw[1], kw, sw, pw)))
+            return dims[i][1]
+        hw = out_of(0, (H, W))
+        kh, kw, sh, sw, ph, pw = self.plan.pool
+        if hw[0] + 2 * ph < kh or hw[1] + 2 * pw < kw:
+            raise ValueError("ResNetEncoder: the image is too small for the stem's pool")
+        pool = (hw, (_conv_out(hw[0], kh, sh, ph), _conv_out(hw[1], kw, sw, pw)))
+        hw = pool[1]
+        for blk in self.plan.blocks:
+            o = out_of(blk["conv3"], out_of(blk["conv2"], out_of(blk["conv1"], hw)))
+            short = out_of(blk["downsample"], hw) if blk["downsample"] is not None else hw
+            if short != o:
+                raise ValueError("ResNetEncoder: {}: the residual branch gives {}x{}, the shortcut {}x{}".format(blk["name"], *o, *short))
+            hw = o
+        return dims, pool, hw
+
+    def trace_bytes(self, B, H, W):
+        """bytes of the trace `forward` keeps for B images of H x W pixels (activations, q per conv, c1 / c2 per Add)"""
+        dims, pool, _ = self._layout(H, W)
+        f = H * W * self.c2 + pool[1][0] * pool[1][1] * self.packs[0]["cout"]
+        for i, pk in enumerate(self.packs):
+            f += 2 * dims[i][1][0] * dims[i][1][1] * pk["cout"]                    # act + q
+        for blk in self.plan.blocks:
+            o = dims[blk["conv3"]][1]
+            f += 3 * o[0] * o[1] * self.packs[blk["conv3"]]["cout"]                # the block's output, c1, c2
+        return 4 * B * f
+
+    # ---- trace ---------------------------------------------------------------------------------------------------------------------------
+    def forward(self, img_nchw, layer_ms=None):
+        """(B, cin, H, W) -> the feature map (B, h w, C) NHWC (a view into the trace).  Everything `relevance` needs from the images is
+        computed here, once per image.  layer_ms: a dict - the call then adds each conv's milliseconds under its name (HIP events)."""
+        img = _dev(img_nchw).detach().to(torch.float32).contiguous()
+        if img.dim() != 4 or img.shape[1] != self.cin:
+            raise ValueError("ResNetEncoder.forward: images must be (B, {}, H, W)".format(self.cin))
+        B, _, H, W = img.shape
+        dims, pool, feat_hw = self._layout(H, W)
+        dev = self.device
+        new = lambda pix, c: torch.empty(B, pix[0] * pix[1], c, dtype=torch.float32, device=dev)
+        if self.shape != (B, H, W):
+            t = {"xs": new((H, W), self.c2), "act": [], "q": [], "out": [], "c1": [], "c2": []}
+            for i, pk in enumerate(self.packs):
+                t["act"].append(new(dims[i][1], pk["cout"]))
+                t["q"].append(new(dims[i][1], pk["cout"]))
+            t["pool"] = new(pool[1], self.packs[0]["cout"])
+            for blk in self.plan.blocks:
+                for k in ("out", "c1", "c2"):
+                    t[k].append(new(dims[blk["conv3"]][1], self.packs[blk["conv3"]]["cout"]))
+            yz = max(2 * pk["cout"] * dims[i][1][0] * dims[i][1][1] for i, pk in enumerate(self.packs))
+            t["yz"] = torch.empty(B * yz, dtype=torch.float32, device=dev)
+            self.trace, self.shape, self._ws = t, (B, H, W), {}
+            self.dims, self.pool_dims, self.feat_hw = dims, pool, feat_hw
+        t = self.trace
+        self.n_img = B
+        lib = _lib.load()
+        check(lib.lrpx_nchw_to_nhwc_posneg(ptr(img), ptr(t["xs"]), B, self.cin, H * W, self.c2, stream_ptr()))
+
+        def conv(i, x, relu):
+            pk = self.packs[i]
+            ev = _events(layer_ms)
+            hw, ohw = dims[i]
+            yz = t["yz"][: B * ohw[0] * ohw[1] * 2 * pk["cout"]].view(B, ohw[0] * ohw[1], 2 * pk["cout"])
+            conv_geom_ex(x, pk["fwd"], _lib.GEOM_FWD, B, hw, ohw, pk["geom"], pk["k_in"], 2 * pk["cout"], out=yz)
+            resnet_bn_act_coef(yz, pk["w"], pk["b"], t["act"][i], t["q"][i], relu)
+            _events_done(ev, layer_ms, self.plan.convs[i]["name"])
+            return t["act"][i]
+        a = conv(0, t["xs"], True)
+        resnet_maxpool_fwd(a, t["pool"], B, pool[0], pool[1], self.packs[0]["cout"], self.plan.pool)
+        x = t["pool"]
+        for bi, blk in enumerate(self.plan.blocks):
+            y3 = conv(blk["conv3"], conv(blk["conv2"], conv(blk["conv1"], x, True), True), False)
+            short = conv(blk["downsample"], x, False) if blk["downsample"] is not None else x
+            resnet_add_relu_coef(y3, short, t["out"][bi], t["c1"][bi], t["c2"][bi])
+            x = t["out"][bi]
+        return x
+
+    # ---- relevance ---------------------------------------------------------------------------------------------------------------------
+    def relevance(self, r_feat_nhwc, map2img=None, out=None, layer_ms=None):
+        """compute_lrp (LRPtools/lrp_wrapper.py:63-87) for n_maps maps: (n_maps, h w, C) relevance at the feature map -> (n_maps, cin, H, W);
+        map m runs on the trace of image map2img[m] (int32 on the device; None: n_maps == B, map m on image m).  No forward work: the
+        pass is one Add split and three or four transposed convs per block, the pool gather, the stem's transposed conv and the fold.
+        layer_ms: as in `forward`."""
+        if self.trace is None:
+            raise ValueError("ResNetEncoder.relevance: no trace - call forward() first")
+        B = self.n_img
+        t, dims = self.trace, self.dims
+        r = _dev(r_feat_nhwc)
+        c_feat = self.packs[self.plan.blocks[-1]["conv3"]]["cout"]
+        if r.dim() != 3 or tuple(r.shape[1:]) != (self.feat_hw[0] * self.feat_hw[1], c_feat) or r.dtype != torch.float32:
+            raise ValueError("ResNetEncoder.relevance: r_feat_nhwc must be float32 (n_maps, {}, {}), got {}".format(
+                self.feat_hw[0] * self.feat_hw[1], c_feat, tuple(r.shape)))
+        n_maps = r.shape[0]
+        if n_maps == 0:
+            raise ValueError("ResNetEncoder.relevance: no maps")
+        if map2img is None:
+            if n_maps != B:
+                raise ValueError("ResNetEncoder.relevance: without map2img there is one map per image of the trace ({} maps, {} images)"
+                                 .format(n_maps, B))
+        else:
+            map2img = check_map2img(map2img, n_maps, B)
+        H, W = self.shape[1], self.shape[2]
+        if out is None:
+            out = torch.empty(n_maps, self.cin, H, W, dtype=torch.float32, device=self.device)
+        elif tuple(out.shape) != (n_maps, self.cin, H, W) or not out.is_contiguous():
+            raise ValueError("ResNetEncoder.relevance: out must be contiguous (n_maps, {}, {}, {})".format(self.cin, H, W))
+        r = r.contiguous()
+        ws = self._workspace(n_maps)
+
+        def convT(i, r_out, x, addend, dst):
+            pk = self.packs[i]
+            ev = _events(layer_ms)
+            hw, ohw = dims[i]
+            n_oc = x.shape[2]
+            o = dst[: n_maps * hw[0] * hw[1] * n_oc].view(n_maps, hw[0] * hw[1], n_oc)
+            conv_geom_ex(r_out, pk["bwd"], _lib.GEOM_BWD, n_maps, hw, ohw, pk["geom"], pk["cout"], n_oc, x=x, q=t["q"][i], addend=addend,
+                         map2img=map2img, n_img=B, out=o, validate=False)
+            _events_done(ev, layer_ms, self.plan.convs[i]["name"])
+            return o
+        cur = 0
+        for bi in range(len(self.plan.blocks) - 1, -1, -1):
+            blk = self.plan.blocks[bi]
+            x = t["out"][bi - 1] if bi > 0 else t["pool"]
+            r1 = ws["r1"][: r.numel()].view(r.shape)
+            r2 = ws["r2"][: r.numel()].view(r.shape)
+            resnet_add_split(r, t["c1"][bi], t["c2"][bi], map2img, r1, r2, n_maps, B)
+            ra = convT(blk["conv3"], r1, t["act"][blk["conv2"]], None, ws["a"])
+            rb = convT(blk["conv2"], ra, t["act"][blk["conv1"]], None, ws["b"])
+            if blk["downsample"] is not None:
+                r2 = convT(blk["downsample"], r2, x, None, ws["a"])
+            r = convT(blk["conv1"], rb, x, r2, ws["r"][cur])
+            cur = 1 - cur
+        pk0 = self.packs[0]
+        rp = ws["a"][: n_maps * t["act"][0][0].numel()].view(n_maps, *t["act"][0].shape[1:])
+        resnet_maxpool_rel(t["act"][0], r, map2img, rp, n_maps, B, self.pool_dims[0], self.pool_dims[1], pk0["cout"], self.plan.pool)
+        rs = convT(0, rp, t["xs"], None, ws["b"])
+        resnet_stem_fold(rs, out, n_maps, self.cin, self.cin, self.c2, H * W)
+        return out
+
+    def _workspace(self, n_maps):
+        """per-map scratch, sized once per (trace shape, n_maps): r1 / r2 of the Add split, two chain buffers, two block-input buffers"""
+        ws = self._ws.get(n_maps)
+        if ws is None:
+            per_blk = max(o[0].numel() for o in self.trace["out"])
+            per_in = max([self.trace["pool"][0].numel()] + [o[0].numel() for o in self.trace["out"]])
+            per_any = max([self.trace["xs"][0].numel(), per_in] + [a[0].numel() for a in self.trace["act"]])
+            new = lambda per: torch.empty(n_maps * per, dtype=torch.float32, device=self.device)
+            ws = {"r1": new(per_blk), "r2": new(per_blk), "a": new(per_any), "b": new(per_any), "r": [new(per_in), new(per_in)]}
+            self._ws = {n_maps: ws}
+        return ws
+
+
+def _events(layer_ms):
+    if layer_ms is None:
+        return None
+    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+    ev[0].record()
+    return ev
+
+
+def _events_done(ev, layer_ms, name):
+    if ev is not None:
+        ev[1].record()
+        ev[1].synchronize()
+        layer_ms[name] = layer_ms.get(name, 0.) + ev[0].elapsed_time(ev[1])

@@ -3,12 +3,19 @@
 tests/golden/make_golden_resnet.py (`bottleneck_net(base=64, blocks=[3, 4, 6, 3])`, seeded weights) on a (4, 3, 224, 224) batch.
 
     python tools/resnet_lrp_timing.py [--out profiles/resnet_lrp_timing.txt] [--batch 4] [--iters 3]
+    python tools/resnet_lrp_timing.py --engine [--engine-out profiles/resnet_engine_timing.txt] [--words 5]
 
 Reports the whole call, the milliseconds per leaf type (HIP events around each rule call, layout conversions and the rule's checks
 included) and every distinct launch of the runtime-geometry conv engine (csrc/conv_geom.hip) with its flop as issued -
 2 n OH OW kh kw K n_oc with the K and n_oc the launch was given, i.e. with the doubled channels of the split [x+ | x-] storage - as
 achieved TFLOP/s against the 157 TFLOP/s fp32-MFMA peak.  Times are HIP events on one stream after a warm-up call, averaged over
---iters calls; an interval around one launch on an otherwise idle stream includes that launch's latency.  Nothing is asserted."""
+--iters calls; an interval around one launch on an otherwise idle stream includes that launch's latency.  Nothing is asserted.
+
+--engine adds a second leg after that report (which it leaves as it is): the batched engine (`ops.ResNetEncoder`) on
+--batch images x --words words = 20 maps, against the generic driver given the same 20 maps as 20 replicated images, in the same
+process.  It reports the milliseconds per trace and per relevance call, the engine's per-layer times, the achieved TFLOP/s of its
+transposed convs (flop as issued: 2 n_maps OH OW kh kw K n_oc) and the speed-up, and says whether the 2x floor of the engine's issue
+is met; which layers hold it back is read off the per-layer table."""
 import argparse
 import collections
 import os
@@ -23,6 +30,9 @@ def main():
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--out", default=None, help="also write the report to this file")
+    ap.add_argument("--engine", action="store_true", help="add the batched-engine leg (ops.ResNetEncoder against the generic driver)")
+    ap.add_argument("--words", type=int, default=5, help="--engine: maps per image")
+    ap.add_argument("--engine-out", default=None, help="--engine: also write that leg's report to this file")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -114,6 +124,73 @@ def main():
     sys.stdout.write(report)
     if a.out:
         with open(a.out, "w") as f:
+            f.write(report)
+    if a.engine:
+        engine_leg(a, net, x)
+
+
+def engine_leg(a, net, x):
+    import torch
+    from lrp_amd import _lib, ops
+    g = torch.Generator().manual_seed(1)
+    n_maps = a.batch * a.words
+    map2img = torch.arange(n_maps, dtype=torch.int32).div(a.words, rounding_mode="floor").to(torch.int32).cuda()
+    with torch.no_grad():
+        feat_shape = tuple(net(x[:1]).shape[1:])
+    targets = torch.randn((n_maps,) + feat_shape, generator=g).cuda()
+    x_rep = x[map2img.long()].contiguous()
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        fn()                                      # warm-up
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(a.iters):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / a.iters
+    generic_ms = timed(lambda: net.compute_lrp(x_rep.clone(), target=targets))
+    eng = ops.ResNetEncoder(net)
+    t_nhwc = ops.nchw_to_nhwc(targets)
+    trace_ms = timed(lambda: eng.forward(x))
+    rel_ms = timed(lambda: eng.relevance(t_nhwc, map2img))
+    both_ms = timed(lambda: (eng.forward(x), eng.relevance(t_nhwc, map2img)))
+    fwd_layers, rel_layers = {}, {}
+    for _ in range(a.iters):
+        eng.forward(x, layer_ms=fwd_layers)
+        eng.relevance(t_nhwc, map2img, layer_ms=rel_layers)
+    lines = [f"# tools/resnet_lrp_timing.py --engine --batch {a.batch} --words {a.words} --iters {a.iters}",
+             f"== bottleneck_net(base=64, blocks=[3,4,6,3]), {a.batch} images x {a.words} words = {n_maps} maps at 224 x 224, "
+             f"{torch.cuda.get_device_name(0)}",
+             f"generic driver, compute_lrp on {n_maps} replicated images : {generic_ms:9.2f} ms",
+             f"engine, forward (trace of {a.batch} images)             : {trace_ms:9.2f} ms",
+             f"engine, relevance ({n_maps} maps)                       : {rel_ms:9.2f} ms",
+             f"engine, forward + relevance                          : {both_ms:9.2f} ms",
+             f"trace memory                                         : {eng.trace_bytes(a.batch, 224, 224) / 2**20 / a.batch:9.1f} MiB per image",
+             f"speed-up over the generic driver (same run)          : {generic_ms / both_ms:9.2f} x   (floor 2.00 x: "
+             f"{'met' if generic_ms / both_ms >= 2.0 else 'NOT met'})", "",
+             "per layer, a pass with one HIP-event wait per layer (ms per call; trace = stacked forward conv + BN / coefficient pass, "
+             f"relevance = transposed conv; flop as issued, % of {PEAK_TFLOPS:.0f} TFLOP/s)",
+             f"  {'layer':<24} {'kernel':<6} {'stride':<6} {'map':<9} {'cin':>5} {'cout':>5} {'trace ms':>9} {'rel ms':>8} {'rel GFLOP':>9} {'TFLOP/s':>8} {'%peak':>6}"]
+    tot_ms = tot_fl = 0.0
+    for i, cv in enumerate(eng.plan.convs):
+        kh, kw, sh, sw, _, _ = cv["geom"]
+        hw, ohw = eng.dims[i]
+        n_oc = eng.c2 if not cv["nonneg"] else cv["cin"]
+        flop = 2.0 * n_maps * ohw[0] * ohw[1] * kh * kw * cv["cout"] * n_oc
+        rms = rel_layers[cv["name"]] / a.iters
+        tf = flop / (rms * 1e-3) / 1e12
+        tot_ms += rms
+        tot_fl += flop
+        lines.append(f"  {cv['name']:<24} {kh}x{kw:<4} {sh}x{sw:<4} {hw[0]}x{hw[1]:<5} {cv['cin']:5d} {cv['cout']:5d} "
+                     f"{fwd_layers[cv['name']] / a.iters:9.3f} {rms:8.3f} {flop / 1e9:9.2f} {tf:8.2f} {100 * tf / PEAK_TFLOPS:6.1f}")
+    lines.append(f"  all transposed convs: {tot_ms:.2f} ms, {tot_fl / 1e9:.1f} GFLOP, {tot_fl / (tot_ms * 1e-3) / 1e12:.2f} TFLOP/s "
+                 f"({100 * tot_fl / (tot_ms * 1e-3) / 1e12 / PEAK_TFLOPS:.1f} % of {PEAK_TFLOPS:.0f})")
+    report = "\n".join(lines) + "\n"
+    sys.stdout.write(report)
+    if a.engine_out:
+        with open(a.engine_out, "w") as f:
             f.write(report)
 
 
