@@ -35,7 +35,8 @@ enum {
 /* The runtime-geometry conv engine and the general MaxPool2d rule (lrpx_conv_geom, lrpx_conv_geom_pack,
  * lrpx_conv_geom_packed_floats, lrpx_maxpool_rule) came WITHOUT a new version number: a caller detects them by the presence
  * of the symbols (dlsym / hasattr on the loaded library).
- * The same holds for the batched ResNet engine's entries (lrpx_conv_geom_ex, lrpx_resnet_*).
+ * The same holds for the batched ResNet engine's entries (lrpx_conv_geom_ex, lrpx_resnet_*) and their conv mode 1 siblings
+ * (lrpx_conv_geom_packed_bf16x3_bytes, lrpx_conv_geom_pack_bf16x3, lrpx_conv_geom_ex_b6).
  * 101: the alpha-beta Conv2d rule (LRPX_PACK_*_PN*, lrpx_divide_alpha_beta, lrpx_maxpool2x2_relevance_ab); 100 before it */
 int lrpx_version(void);
 const char* lrpx_last_error_string(void);
@@ -197,6 +198,18 @@ typedef struct lrpx_conv_geom_ex_desc {
 } lrpx_conv_geom_ex_desc;
 /* fp32 MFMA, fp32 accumulation (the grade of conv mode 0); no atomics: a map's result does not depend on the other maps. */
 int lrpx_conv_geom_ex(const lrpx_conv_geom_ex_desc* d, void* stream);
+
+/* ---- the batched engine in the exact arithmetic of conv mode 1 (csrc/conv_geom_b6.hip; ops.ResNetEncoder(conv_mode=1))
+ * Every fp32 operand is split exactly into three bf16 planes; the six plane products with i + j <= 2 run on
+ * v_mfma_f32_32x32x16_bf16 with fp32 accumulation, small terms first: fp32-grade results in 12 bf16 MFMAs per (tap, 32-channel chunk)
+ * where lrpx_conv_geom_ex issues 16 fp32 ones.  Detected by the presence of the symbols, like the other ResNet entries. */
+/* bytes of the bf16x3 image: ceil(n_oc / 32) * taps * ceil(k / 32) * 2 k-steps * 3 planes * 1024 */
+size_t lrpx_conv_geom_packed_bf16x3_bytes(int n_oc, int k, int taps);
+/* as lrpx_conv_geom_pack (the caller stacks W+ / W- first); packed: lrpx_conv_geom_packed_bf16x3_bytes bytes, 16-byte aligned */
+int lrpx_conv_geom_pack_bf16x3(const float* w, int cout, int cin, int kh, int kw, int dir, void* packed, void* stream);
+/* lrpx_conv_geom_ex with `wpacked` the bf16x3 image of the same direction: same descriptor, same refusals, same tiling and masking,
+ * no atomics.  An in * q that overflows to +-inf comes out NaN here (the lower planes of inf are NaN), inf there. */
+int lrpx_conv_geom_ex_b6(const lrpx_conv_geom_ex_desc* d, void* stream);
 
 /* ---- elementwise / layout kernels -------------------------------------------------------------- */
 /* NHWC <-> BLOCKED (csrc/blocked.h): n_groups tensors of pix_per_group pixels x c channels (c %% 16 == 0), each its own block set

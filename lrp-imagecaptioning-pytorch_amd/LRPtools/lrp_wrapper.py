@@ -18,8 +18,9 @@ relevance pass (lrp_wrapper.py:37-87).  Here `add_lrp` validates the same leaf -
 `add_lrp(model, lrp_params=...)` lays a dict over the preset's parameters (the reference's add_lrp has the comment "Override default
 parameters if provided" and no argument): the VGG16 encoder with another alpha / beta and `ignore_bias=True` runs the batched
 `ops.Vgg16.relevance_alpha_beta`, with `ignore_bias=False` the generic driver.
-For a bottleneck ResNet under the preset `add_lrp` additionally attaches `model.compute_lrp_maps(images, targets, map2img=None)`: the batched
-engine `ops.ResNetEncoder` (one trace per image, one map per target row, no hooks, no `.grad`).  `compute_lrp` is unchanged.
+For a bottleneck ResNet under the preset `add_lrp` additionally attaches `model.compute_lrp_maps(images, targets, map2img=None, conv_mode=0)`:
+the batched engine `ops.ResNetEncoder` (one trace per image, one map per target row, no hooks, no `.grad`; conv_mode=1: its
+contractions in the exact bf16-split arithmetic).  `compute_lrp` is unchanged.
 Improvement over the reference: `add_lrp` is idempotent (the reference stacks hooks on every call, which
 multiplies its cost without changing the result)."""
 import torch
@@ -117,27 +118,31 @@ def _attach_resnet_engine(model, params):
     """`model.compute_lrp_maps` for a bottleneck ResNet under the preset (ops.match_bottleneck_resnet); any other model or `lrp_params`:
     the attribute is absent.  Installs no hooks; the engine (packed weights) is built at the first call."""
     model.__dict__.pop("compute_lrp_maps", None)
-    model.__dict__.pop("_lrpx_resnet", None)
+    for key in [k for k in model.__dict__ if k.startswith("_lrpx_resnet")]:
+        del model.__dict__[key]
     if params != SequentialPresetA().lrp_params:
         return
     try:
         ops.match_bottleneck_resnet(model)
     except ValueError:
         return
-    model.compute_lrp_maps = lambda images, targets, map2img=None: compute_lrp_maps(model, images, targets, map2img)
+    model.compute_lrp_maps = lambda images, targets, map2img=None, conv_mode=0: compute_lrp_maps(model, images, targets, map2img, conv_mode)
 
 
-def compute_lrp_maps(model, images, targets, map2img=None):
+def compute_lrp_maps(model, images, targets, map2img=None, conv_mode=0):
     """The batched form of `compute_lrp` for the bottleneck ResNet encoders: `images` (B, 3, H, W) are traced ONCE and every row of
     `targets` (n_maps, C, h, w) NCHW - the relevance at the encoder's output - becomes one map (n_maps, 3, H, W) on the trace of image
     map2img[m] (int32 tensor on the device; None: n_maps == B, map m on image m).  Runs `ops.ResNetEncoder` (built on first use from
     the model's weights as they are then; `add_lrp(model)` again after changing them), not the hooks of the generic driver.  Each map
     equals what `compute_lrp` returns for (that image, that target) on a FRESH sample tensor: this function does not touch `.grad` -
     it neither reads nor accumulates into `images.grad` - and returns the maps themselves, not a running sum.  Like `compute_lrp` it
-    asserts the result is finite and not all zero (lrp_wrapper.py:81)."""
-    eng = model.__dict__.get("_lrpx_resnet")
+    asserts the result is finite and not all zero (lrp_wrapper.py:81).  conv_mode: the engine's arithmetic (`ops.ResNetEncoder`: 0 fp32
+    MFMA, 1 exact bf16 split); the model keeps one engine per mode, `model._lrpx_resnet` for mode 0."""
+    key = "_lrpx_resnet" if conv_mode == 0 else "_lrpx_resnet_mode{}".format(conv_mode)
+    eng = model.__dict__.get(key)
     if eng is None:
-        eng = model._lrpx_resnet = ops.ResNetEncoder(model)
+        eng = ops.ResNetEncoder(model, conv_mode=conv_mode)
+        setattr(model, key, eng)
     feats = eng.forward(images.detach())
     hw = eng.feat_hw
     if targets.dim() != 4 or tuple(targets.shape[1:]) != (feats.shape[2], hw[0], hw[1]):

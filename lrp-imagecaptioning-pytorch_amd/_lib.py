@@ -225,6 +225,9 @@ SIGNATURES = {
     "lrpx_conv_geom_pack": (_i, [_f, _i, _i, _i, _i, _i, _f, _f]),
     "lrpx_max_abs_diff": (_i, [_f, _f, _l, _f, _f]),
     "lrpx_conv_geom_ex": (_i, [C.POINTER(ConvGeomExDesc), _f]),
+    "lrpx_conv_geom_packed_bf16x3_bytes": (_sz, [_i, _i, _i]),
+    "lrpx_conv_geom_pack_bf16x3": (_i, [_f, _i, _i, _i, _i, _i, _f, _f]),
+    "lrpx_conv_geom_ex_b6": (_i, [C.POINTER(ConvGeomExDesc), _f]),
     "lrpx_resnet_bn_act_coef": (_i, [_f, _i, _f, _f, _f, _f, _l, _i, _i, _f]),
     "lrpx_resnet_add_relu_coef": (_i, [_f, _f, _f, _f, _f, _l, _f]),
     "lrpx_resnet_maxpool_fwd": (_i, [_f, _f] + [_i] * 12 + [_f]),

@@ -202,6 +202,17 @@ def conv_geom_pack(w, direction):
     return out
 
 
+def conv_geom_pack_bf16x3(w, direction):
+    """w (cout, cin, kh, kw) on the device -> the bf16x3 fragments of `lrpx_conv_geom_ex_b6` for that direction (as `conv_geom_pack`):
+    every weight split exactly into three bf16 planes (csrc/conv_geom_b6.hip).  A uint8 tensor."""
+    lib = _lib.load()
+    cout, cin, kh, kw = w.shape
+    k, n_oc = (cin, cout) if direction == _lib.GEOM_FWD else (cout, cin)
+    out = torch.empty(lib.lrpx_conv_geom_packed_bf16x3_bytes(n_oc, k, kh * kw), dtype=torch.uint8, device=w.device)
+    check(lib.lrpx_conv_geom_pack_bf16x3(ptr(w.to(torch.float32).contiguous()), cout, cin, kh, kw, direction, ptr(out), stream_ptr()))
+    return out
+
+
 def conv_geom(inp, wpacked, direction, n, hw, ohw, geom, k, n_oc, bias=None, x=None, out=None):
     """The runtime-geometry conv engine (csrc/conv_geom.hip), NHWC fp32.  hw = (H, W) the conv's input map, ohw = (OH, OW) its
     output map, geom = (kh, kw, sh, sw, ph, pw).  GEOM_FWD: inp (n, H W, k) -> out (n, OH OW, n_oc) (+ bias);
@@ -696,8 +707,9 @@ def check_map2img(map2img, n_maps, n_img):
 
 
 def conv_geom_ex(inp, wpacked, direction, n, hw, ohw, geom, k, n_oc, bias=None, x=None, q=None, addend=None, map2img=None, n_img=None,
-                 out=None, validate=True):
-    """`lrpx_conv_geom_ex` (csrc/conv_geom_ex.hip), NHWC fp32; hw / ohw / geom as `conv_geom`.  GEOM_FWD: inp (n, H W, k) -> out
+                 out=None, validate=True, b6=False):
+    """`lrpx_conv_geom_ex` (csrc/conv_geom_ex.hip; b6: `lrpx_conv_geom_ex_b6`, csrc/conv_geom_b6.hip, the exact bf16-split arithmetic of
+    conv mode 1, with wpacked from `conv_geom_pack_bf16x3`), NHWC fp32; hw / ohw / geom as `conv_geom`.  GEOM_FWD: inp (n, H W, k) -> out
     (n, OH OW, n_oc) (+ bias).  GEOM_BWD: inp (n maps, OH OW, k) -> out (n, H W, n_oc) = x[img] * convT(inp * q[img]) + addend with
     img = map2img[m] (None: identity); x (n_img, H W, n_oc), q (n_img, OH OW, k), addend like out.  validate: check map2img on the host
     first (`check_map2img`; a caller that already has passes False)."""
@@ -720,6 +732,10 @@ def conv_geom_ex(inp, wpacked, direction, n, hw, ohw, geom, k, n_oc, bias=None, 
         raise ValueError("conv_geom_ex: the output must hold n x pixels x n_oc floats")
     d = _lib.ConvGeomExDesc(ptr(_dev(inp)), ptr(_dev(wpacked)), ptr(_dev(bias)), ptr(_dev(x)), ptr(_dev(q)), ptr(_dev(addend)),
                             ptr(_dev(map2img)), ptr(_dev(out)), direction, n, n_img or 0, hw[0], hw[1], ohw[0], ohw[1], *geom, k, n_oc)
+    if b6:
+        _count("conv_geom_ex_b6", direction)
+        check(_lib.load().lrpx_conv_geom_ex_b6(C.byref(d), stream_ptr()))
+        return out
     _count("conv_geom_ex", direction)
     check(_lib.load().lrpx_conv_geom_ex(C.byref(d), stream_ptr()))
     return out
@@ -884,9 +900,20 @@ class ResNetEncoder:
     the BatchNorm rule and the division by Z+ (per Add, its two split coefficients) - and `relevance` turns n_maps relevance tensors at
     the feature map into image-sized maps, each on the trace of image map2img[m], as a chain of transposed convs (`lrpx_conv_geom_ex`,
     K = cout, W+ only) with NHWC tensors throughout.  The preset only: alpha 1, beta 0, ignore_bias, BatchNorm epsilon rule, ReLU
-    identity, winner-take-all pool (lrp_wrapper.py:7-12,42-56).  DESIGN.md 5.8."""
+    identity, winner-take-all pool (lrp_wrapper.py:7-12,42-56).  DESIGN.md 5.8.
+    conv_mode: the arithmetic of every contraction of the trace and of the maps - 0: fp32 MFMA (`lrpx_conv_geom_ex`); 1: the exact
+    bf16 split, six plane products on the bf16 MFMA (`lrpx_conv_geom_ex_b6`).  The engine's own choice: it does not
+    follow `lrpx_set_conv_mode`.  `replica()` shares packs and mode."""
 
-    def __init__(self, module):
+    CONV_MODES = (0, 1)
+
+    def __init__(self, module, conv_mode=0):
+        if isinstance(conv_mode, bool) or conv_mode not in self.CONV_MODES:
+            raise ValueError("ResNetEncoder: conv_mode {!r}: this engine has modes 0 (fp32 MFMA) and 1 (exact bf16 split); the f16 "
+                             "modes 2 / 3 are not built at these geometries".format(conv_mode))
+        self.conv_mode = conv_mode
+        self.b6 = conv_mode == 1
+        pack = conv_geom_pack_bf16x3 if self.b6 else conv_geom_pack
         plan = match_bottleneck_resnet(module)
         tensors = list(module.parameters()) + list(module.buffers())
         if not tensors or any(t.device.type != "cuda" for t in tensors):
@@ -904,14 +931,14 @@ class ResNetEncoder:
             b = (bn.bias.detach().float() - (bn.running_mean.detach().float() * bn.weight.detach().float()) / sd).contiguous()   # :211
             wpos = wt.clamp(min=0)
             if cv["nonneg"]:            # x >= 0: Z+ = conv(x, W+), K = cin;  columns [W | W+] share one gather of the input tile
-                fwd = conv_geom_pack(torch.cat([wt, wpos], 0), _lib.GEOM_FWD)
-                bwd = conv_geom_pack(wpos, _lib.GEOM_BWD)
+                fwd = pack(torch.cat([wt, wpos], 0), _lib.GEOM_FWD)
+                bwd = pack(wpos, _lib.GEOM_BWD)
                 k_in = cv["cin"]
             else:                       # the stem on the split image: y = [x+ | x-] [W | W], Z = [x+ | x-] [W+ | W-]  (lrp_modules.py:81-84)
                 pad = torch.zeros(wt.shape[0], self.c2 - 2 * self.cin, *wt.shape[2:], device=self.device)
                 zrow = torch.cat([wpos, wt.clamp(max=0), pad], 1)
-                fwd = conv_geom_pack(torch.cat([torch.cat([wt, wt, pad], 1), zrow], 0), _lib.GEOM_FWD)
-                bwd = conv_geom_pack(zrow, _lib.GEOM_BWD)
+                fwd = pack(torch.cat([torch.cat([wt, wt, pad], 1), zrow], 0), _lib.GEOM_FWD)
+                bwd = pack(zrow, _lib.GEOM_BWD)
                 k_in = self.c2
             self.packs.append(dict(fwd=fwd, bwd=bwd, w=w, b=b, k_in=k_in, cout=cv["cout"], geom=cv["geom"]))
         torch.cuda.current_stream().synchronize()
@@ -998,7 +1025,7 @@ class ResNetEncoder:
             ev = _events(layer_ms)
             hw, ohw = dims[i]
             yz = t["yz"][: B * ohw[0] * ohw[1] * 2 * pk["cout"]].view(B, ohw[0] * ohw[1], 2 * pk["cout"])
-            conv_geom_ex(x, pk["fwd"], _lib.GEOM_FWD, B, hw, ohw, pk["geom"], pk["k_in"], 2 * pk["cout"], out=yz)
+            conv_geom_ex(x, pk["fwd"], _lib.GEOM_FWD, B, hw, ohw, pk["geom"], pk["k_in"], 2 * pk["cout"], out=yz, b6=self.b6)
             resnet_bn_act_coef(yz, pk["w"], pk["b"], t["act"][i], t["q"][i], relu)
             _events_done(ev, layer_ms, self.plan.convs[i]["name"])
             return t["act"][i]
@@ -1051,7 +1078,7 @@ class ResNetEncoder:
             n_oc = x.shape[2]
             o = dst[: n_maps * hw[0] * hw[1] * n_oc].view(n_maps, hw[0] * hw[1], n_oc)
             conv_geom_ex(r_out, pk["bwd"], _lib.GEOM_BWD, n_maps, hw, ohw, pk["geom"], pk["cout"], n_oc, x=x, q=t["q"][i], addend=addend,
-                         map2img=map2img, n_img=B, out=o, validate=False)
+                         map2img=map2img, n_img=B, out=o, validate=False, b6=self.b6)
             _events_done(ev, layer_ms, self.plan.convs[i]["name"])
             return o
         cur = 0

@@ -4,6 +4,7 @@ tests/golden/make_golden_resnet.py (`bottleneck_net(base=64, blocks=[3, 4, 6, 3]
 
     python tools/resnet_lrp_timing.py [--out profiles/resnet_lrp_timing.txt] [--batch 4] [--iters 3]
     python tools/resnet_lrp_timing.py --engine [--engine-out profiles/resnet_engine_timing.txt] [--words 5]
+    python tools/resnet_lrp_timing.py --engine --conv-mode both --batch 16 [--engine-only] [--engine-out profiles/resnet_engine_b6_timing.txt]
 
 Reports the whole call, the milliseconds per leaf type (HIP events around each rule call, layout conversions and the rule's checks
 included) and every distinct launch of the runtime-geometry conv engine (csrc/conv_geom.hip) with its flop as issued -
@@ -15,7 +16,13 @@ achieved TFLOP/s against the 157 TFLOP/s fp32-MFMA peak.  Times are HIP events o
 --batch images x --words words = 20 maps, against the generic driver given the same 20 maps as 20 replicated images, in the same
 process.  It reports the milliseconds per trace and per relevance call, the engine's per-layer times, the achieved TFLOP/s of its
 transposed convs (flop as issued: 2 n_maps OH OW kh kw K n_oc) and the speed-up, and says whether the 2x floor of the engine's issue
-is met; which layers hold it back is read off the per-layer table."""
+is met; which layers hold it back is read off the per-layer table.
+
+--conv-mode picks the engine's arithmetic for that leg (0: fp32 MFMA, 1: the exact bf16 split of DESIGN.md 5.9).  `both` runs the leg
+in mode 0 and then compares the modes: both engines in this process, warmed, mode 0 and mode 1 ALTERNATING for --reps repetitions
+each (at least 5), HIP events around `forward` and around `relevance`; then the per-layer tables of both.  Baseline: the mode-0 engine
+of the same run.  Noise: the spread (max - min) of mode 0 over its repetitions - a difference inside it is reported as "no
+difference".  --engine-only skips the generic driver (the first report and the engine leg's comparison against it)."""
 import argparse
 import collections
 import os
@@ -33,6 +40,9 @@ def main():
     ap.add_argument("--engine", action="store_true", help="add the batched-engine leg (ops.ResNetEncoder against the generic driver)")
     ap.add_argument("--words", type=int, default=5, help="--engine: maps per image")
     ap.add_argument("--engine-out", default=None, help="--engine: also write that leg's report to this file")
+    ap.add_argument("--conv-mode", choices=["0", "1", "both"], default="0", help="--engine: the engine's arithmetic; both: compare them")
+    ap.add_argument("--reps", type=int, default=5, help="--conv-mode both: alternating repetitions per mode (at least 5)")
+    ap.add_argument("--engine-only", action="store_true", help="--engine: skip the generic driver's legs")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -48,6 +58,8 @@ def main():
     lrp_wrapper.add_lrp(net)
     g = torch.Generator().manual_seed(0)
     x = torch.randn(a.batch, 3, 224, 224, generator=g).cuda()
+    if a.engine and a.engine_only:
+        return engine_leg(a, net, x)
     with torch.no_grad():
         target = torch.randn(net(x).shape, generator=g).cuda()
 
@@ -150,8 +162,9 @@ def engine_leg(a, net, x):
         e1.record()
         e1.synchronize()
         return e0.elapsed_time(e1) / a.iters
-    generic_ms = timed(lambda: net.compute_lrp(x_rep.clone(), target=targets))
-    eng = ops.ResNetEncoder(net)
+    mode = 1 if a.conv_mode == "1" else 0
+    generic_ms = float("nan") if a.engine_only else timed(lambda: net.compute_lrp(x_rep.clone(), target=targets))
+    eng = ops.ResNetEncoder(net, conv_mode=mode)
     t_nhwc = ops.nchw_to_nhwc(targets)
     trace_ms = timed(lambda: eng.forward(x))
     rel_ms = timed(lambda: eng.relevance(t_nhwc, map2img))
@@ -160,16 +173,17 @@ def engine_leg(a, net, x):
     for _ in range(a.iters):
         eng.forward(x, layer_ms=fwd_layers)
         eng.relevance(t_nhwc, map2img, layer_ms=rel_layers)
-    lines = [f"# tools/resnet_lrp_timing.py --engine --batch {a.batch} --words {a.words} --iters {a.iters}",
+    lines = [f"# tools/resnet_lrp_timing.py --engine --conv-mode {a.conv_mode} --batch {a.batch} --words {a.words} --iters {a.iters}"
+             + (" --engine-only" if a.engine_only else ""),
              f"== bottleneck_net(base=64, blocks=[3,4,6,3]), {a.batch} images x {a.words} words = {n_maps} maps at 224 x 224, "
-             f"{torch.cuda.get_device_name(0)}",
-             f"generic driver, compute_lrp on {n_maps} replicated images : {generic_ms:9.2f} ms",
+             f"{torch.cuda.get_device_name(0)}, engine conv mode {mode}",
+             f"generic driver, compute_lrp on {n_maps} replicated images : {generic_ms:9.2f} ms" + ("  (skipped)" if a.engine_only else ""),
              f"engine, forward (trace of {a.batch} images)             : {trace_ms:9.2f} ms",
              f"engine, relevance ({n_maps} maps)                       : {rel_ms:9.2f} ms",
              f"engine, forward + relevance                          : {both_ms:9.2f} ms",
              f"trace memory                                         : {eng.trace_bytes(a.batch, 224, 224) / 2**20 / a.batch:9.1f} MiB per image",
              f"speed-up over the generic driver (same run)          : {generic_ms / both_ms:9.2f} x   (floor 2.00 x: "
-             f"{'met' if generic_ms / both_ms >= 2.0 else 'NOT met'})", "",
+             f"{'not run' if a.engine_only else 'met' if generic_ms / both_ms >= 2.0 else 'NOT met'})", "",
              "per layer, a pass with one HIP-event wait per layer (ms per call; trace = stacked forward conv + BN / coefficient pass, "
              f"relevance = transposed conv; flop as issued, % of {PEAK_TFLOPS:.0f} TFLOP/s)",
              f"  {'layer':<24} {'kernel':<6} {'stride':<6} {'map':<9} {'cin':>5} {'cout':>5} {'trace ms':>9} {'rel ms':>8} {'rel GFLOP':>9} {'TFLOP/s':>8} {'%peak':>6}"]
@@ -187,11 +201,74 @@ def engine_leg(a, net, x):
                      f"{fwd_layers[cv['name']] / a.iters:9.3f} {rms:8.3f} {flop / 1e9:9.2f} {tf:8.2f} {100 * tf / PEAK_TFLOPS:6.1f}")
     lines.append(f"  all transposed convs: {tot_ms:.2f} ms, {tot_fl / 1e9:.1f} GFLOP, {tot_fl / (tot_ms * 1e-3) / 1e12:.2f} TFLOP/s "
                  f"({100 * tot_fl / (tot_ms * 1e-3) / 1e12 / PEAK_TFLOPS:.1f} % of {PEAK_TFLOPS:.0f})")
+    if a.conv_mode == "both":
+        lines += [""] + mode_leg(a, net, x, t_nhwc, map2img, eng)
     report = "\n".join(lines) + "\n"
     sys.stdout.write(report)
     if a.engine_out:
         with open(a.engine_out, "w") as f:
             f.write(report)
+
+
+def mode_leg(a, net, x, t_nhwc, map2img, eng0):
+    """conv mode 0 against conv mode 1 of the engine, alternating in this process; returns the report's lines"""
+    import torch
+    from lrp_amd import ops
+    reps = max(5, a.reps)
+    engs = {0: eng0, 1: ops.ResNetEncoder(net, conv_mode=1)}
+    for e in engs.values():                       # warm-up: trace buffers, workspaces, every kernel loaded
+        e.forward(x)
+        e.relevance(t_nhwc, map2img)
+    torch.cuda.synchronize()
+    r0, r1 = engs[0].relevance(t_nhwc, map2img), engs[1].relevance(t_nhwc, map2img)
+    dev = ((r1 - r0).abs().amax(dim=(1, 2, 3)) / r0.abs().amax(dim=(1, 2, 3))).max().item()
+
+    def once(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+    fwd, rel = {0: [], 1: []}, {0: [], 1: []}
+    for _ in range(reps):
+        for m in (0, 1):
+            fwd[m].append(once(lambda: engs[m].forward(x)))
+            rel[m].append(once(lambda: engs[m].relevance(t_nhwc, map2img)))
+    fl, rl = {0: {}, 1: {}}, {0: {}, 1: {}}
+    for _ in range(a.iters):
+        for m in (0, 1):
+            engs[m].forward(x, layer_ms=fl[m])
+            engs[m].relevance(t_nhwc, map2img, layer_ms=rl[m])
+    med = lambda v: sorted(v)[len(v) // 2]
+    spread = lambda v: max(v) - min(v)
+
+    def verdict(t):
+        d = med(t[0]) - med(t[1])
+        if abs(d) <= spread(t[0]):
+            return "no difference (inside mode 0's spread)"
+        return f"mode 1 {'faster' if d > 0 else 'SLOWER'}: {med(t[0]) / med(t[1]):.2f} x"
+    lines = [f"== conv mode 0 (fp32 MFMA) against conv mode 1 (bf16 split, six products), {reps} alternating repetitions each, ms per call",
+             f"  largest difference of a mode-1 map from its mode-0 map: {dev:.2e} of the map's maximum",
+             f"  {'':<10} {'mode 0 median':>13} {'min':>8} {'max':>8} {'mode 1 median':>13} {'min':>8} {'max':>8}   verdict"]
+    for name, t in (("forward", fwd), ("relevance", rel)):
+        lines.append(f"  {name:<10} {med(t[0]):13.3f} {min(t[0]):8.3f} {max(t[0]):8.3f} {med(t[1]):13.3f} {min(t[1]):8.3f} {max(t[1]):8.3f}   "
+                     + verdict(t))
+    lines += ["", f"per layer, one HIP-event wait per layer, mean of {a.iters} passes (ms; ratio = mode 0 / mode 1, above 1: mode 1 faster)",
+              f"  {'layer':<24} {'kernel':<6} {'stride':<6} {'map':<9} {'cin':>5} {'cout':>5} {'trace m0':>9} {'trace m1':>9} {'ratio':>6} "
+              f"{'rel m0':>8} {'rel m1':>8} {'ratio':>6}"]
+    tot = {k: 0.0 for k in ("f0", "f1", "r0", "r1")}
+    for i, cv in enumerate(eng0.plan.convs):
+        kh, kw, sh, sw, _, _ = cv["geom"]
+        hw = eng0.dims[i][0]
+        f0, f1, q0, q1 = (d[cv["name"]] / a.iters for d in (fl[0], fl[1], rl[0], rl[1]))
+        for k, v in zip(("f0", "f1", "r0", "r1"), (f0, f1, q0, q1)):
+            tot[k] += v
+        lines.append(f"  {cv['name']:<24} {kh}x{kw:<4} {sh}x{sw:<4} {hw[0]}x{hw[1]:<5} {cv['cin']:5d} {cv['cout']:5d} {f0:9.3f} {f1:9.3f} "
+                     f"{f0 / f1:6.2f} {q0:8.3f} {q1:8.3f} {q0 / q1:6.2f}")
+    lines.append(f"  {'all conv layers':<24} {'':<6} {'':<6} {'':<9} {'':>5} {'':>5} {tot['f0']:9.3f} {tot['f1']:9.3f} {tot['f0'] / tot['f1']:6.2f} "
+                 f"{tot['r0']:8.3f} {tot['r1']:8.3f} {tot['r0'] / tot['r1']:6.2f}")
+    return lines
 
 
 if __name__ == "__main__":
