@@ -88,6 +88,15 @@ int lrpx_pack_weights_f16x2(const float* w, int cout, int cin, int taps, int mod
  * layout of v_mfma_f32_32x32x64_f8f6f4 (K = 3 taps + a zero slot, x 16 channels).  3x3 kernels, modes BWD_POS / BWD_PLAIN */
 size_t lrpx_packed_f16f8_bytes(int n_oc, int k);
 int lrpx_pack_weights_f16f8(const float* w, int cout, int cin, int mode, void* packed, void* stream);
+/* Winograd F(2x2,3x3) form of the same relevance weights (modes BWD_POS / BWD_PLAIN, 3x3 kernels): for each of the 16 transform
+ * positions U = G g G^T evaluated in fp64, rounded once to fp32 and stored as three bf16 planes (16/9 of the bf16x3 image);
+ * lrpx_conv_desc.wpacked_wino */
+size_t lrpx_packed_wino_b6_bytes(int n_oc, int k);
+int lrpx_pack_weights_wino_b6(const float* w, int cout, int cin, int mode, void* packed, void* stream);
+/* which bf16x6 REL_MUL convs with wpacked_wino run on the Winograd kernel: bit 0 = 56 x 56, bit 1 = 28 x 28, bit 2 = 14 x 14 maps.
+ * Process-wide; initial value from LRPX_B6_WINO (default 7: all three).  bits < 0 only queries.  Returns the previous value.  0 = the direct
+ * kernels, bit for bit what the library computed before the Winograd kernel existed */
+int lrpx_set_b6_wino(int bits);
 /* K-chunk used by lrpx_conv_mfma for a given image width / taps / input channels */
 int lrpx_conv_kc(int hw, int taps, int cin);
 
@@ -144,6 +153,10 @@ typedef struct lrpx_conv_desc {
                                  below): [16-channel chunk][32-pixel block][4-channel part][pixel][4] - `in` / out: ONE block set over
                                  all n_maps * pixels, `x`: one block set per image.  f16x3 = 2 with REL_MUL (the relevance chain of conv
                                  mode 3) REQUIRES 7; its 224 x 224 kernel 1 (x and the output stay NHWC); every other kernel 0 */
+    const void* wpacked_wino; /* optional, bf16x6 with REL_MUL, no pool_am, hw 56 / 28 / 14, n_oc %% 64 == 0, NHWC `in`: the same weights from
+                                 lrpx_pack_weights_wino_b6.  Where lrpx_set_b6_wino has the bit of hw set the conv runs as Winograd F(2x2,3x3)
+                                 on the exact splits (16 instead of 36 six-product multiplications per 2x2 outputs and channel pair; fp32
+                                 grade like the direct kernel, other rounding); tile_group is ignored there */
 } lrpx_conv_desc;
 /* 3x3/pad-1 convolution (taps=9, square hw x hw maps) or dense GEMM (taps=1) on the fp32 MFMA with
  * the fused epilogues of the relevance rules.  Replaces F.conv2d / conv backward inside

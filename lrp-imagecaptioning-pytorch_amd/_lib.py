@@ -73,7 +73,7 @@ class ConvDesc(C.Structure):
                 ("bias", _f), ("x", _f), ("u", _f), ("zdiv", _f), ("map2img", _f),
                 ("out0", _f), ("out1", _f),
                 ("f16x3", _i), ("out_chunk", _i), ("in_amax", _f), ("out1_amax", _f), ("out0_amax", _f), ("pool_am", _f),
-                ("tile_group", _i), ("blocked", _i)]
+                ("tile_group", _i), ("blocked", _i), ("wpacked_wino", _f)]
 
 
 class ConvGeomDesc(C.Structure):
@@ -111,6 +111,9 @@ SIGNATURES = {
     "lrpx_pack_weights_f16x2": (_i, [_f, _i, _i, _i, _i, _f, _f]),
     "lrpx_packed_f16f8_bytes": (_sz, [_i, _i]),
     "lrpx_pack_weights_f16f8": (_i, [_f, _i, _i, _i, _f, _f]),
+    "lrpx_packed_wino_b6_bytes": (_sz, [_i, _i]),
+    "lrpx_pack_weights_wino_b6": (_i, [_f, _i, _i, _i, _f, _f]),
+    "lrpx_set_b6_wino": (_i, [_i]),
     "lrpx_conv_kc": (_i, [_i, _i, _i]),
     "lrpx_conv_mfma": (_i, [C.POINTER(ConvDesc), _f]),
     "lrpx_nchw_to_nhwc": (_i, [_f, _f, _i, _i, _i, _i, _f]),

@@ -95,6 +95,10 @@ int launch_b6_14_plain(const ConvArgs& a, hipStream_t s);
 int launch_b6_28_plain(const ConvArgs& a, hipStream_t s);
 int launch_b6_56_plain(const ConvArgs& a, hipStream_t s);
 
+int launch_b6_56_wino(const ConvArgs& a, hipStream_t s);      // ... Winograd F(2x2,3x3) on the exact splits (conv_wino_b6.h; a.wp = lrpx_pack_weights_wino_b6)
+int launch_b6_28_wino(const ConvArgs& a, hipStream_t s);
+int launch_b6_14_wino(const ConvArgs& a, hipStream_t s);
+
 int launch_h3_224_rel(const ConvArgs& a, hipStream_t s);
 int launch_h3_112_rel(const ConvArgs& a, hipStream_t s);
 int launch_h3_112n_rel(const ConvArgs& a, hipStream_t s);

@@ -1,0 +1,250 @@
+// Winograd F(2x2, 3x3) relevance conv on the exact bf16 splits (conv mode 1, REL_MUL epilogue).
+//
+//   Y = A^T [ (G g G^T) (.) (B^T d B) ] A        per 2x2 output tile and channel pair: 16 multiplications instead of 36
+//
+// The 16 element-wise products are 16 GEMMs  M[xi][tile][ci] = sum_co V[xi][tile][co] U[xi][co][ci]  (xi = 4 i + j), each
+// computed exactly like the direct kernel computes its one GEMM: both operands are fp32 values split EXACTLY into three bf16
+// planes, the six leading plane products run on v_mfma_f32_32x32x16_bf16 (smallest terms first), fp32 accumulation.
+//   * U = G g G^T is evaluated in fp64, rounded ONCE to fp32 and split at pack time (lrpx_pack_weights_wino_b6);
+//   * V = B^T d B is evaluated in fp32 (+-1 coefficients only: one add per element and stage) by the whole workgroup
+//     while it stages a 16-channel K-chunk, and kept in LDS as fp32 (64 KiB per chunk, double buffered); a wave owns
+//     two of the 16 xi, so every V element is read - and split into its planes - by exactly one wave;
+//   * GEMM rows are the 2x2 tiles of all maps flattened (tile T = map * (HW/2)^2 + ty * HW/2 + tx): fragments may straddle
+//     maps and the last workgroup is ragged; a tile's sums never depend on its neighbours or on the batch.
+// Workgroup: 8 waves, 64 tiles x 64 output channels x 16 xi; wave w accumulates xi = 2w, 2w+1 (2 row x 2 channel fragments
+// each: 128 accumulator registers).  The output transform exchanges M through LDS (the V buffers, after the K loop), then
+// out = x * Y as in epi_finish<EPI_REL_MUL> (NHWC or channel-chunked output, map2img for the multiplicand).
+// B fragments stream from L2: 32 B/clk/CU, sustainable only while the CUs of an XCD walk the same 64-channel slice
+// (16 xi x K x 64 x 6 B = 3.1 MB at K = 512): workgroups are ordered XCD-contiguous in bands of 32 row blocks.
+#pragma once
+#include "conv_bf16x6.h"
+
+namespace lrpx {
+
+constexpr int WINO_KQ = 1088;              // bytes per (xi, 4-channel quad) plane: 64 tiles x 16 B + 64 B (conflict-free float4 commits)
+constexpr int WINO_XI = 4 * WINO_KQ;       // bytes per xi
+constexpr int WINO_BUF = 16 * WINO_XI;     // bytes per V buffer
+constexpr int WINO_LDS = 2 * WINO_BUF;     // 139 264 B: one workgroup per CU
+constexpr int WINO_MROW = 33;              // floats per (xi, tile) row of the M exchange
+
+// 8 fp32 -> three bf16x8 planes, v == p0 + p1 + p2 exactly
+__device__ __forceinline__ void wino_split8(const f32x4 q0, const f32x4 q1, bf16x8& p0, bf16x8& p1, bf16x8& p2) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        unsigned short s0, s1, s2;
+        split3(e < 4 ? q0[e & 3] : q1[e & 3], s0, s1, s2);
+        p0[e] = (short)s0; p1[e] = (short)s1; p2[e] = (short)s2;
+    }
+}
+
+template <int HW>
+__global__ __launch_bounds__(512) void conv_wino_b6_kernel(ConvArgs a, int total_tiles, int m_blocks, int n_blocks) {
+    constexpr int TW = HW / 2, TPM = TW * TW, P = HW * HW;
+    constexpr int BAND = 32;
+    extern __shared__ __attribute__((aligned(16))) char ldsw[];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int li = lane & 31, lh = lane >> 5;
+
+    // XCD-contiguous order: the 32 row blocks of a band run the same channel slice at the same time on one XCD
+    const int bid = blockIdx.x;
+    const int xcd = bid & 7, idx = bid >> 3;
+    const int mb8 = (m_blocks + 7) >> 3;
+    const int band = idx / (BAND * n_blocks), rem = idx - band * (BAND * n_blocks);
+    const int band_rows = min(BAND, mb8 - band * BAND);
+    const int nblk = rem / band_rows;
+    const int mblk = (band * BAND + rem - nblk * band_rows) * 8 + xcd;
+    if (mblk >= m_blocks) return;
+    const int row0 = mblk * 64;
+    const int nchunk = a.cin / 16;
+
+    // ---- staging: thread = (tile, 4-channel quad, half of the transform rows); three patch rows x four columns each ----
+    const int seg = tid & 3, stile = (tid >> 2) & 63;
+    const int half = wave >> 2;                 // 0: V rows i = 0, 1 (patch rows 0..2)   1: i = 2, 3 (patch rows 1..3)
+    unsigned smask = 0;
+    long sbase;
+    {
+        const int T = row0 + stile;
+        const int n = T / TPM, t = T - n * TPM;
+        const int ty = t / TW, tx = t - ty * TW;
+        const int y0 = 2 * ty - 1 + half, x0 = 2 * tx - 1;
+        if (T < total_tiles) {
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    if (y0 + r >= 0 && y0 + r < HW && x0 + c >= 0 && x0 + c < HW) smask |= 1u << (r * 4 + c);
+        }
+        sbase = (((long)n * HW + y0) * HW + x0) * a.cin + seg * 4;
+    }
+    f32x4 rv[3][4];
+#define LRPXW_ISSUE(CHUNK)                                                                                          \
+    _Pragma("unroll") for (int r = 0; r < 3; ++r) _Pragma("unroll") for (int c = 0; c < 4; ++c) {                    \
+        rv[r][c] = f32x4{0, 0, 0, 0};                                                                               \
+        if (smask & (1u << (r * 4 + c)))                                                                            \
+            rv[r][c] = *reinterpret_cast<const f32x4*>(a.in + sbase + (long)(r * HW + c) * a.cin + (CHUNK) * 16);    \
+    }
+    // stage 1 (rows): t_0 = d0 - d2, t_1 = d1 + d2, t_2 = d2 - d1, t_3 = d1 - d3; stage 2 (columns) alike
+#define LRPXW_COMMIT(BUFIDX)                                                                                        \
+    {                                                                                                               \
+        char* vb = ldsw + (BUFIDX) * WINO_BUF + (half * 8) * WINO_XI + seg * WINO_KQ + stile * 16;                  \
+        _Pragma("unroll") for (int ii = 0; ii < 2; ++ii) {                                                          \
+            f32x4 t[4];                                                                                             \
+            _Pragma("unroll") for (int c = 0; c < 4; ++c)                                                           \
+                t[c] = half == 0 ? (ii == 0 ? rv[0][c] - rv[2][c] : rv[1][c] + rv[2][c])                            \
+                                 : (ii == 0 ? rv[1][c] - rv[0][c] : rv[0][c] - rv[2][c]);                           \
+            *reinterpret_cast<f32x4*>(vb + (ii * 4 + 0) * WINO_XI) = t[0] - t[2];                                   \
+            *reinterpret_cast<f32x4*>(vb + (ii * 4 + 1) * WINO_XI) = t[1] + t[2];                                   \
+            *reinterpret_cast<f32x4*>(vb + (ii * 4 + 2) * WINO_XI) = t[2] - t[1];                                   \
+            *reinterpret_cast<f32x4*>(vb + (ii * 4 + 3) * WINO_XI) = t[1] - t[3];                                   \
+        }                                                                                                           \
+    }
+
+    LRPXW_ISSUE(0)
+
+    f32x16 acc[2][2][2];     // [xi of the wave][row fragment][channel fragment]
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) acc[x][rt][nb][e] = 0.f;
+
+    // B fragments [ocb][xi][k-step][plane][64 lanes][16 B]: the fragments of channel block nb are re-loaded for the next
+    // (xi, k-step) as soon as its MFMAs are issued, i.e. half a step ahead
+    const u32x4* wp = reinterpret_cast<const u32x4*>(a.wp) + lane;
+    const long ocb_stride = (long)16 * nchunk * 192;
+    const int last_step = 2 * nchunk - 1;
+    auto bptr = [&](int step, int nb) -> const u32x4* {
+        const int s = min(step, last_step);
+        const int xi = 2 * wave + (s & 1), ks = s >> 1;
+        return wp + (long)(nblk * 2 + nb) * ocb_stride + ((long)xi * nchunk + ks) * 192;
+    };
+    u32x4 bq[2][3];
+#pragma unroll
+    for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+        for (int p = 0; p < 3; ++p) bq[nb][p] = bptr(0, nb)[p * 64];
+
+    LRPXW_COMMIT(0)
+    __syncthreads();
+
+    for (int chunk = 0; chunk < nchunk; ++chunk) {
+        const bool more = chunk + 1 < nchunk;
+        if (more) { LRPXW_ISSUE(chunk + 1) }
+        const char* vbuf = ldsw + (chunk & 1) * WINO_BUF;
+#pragma unroll
+        for (int x = 0; x < 2; ++x) {
+            const char* vx = vbuf + (2 * wave + x) * WINO_XI + (2 * lh) * WINO_KQ + li * 16;
+            bf16x8 ap[2][3];
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt) {
+                const f32x4 q0 = *reinterpret_cast<const f32x4*>(vx + rt * 512);
+                const f32x4 q1 = *reinterpret_cast<const f32x4*>(vx + rt * 512 + WINO_KQ);
+                wino_split8(q0, q1, ap[rt][0], ap[rt][1], ap[rt][2]);
+            }
+#pragma unroll
+            for (int nb = 0; nb < 2; ++nb) {
+                const bf16x8 b0 = __builtin_bit_cast(bf16x8, bq[nb][0]);
+                const bf16x8 b1 = __builtin_bit_cast(bf16x8, bq[nb][1]);
+                const bf16x8 b2 = __builtin_bit_cast(bf16x8, bq[nb][2]);
+#pragma unroll
+                for (int rt = 0; rt < 2; ++rt) {
+                    f32x16 c = acc[x][rt][nb];
+                    // smallest terms first
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[rt][2], b0, c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[rt][1], b1, c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[rt][0], b2, c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[rt][1], b0, c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[rt][0], b1, c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[rt][0], b0, c, 0, 0, 0);
+                    acc[x][rt][nb] = c;
+                }
+                const u32x4* nx = bptr(2 * chunk + x + 1, nb);
+#pragma unroll
+                for (int p = 0; p < 3; ++p) bq[nb][p] = nx[p * 64];
+            }
+        }
+        if (more) { LRPXW_COMMIT((chunk + 1) & 1) }
+        __syncthreads();
+    }
+#undef LRPXW_ISSUE
+#undef LRPXW_COMMIT
+
+    // ---- output transform Y = A^T M A (A^T = [1 1 1 0; 0 1 -1 -1]) through LDS, then out = x * Y ----
+    float* ms = reinterpret_cast<float*>(ldsw);
+    const float* __restrict__ X = a.X;
+    float* __restrict__ ob = a.out1 ? a.out1 : a.out0;
+    const int ncol = a.oc_split;
+    const int ch = a.out_chunk;
+    const int ostr = ch > 0 ? ch : ncol;
+    const long total_pix = (long)a.n_maps * P;
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {
+#pragma unroll
+            for (int x = 0; x < 2; ++x)
+#pragma unroll
+                for (int e = 0; e < 16; ++e)
+                    ms[((2 * wave + x) * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh) * WINO_MROW + li] = acc[x][rt][nb][e];
+            __syncthreads();
+#pragma unroll
+            for (int it = 0; it < 2; ++it) {
+                const int pr = tid + it * 512;
+                const int c = pr & 31, tl = pr >> 5;
+                float m[16];
+#pragma unroll
+                for (int xi = 0; xi < 16; ++xi) m[xi] = ms[(xi * 32 + tl) * WINO_MROW + c];
+                float s0[4], s1[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    s0[j] = (m[j] + m[4 + j]) + m[8 + j];
+                    s1[j] = (m[4 + j] - m[8 + j]) - m[12 + j];
+                }
+                const float y00 = (s0[0] + s0[1]) + s0[2], y01 = (s0[1] - s0[2]) - s0[3];
+                const float y10 = (s1[0] + s1[1]) + s1[2], y11 = (s1[1] - s1[2]) - s1[3];
+                const int T = row0 + rt * 32 + tl;
+                const int oc = (nblk * 2 + nb) * 32 + c;
+                if (T < total_tiles && oc < ncol) {
+                    const int n = T / TPM, t = T - n * TPM;
+                    const int ty = t / TW, tx = t - ty * TW;
+                    const long img = a.map2img ? a.map2img[n] : n;
+                    const int p = (2 * ty) * HW + 2 * tx;
+                    const float* xp = X + (img * P + p) * ncol + oc;
+                    const long obase = ch > 0 ? (long)(oc / ch) * total_pix * ch + (oc % ch) : (long)oc;
+                    float* op = ob + ((long)n * P + p) * ostr + obase;
+                    const float x00 = xp[0], x01 = xp[ncol], x10 = xp[(long)HW * ncol], x11 = xp[(long)(HW + 1) * ncol];
+                    __builtin_nontemporal_store(x00 * y00, &op[0]);
+                    __builtin_nontemporal_store(x01 * y01, &op[ostr]);
+                    __builtin_nontemporal_store(x10 * y10, &op[(long)HW * ostr]);
+                    __builtin_nontemporal_store(x11 * y11, &op[(long)(HW + 1) * ostr]);
+                }
+            }
+            __syncthreads();
+        }
+}
+
+template <int HW>
+int launch_conv_wino_b6(const ConvArgs& a, hipStream_t stream) {
+    constexpr int TPM = (HW / 2) * (HW / 2);
+    const long total_tiles = (long)a.n_maps * TPM;
+    const long m_blocks = ceil_div(total_tiles, 64);
+    const int n_blocks = a.n_oc / 64;
+    const long grid = ceil_div(m_blocks, 8) * 8 * n_blocks;
+    if (grid <= 0 || grid > 0x7fffffffL || a.n_oc % 64 != 0) {
+        set_error("conv_wino_b6: grid %ld out of range or n_oc %d not a multiple of 64", grid, a.n_oc);
+        return LRPX_EINVAL;
+    }
+    auto kern = conv_wino_b6_kernel<HW>;
+    static LdsOnce attr_once;
+    LRPX_TRY(reserve_lds_once(attr_once, kern, WINO_LDS, "conv_wino_b6"));
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), WINO_LDS, stream, a, (int)total_tiles, (int)m_blocks, n_blocks);
+    return check_launch("conv_wino_b6");
+}
+
+}  // namespace lrpx

@@ -5,6 +5,7 @@
 
 #include <mutex>
 
+#include <atomic>
 #include "common.h"
 #include "conv_mfma.h"
 #include "conv_bf16x6.h"
@@ -76,11 +77,18 @@ const Switches& switches() {
         w.x6_legacy = set("LRPX_X6_LEGACY");
         w.b6_wide = num("LRPX_B6_WIDE", 0);
         w.b6_rel_ksplit14 = num("LRPX_B6_REL_KSPLIT14", 2);
+        w.b6_wino = num("LRPX_B6_WINO", 7) & 7;
         w.b6_fwd_ksplit28 = num("LRPX_B6_FWD_KSPLIT28", 4);
         w.b6_fwd_ksplit56 = num("LRPX_B6_FWD_KSPLIT56", 2);
         return w;
     }();
     return sw;
+}
+
+static std::atomic<int> g_b6_wino{-1};
+int b6_wino_bits() {
+    const int v = g_b6_wino.load(std::memory_order_relaxed);
+    return v >= 0 ? v : switches().b6_wino;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -209,6 +217,46 @@ __global__ void pack_weights_bf16x3_kernel(const float* __restrict__ w, unsigned
     unsigned short p0, p1, p2;
     split3(v, p0, p1, p2);
     const long base = ((((long)ocb * nchunk + chunk) * taps + tap) * 3) * 512 + lane * 8 + j;
+    out[base] = p0; out[base + 512] = p1; out[base + 1024] = p2;
+}
+
+// Winograd F(2x2,3x3) weights of a relevance conv for conv_wino_b6.h: U[xi = 4 i + j] = (G g G^T)[i][j] with g[r][s] the kernel the
+// relevance conv applies (w[co][ci] flipped, clamped at 0 for BWD_POS), G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1].  Evaluated in fp64
+// (the products by 0, 1, .5 are exact, the sums run r = 0, 1, 2 then s = 0, 1, 2), rounded once to fp32 and split into three bf16 planes:
+// [ocb][xi 16][k-step][plane 3][lane 64][8 bf16], lane l holds U[xi][co = 16*kstep + 8*(l>>5) + j][ci = 32*ocb + (l&31)]
+__global__ void pack_weights_wino_b6_kernel(const float* __restrict__ w, unsigned short* __restrict__ out, int cout, int cin,
+                                            int mode, int k_pad, long total) {
+    long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;   // one thread per (.., lane, j): writes the 3 planes
+    if (idx >= total) return;
+    const int j = idx & 7;
+    const int lane = (idx >> 3) & 63;
+    long rest = idx >> 9;
+    const int nchunk = k_pad / 16;
+    const int ks = rest % nchunk; rest /= nchunk;
+    const int xi = rest % 16; rest /= 16;
+    const int ocb = (int)rest;
+    const int ci = ocb * 32 + (lane & 31);
+    const int co = ks * 16 + 8 * (lane >> 5) + j;
+    const double G[4][3] = {{1., 0., 0.}, {.5, .5, .5}, {.5, -.5, .5}, {0., 0., 1.}};
+    double u = 0.;
+    if (co < cout && ci < cin) {
+        const float* g = w + ((long)co * cin + ci) * 9;
+        const int i = xi >> 2, jj = xi & 3;
+        double t[3];
+        for (int s = 0; s < 3; ++s) {
+            double acc = 0.;
+            for (int r = 0; r < 3; ++r) {
+                float v = g[8 - (r * 3 + s)];
+                if (mode == LRPX_PACK_BWD_POS) v = fmaxf(v, 0.f);
+                acc += G[i][r] * (double)v;
+            }
+            t[s] = acc;
+        }
+        for (int s = 0; s < 3; ++s) u += t[s] * G[jj][s];
+    }
+    unsigned short p0, p1, p2;
+    split3((float)u, p0, p1, p2);
+    const long base = ((((long)ocb * 16 + xi) * nchunk + ks) * 3) * 512 + lane * 8 + j;
     out[base] = p0; out[base + 512] = p1; out[base + 1024] = p2;
 }
 
@@ -1062,6 +1110,28 @@ int lrpx_pack_weights_bf16x3(const float* w, int cout, int cin, int taps, int mo
     hipLaunchKernelGGL(pack_weights_bf16x3_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, w,
                        (unsigned short*)packed, cout, cin, taps, mode, k_pad, total);
     return check_launch("pack_weights_bf16x3");
+}
+
+size_t lrpx_packed_wino_b6_bytes(int n_oc, int k) {
+    return (size_t)round_up(n_oc, 32) * (size_t)round_up(k, 16) * 16 * 3 * sizeof(unsigned short);
+}
+
+int lrpx_pack_weights_wino_b6(const float* w, int cout, int cin, int mode, void* packed, void* stream) {
+    LRPX_CHECK_PTRS("lrpx_pack_weights_wino_b6", {w, "w"}, {packed, "packed"});
+    LRPX_REQUIRE(w && packed, "pack_weights_wino_b6: null pointer");
+    LRPX_REQUIRE(mode == LRPX_PACK_BWD_POS || mode == LRPX_PACK_BWD_PLAIN, "pack_weights_wino_b6: mode %d not supported", mode);
+    int n_oc_pad, k_pad;
+    pack_dims(cout, cin, mode, 16, &n_oc_pad, &k_pad);
+    long total = (long)n_oc_pad * k_pad * 16;     // threads: one per (oc, k, xi)
+    hipLaunchKernelGGL(pack_weights_wino_b6_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, w,
+                       (unsigned short*)packed, cout, cin, mode, k_pad, total);
+    return check_launch("pack_weights_wino_b6");
+}
+
+int lrpx_set_b6_wino(int bits) {
+    const int prev = b6_wino_bits();
+    if (bits >= 0) g_b6_wino.store(bits & 7, std::memory_order_relaxed);
+    return prev;
 }
 
 int lrpx_nchw_to_nhwc(const float* src, float* dst, int n, int c, int hw_pix, int c_pad, void* stream) {

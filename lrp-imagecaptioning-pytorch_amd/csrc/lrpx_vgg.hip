@@ -251,6 +251,14 @@ int conv_dispatch(const lrpx_conv_desc* d, hipStream_t s, int f16_ksplit) {
             if (d->hw == 28) return launch_b6_28_pool(a, s);
             LRPX_REQUIRE(false, "conv_mfma: no pooled-input bf16x6 kernel built for hw=%d n_oc=%d", d->hw, d->n_oc);
         }
+        if (d->epi == EPI_REL_MUL && d->wpacked_wino && !d->in_chunked && d->n_oc % 64 == 0 && d->hw <= 56 &&
+            (b6_wino_bits() & (d->hw == 56 ? 1 : (d->hw == 28 ? 2 : 4)))) {
+            // Winograd F(2x2,3x3) on the same exact splits (conv_wino_b6.h): chosen by the layer's map size, never by the batch
+            a.wp = reinterpret_cast<const float*>(d->wpacked_wino);
+            if (d->hw == 56) return launch_b6_56_wino(a, s);
+            if (d->hw == 28) return launch_b6_28_wino(a, s);
+            return launch_b6_14_wino(a, s);
+        }
         if (d->epi == EPI_REL_MUL) {
             const int b6w = switches().b6_wide;
             if ((b6w & 1) && d->n_oc >= 256 && d->hw == 56) return launch_b6_56w_rel(a, s);
@@ -404,9 +412,14 @@ static thread_local float tl_ms[17];
 struct VggPacked {   // offsets in floats into the packed blob
     size_t fwd[17], bwd[17], bwdp[17], bwd6[17], bwdp6[17], bwdh[17], bwdph[17], bwd8[17], bwdp8[17], fwd6[17], fwdh[17], bias[17], fwdh0, first6, first6p, first16, first16p, total;
     size_t chs[17];      // per-output-channel balance factors rs_l[c] of conv l (powers of two, see lrpx_vgg16_pack)
+    size_t bwdw6[17];    // Winograd F(2x2,3x3) form of bwd6 (lrpx_pack_weights_wino_b6) for the relevance convs wino_layer() names, else 0
     size_t spread;       // [17] per conv layer: largest ratio of row maxima max|W[c,:]| inside one 16-row K slice (lrpx_vgg16_row_spread)
     size_t scratch;      // scaled weight copies while packing: cout*cin*9 + 2*cout*2*cin*9 floats of the largest layer
 };
+// relevance convs that can run on conv_wino_b6.h: long K on 56 / 28 / 14-pixel maps, not under a pool (conv3_1/2, conv4_1/2, conv5_1/2/3)
+static bool wino_layer(int l) {
+    return l > 0 && kVgg[l].conv && kVgg[l].hw <= 56 && kVgg[l].cin % 64 == 0 && !(l + 1 < kNL && !kVgg[l + 1].conv);
+}
 static VggPacked vgg_packed_layout() {
     VggPacked p;
     size_t off = 0;
@@ -439,6 +452,10 @@ static VggPacked vgg_packed_layout() {
         if (kVgg[l].conv) off += (size_t)kVgg[l].cout;
     }
     p.spread = off; off += 32;
+    for (int l = 0; l < kNL; ++l) {
+        p.bwdw6[l] = 0;
+        if (wino_layer(l)) { p.bwdw6[l] = off; off += lrpx_packed_wino_b6_bytes(kVgg[l].cin, kVgg[l].cout) / sizeof(float); }
+    }
     p.scratch = off; off += (size_t)512 * 512 * 9 * 3;
     p.total = off;
     return p;
@@ -678,6 +695,7 @@ int lrpx_vgg16_pack(const float* const* w, const float* const* b, void* packed, 
                                        base + p.bwdp[l], stream));
         }
         if (l > 0) LRPX_TRY(lrpx_pack_weights_bf16x3(wr, L.cout, L.cin, 9, LRPX_PACK_BWD_POS, base + p.bwd6[l], stream));
+        if (wino_layer(l)) LRPX_TRY(lrpx_pack_weights_wino_b6(wr, L.cout, L.cin, LRPX_PACK_BWD_POS, base + p.bwdw6[l], stream));
         if (l > 0) LRPX_TRY(lrpx_pack_weights_f16x2(wr, L.cout, L.cin, 9, LRPX_PACK_BWD_POS, base + p.bwdh[l], stream));
         if (l > 0) LRPX_TRY(lrpx_pack_weights_f16x2(wd, 2 * L.cout, L.cin, 9, LRPX_PACK_FWD, base + p.fwdh[l], stream));
         if (l > 0) LRPX_TRY(lrpx_pack_weights_f16x2(w_plain, L.cout, L.cin, 9, LRPX_PACK_BWD_PLAIN, base + p.bwdph[l], stream));
@@ -982,6 +1000,7 @@ int lrpx_vgg16_relevance_ex(const void* packed, const void* trace, int n_img, co
             d.bf16x6 = 1; d.epi = EPI_REL_MUL; d.wpacked = pk + p.bwd6[l];
             d.tile_group = (n_maps % n_img == 0) ? n_maps / n_img : 0;
             if (l + 1 < kNL && !kVgg[l + 1].conv) d.pool_am = (const uint8_t*)(tr + t.am[l + 1]);
+            else if (wino_layer(l)) d.wpacked_wino = pk + p.bwdw6[l];      // (used where lrpx_set_b6_wino / LRPX_B6_WINO has the bit of L.hw)
         } else if (h3) {
             d.f16x3 = 1; d.epi = EPI_REL_MUL; d.wpacked = pk + p.bwdh[l]; d.in_amax = amax + (size_t)l * n_maps;
             // the maps of one image (the words of its caption) usually follow each other: tile-order hint for the
@@ -996,7 +1015,8 @@ int lrpx_vgg16_relevance_ex(const void* packed, const void* trace, int n_img, co
             if (blk) d.blocked = l == 1 ? 1 : 7;
         }
         else if (use_bf16x6) { d.bf16x6 = 1; d.wpacked = pk + p.bwd6[l]; }   // round 1's flow (LRPX_X6_LEGACY): EPI_REL, pool kernels
-        const int rel_ks = (b6 && L.hw == 14) ? switches().b6_rel_ksplit14 : 1;
+        // (14 x 14 on the Winograd kernel: one launch of 8 x ceil(49 n_maps / 64) workgroups, no K split)
+        const int rel_ks = (b6 && L.hw == 14 && !(d.wpacked_wino && (b6_wino_bits() & 4))) ? switches().b6_rel_ksplit14 : 1;
         if (rel_ks > 1 && (rel_ks & (rel_ks - 1)) == 0 && rel_ks <= 4 && (L.cout / 16) % rel_ks == 0) {
             // the 14 x 14 relevance layers K-split in two (LRPX_B6_REL_KSPLIT14): partial sums into the R buffer (unused in the fused flow), then
             // out = multiplicand * (pairwise sum) in rel_mul_finish.  At 320 maps the layers cost the same (1 120 -> 2 240 workgroups on 512 slots:

@@ -55,6 +55,20 @@ def pack_weights_bf16x3(w, cout, cin, mode, taps=9):
     return out
 
 
+def pack_weights_wino_b6(w, cout, cin, mode):
+    """3x3 relevance weights (PACK_BWD_POS / PACK_BWD_PLAIN) in the Winograd F(2x2,3x3) form of conv mode 1: U = G g G^T per transform
+    position, fp64 -> one rounding to fp32 -> three bf16 planes (for conv_mfma(..., bf16x6=1, wpacked_wino=...); csrc/conv_wino_b6.h)."""
+    lib = _lib.load()
+    out = torch.empty(lib.lrpx_packed_wino_b6_bytes(cin, cout) // 2, dtype=torch.int16, device=w.device)
+    check(lib.lrpx_pack_weights_wino_b6(ptr(w.contiguous()), cout, cin, mode, ptr(out), stream_ptr()))
+    return out
+
+
+def set_b6_wino(bits):
+    """lrpx_set_b6_wino: bit mask of the map sizes (56: 1, 28: 2, 14: 4) whose conv-mode-1 relevance convs run as Winograd; returns the previous mask"""
+    return _lib.load().lrpx_set_b6_wino(int(bits))
+
+
 def pack_weights_f16x2(w, cout, cin, mode, taps=9):
     """3x3 conv weights (taps = 9) or a dense (cout, cin) matrix (taps = 1) -> layer-scaled fp16 hi/lo planes in fragment
     layout (for conv_mfma(..., f16x3=1)).  Dense: PACK_BWD_PLAIN = the transposed product  out[m, i] = sum_o a[m, o] w[o, i]
@@ -125,7 +139,7 @@ def amax_maps(s, n_maps):
 def conv_desc(inp, wpacked, n_maps, hw, cin, n_oc, taps, epi, *, pix_per_map=0, stab=STAB_NONE, oc_split=0,
               relu=0, bias=None, x=None, u=None, zdiv=None, map2img=None, out0=None, out1=None, bf16x6=0,
               f16x3=0, in_amax=None, out1_amax=None, pool_am=None, out0_amax=None, blocked=0, tile_group=0, out_chunk=0,
-              in_chunked=0):
+              in_chunked=0, wpacked_wino=None):
     """the lrpx_conv_desc of one contraction (the tensors must outlive its use: the descriptor holds raw pointers).
     tile_group / out_chunk / in_chunked: the tile-order hint and the K-chunked S layouts the VGG16 chain sets (include/lrpx.h)"""
     d = ConvDesc()
@@ -138,6 +152,7 @@ def conv_desc(inp, wpacked, n_maps, hw, cin, n_oc, taps, epi, *, pix_per_map=0, 
     d.out0, d.out1 = ptr(out0), ptr(out1)
     d.blocked = blocked
     d.tile_group, d.out_chunk, d.in_chunked = tile_group, out_chunk, in_chunked
+    d.wpacked_wino = ptr(_dev(wpacked_wino)) if wpacked_wino is not None else None
     return d
 
 
