@@ -36,7 +36,8 @@ enum {
  * lrpx_conv_geom_packed_floats, lrpx_maxpool_rule) came WITHOUT a new version number: a caller detects them by the presence
  * of the symbols (dlsym / hasattr on the loaded library).
  * The same holds for the batched ResNet engine's entries (lrpx_conv_geom_ex, lrpx_resnet_*) and their conv mode 1 siblings
- * (lrpx_conv_geom_packed_bf16x3_bytes, lrpx_conv_geom_pack_bf16x3, lrpx_conv_geom_ex_b6).
+ * (lrpx_conv_geom_packed_bf16x3_bytes, lrpx_conv_geom_pack_bf16x3, lrpx_conv_geom_ex_b6), and for the general alpha-beta rule on
+ * that engine (lrpx_conv_geom_ab, lrpx_conv_geom_ab_b6, lrpx_resnet_coef_neg).
  * 101: the alpha-beta Conv2d rule (LRPX_PACK_*_PN*, lrpx_divide_alpha_beta, lrpx_maxpool2x2_relevance_ab); 100 before it */
 int lrpx_version(void);
 const char* lrpx_last_error_string(void);
@@ -223,6 +224,28 @@ int lrpx_conv_geom_pack_bf16x3(const float* w, int cout, int cin, int kh, int kw
 /* lrpx_conv_geom_ex with `wpacked` the bf16x3 image of the same direction: same descriptor, same refusals, same tiling and masking,
  * no atomics.  An in * q that overflows to +-inf comes out NaN here (the lower planes of inf are NaN), inf there. */
 int lrpx_conv_geom_ex_b6(const lrpx_conv_geom_ex_desc* d, void* stream);
+
+/* ---- the transposed direction of both engines with TWO coefficients: the general alpha-beta rule without bias on the batched engine
+ * (LRPtools/lrp_modules.py:124-150; ops.ResNetEncoder.relevance_alpha_beta).  For a conv with a non-negative input
+ *   R_in = x ( convT(alpha R qp, W+) + convT(-beta R qn, W-) ),   qp = f / safe(conv(x, W+)),  qn = f / safe(conv(x, W-)),
+ * f the BatchNorm fraction above the conv.  One contraction over the stacked index kappa in [0, 2 kr) against the rows [W+ ; W-]:
+ *   out[m,h,w,ci] = x[img,h,w,ci] * sum_kappa A(kappa) * w2[kappa,ci,r,s]  (+ addend[m,h,w,ci]),   img = map2img[m],
+ *   A(kappa) = (in[m,oh,ow,c] * qh[img,oh,ow,c]) * sh,  c = kappa mod kr,  (qh, sh) = (q, scale) for kappa < kr, (q2, scale2) above,
+ * formed in fp32, in that order, while the A tile is gathered (scale 1 is the operand of lrpx_conv_geom_ex bit for bit); S never
+ * exists.  alpha and beta are launch arguments: nothing per image depends on them.  Tiling, stages, sub-pixel classes, masking and the
+ * epilogue are those of lrpx_conv_geom_ex / _ex_b6; no atomics, a map's result does not depend on the other maps of the call. */
+typedef struct lrpx_conv_geom_ab_desc {
+    lrpx_conv_geom_ex_desc base; /* dir = LRPX_GEOM_BWD only; in / q have row length kr (not k); q is required; bias NULL.
+                                    k = 2 kr: wpacked is lrpx_conv_geom_pack(_bf16x3) of the (2 kr, n_oc, kh, kw) tensor [W+ ; W-].
+                                    k = kr: the W+ half alone (beta == 0): wpacked as for lrpx_conv_geom_ex, q2 NULL, scale2 0 */
+    const float* q2;             /* [n_img*oh*ow][kr], 16-byte aligned: the coefficient of the second half; required iff k = 2 kr */
+    float scale, scale2;         /* finite: alpha and -beta */
+    int kr;                      /* relevance channels (the conv's cout), a multiple of 4 */
+} lrpx_conv_geom_ab_desc;
+int lrpx_conv_geom_ab(const lrpx_conv_geom_ab_desc* d, void* stream);      /* fp32 MFMA, the arithmetic of lrpx_conv_geom_ex */
+/* exact bf16 split (split3 after both multiplications); the cross products collect in an accumulator of their own, joined to the
+ * a0 b0 sums once per output: W+ against W- cancels, and fewer roundings at the running sum's size keep the result fp32 grade */
+int lrpx_conv_geom_ab_b6(const lrpx_conv_geom_ab_desc* d, void* stream);
 
 /* ---- elementwise / layout kernels -------------------------------------------------------------- */
 /* NHWC <-> BLOCKED (csrc/blocked.h): n_groups tensors of pix_per_group pixels x c channels (c %% 16 == 0), each its own block set
@@ -726,6 +749,10 @@ int lrpx_maxpool_rule(const float* x, const float* r_out, float* r_in, long plan
  * utils.safe_divide inside lrp_backward (utils.py:16-18,28) - everything between R at the BN's output and S of the conv. */
 int lrpx_resnet_bn_act_coef(const float* yz, int ld, const float* w, const float* b, float* act, float* q, long rows, int c, int relu,
                             void* stream);
+/* The second coefficient of the general alpha-beta rule (lrpx_conv_geom_ab): yz columns [0,c) the conv's output y, [c,2c) Z- =
+ * conv(x,W-) (the stem: conv(x+,W-) + conv(x-,W+));  qn [rows][c] = safe_divide(|y w|, |y w| + |b|) / (Z- + 1e-7 [Z- == 0]), the
+ * fraction evaluated as lrpx_resnet_bn_act_coef evaluates it.  Independent of alpha / beta: once per image. */
+int lrpx_resnet_coef_neg(const float* yz, int ld, const float* w, const float* b, float* qn, long rows, int c, void* stream);
 /* out = max(x1 + x2, 0) (models/resnet.py:137-138) and the coefficients of Add.propagate_relevance (lrp_modules.py:262-275):
  * c_k = x_k / (x1 + x2 + 0.01 sign(x1 + x2)), NaN -> 0, + 0.5 where x1 + x2 == 0, so that R_k = R c_k.  (x1 == -x2 != 0, where the
  * reference's result is non-finite and its asserts fire, gives 0.5.)  n elements each. */

@@ -20,7 +20,9 @@ parameters if provided" and no argument): the VGG16 encoder with another alpha /
 `ops.Vgg16.relevance_alpha_beta`, with `ignore_bias=False` the generic driver.
 For a bottleneck ResNet under the preset `add_lrp` additionally attaches `model.compute_lrp_maps(images, targets, map2img=None, conv_mode=0)`:
 the batched engine `ops.ResNetEncoder` (one trace per image, one map per target row, no hooks, no `.grad`; conv_mode=1: its
-contractions in the exact bf16-split arithmetic).  `compute_lrp` is unchanged.
+contractions in the exact bf16-split arithmetic).  Under any other alpha / beta it attaches `model.compute_lrp_maps_ab`
+instead: the same contract with the model's alpha / beta, on `ops.ResNetEncoder.relevance_alpha_beta`.  `compute_lrp` is
+unchanged.
 Improvement over the reference: `add_lrp` is idempotent (the reference stacks hooks on every call, which
 multiplies its cost without changing the result)."""
 import torch
@@ -115,18 +117,38 @@ def add_lrp(model, lrp_params=None):
 
 
 def _attach_resnet_engine(model, params):
-    """`model.compute_lrp_maps` for a bottleneck ResNet under the preset (ops.match_bottleneck_resnet); any other model or `lrp_params`:
-    the attribute is absent.  Installs no hooks; the engine (packed weights) is built at the first call."""
-    model.__dict__.pop("compute_lrp_maps", None)
-    for key in [k for k in model.__dict__ if k.startswith("_lrpx_resnet")]:
+    """`model.compute_lrp_maps` for a bottleneck ResNet under the preset (ops.match_bottleneck_resnet), `model.compute_lrp_maps_ab`
+    under any other alpha / beta (`ignore_bias` either way: the matcher refuses convs with bias, so it cannot matter); any other model:
+    both attributes are absent.  Installs no hooks; the engine (packed weights) is built at the first call."""
+    for key in [k for k in model.__dict__ if k.startswith("_lrpx_resnet") or k in ("compute_lrp_maps", "compute_lrp_maps_ab")]:
         del model.__dict__[key]
-    if params != SequentialPresetA().lrp_params:
+    preset = SequentialPresetA().lrp_params
+    is_preset = params == preset
+    if not is_preset and (params["alpha"], params["beta"]) == (preset["alpha"], preset["beta"]):
         return
     try:
         ops.match_bottleneck_resnet(model)
     except ValueError:
         return
-    model.compute_lrp_maps = lambda images, targets, map2img=None, conv_mode=0: compute_lrp_maps(model, images, targets, map2img, conv_mode)
+    if is_preset:
+        model.compute_lrp_maps = lambda images, targets, map2img=None, conv_mode=0: compute_lrp_maps(model, images, targets, map2img, conv_mode)
+    else:
+        model.compute_lrp_maps_ab = lambda images, targets, map2img=None, conv_mode=0: compute_lrp_maps_ab(model, images, targets, map2img,
+                                                                                                         conv_mode)
+
+
+def _resnet_engine_pass(model, images, targets, map2img, conv_mode, who):
+    """trace `images` on the model's engine of `conv_mode` (built on first use) and check `targets`: (engine, targets NHWC)"""
+    key = "_lrpx_resnet" if conv_mode == 0 else "_lrpx_resnet_mode{}".format(conv_mode)
+    eng = model.__dict__.get(key)
+    if eng is None:
+        eng = ops.ResNetEncoder(model, conv_mode=conv_mode)
+        setattr(model, key, eng)
+    feats = eng.forward(images.detach())
+    hw = eng.feat_hw
+    if targets.dim() != 4 or tuple(targets.shape[1:]) != (feats.shape[2], hw[0], hw[1]):
+        raise ValueError("{}: targets must be (n_maps, {}, {}, {}), got {}".format(who, feats.shape[2], hw[0], hw[1], tuple(targets.shape)))
+    return eng, ops.nchw_to_nhwc(targets.detach().to(torch.float32))
 
 
 def compute_lrp_maps(model, images, targets, map2img=None, conv_mode=0):
@@ -138,17 +160,20 @@ def compute_lrp_maps(model, images, targets, map2img=None, conv_mode=0):
     it neither reads nor accumulates into `images.grad` - and returns the maps themselves, not a running sum.  Like `compute_lrp` it
     asserts the result is finite and not all zero (lrp_wrapper.py:81).  conv_mode: the engine's arithmetic (`ops.ResNetEncoder`: 0 fp32
     MFMA, 1 exact bf16 split); the model keeps one engine per mode, `model._lrpx_resnet` for mode 0."""
-    key = "_lrpx_resnet" if conv_mode == 0 else "_lrpx_resnet_mode{}".format(conv_mode)
-    eng = model.__dict__.get(key)
-    if eng is None:
-        eng = ops.ResNetEncoder(model, conv_mode=conv_mode)
-        setattr(model, key, eng)
-    feats = eng.forward(images.detach())
-    hw = eng.feat_hw
-    if targets.dim() != 4 or tuple(targets.shape[1:]) != (feats.shape[2], hw[0], hw[1]):
-        raise ValueError("compute_lrp_maps: targets must be (n_maps, {}, {}, {}), got {}".format(feats.shape[2], hw[0], hw[1],
-                                                                                                 tuple(targets.shape)))
-    r = eng.relevance(ops.nchw_to_nhwc(targets.detach().to(torch.float32)), map2img)
+    eng, t_nhwc = _resnet_engine_pass(model, images, targets, map2img, conv_mode, "compute_lrp_maps")
+    r = eng.relevance(t_nhwc, map2img)
+    ops.check_relevance(r, finite=True, nonzero=True)
+    return r
+
+
+def compute_lrp_maps_ab(model, images, targets, map2img=None, conv_mode=0):
+    """`compute_lrp_maps` under the alpha / beta `add_lrp(model, lrp_params=...)` left on the model: the general alpha-beta rule of
+    every Conv2d (lrp_modules.py:124-150), everything else as there; the same per-mode engines.  Each map equals what `compute_lrp`
+    (the generic driver, under the same parameters) returns on a fresh sample tensor.  A non-finite result is refused like there:
+    with beta != 0 the relevance grows by about (alpha + beta) per conv, which can leave fp32's range on a deep net."""
+    alpha, beta, _ = lrp_modules.alpha_beta_params(getattr(model, "_lrpx_params", None))
+    eng, t_nhwc = _resnet_engine_pass(model, images, targets, map2img, conv_mode, "compute_lrp_maps_ab")
+    r = eng.relevance_alpha_beta(t_nhwc, map2img, alpha, beta)
     ops.check_relevance(r, finite=True, nonzero=True)
     return r
 

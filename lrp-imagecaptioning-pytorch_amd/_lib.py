@@ -90,6 +90,11 @@ class ConvGeomExDesc(C.Structure):
                 ("kh", _i), ("kw", _i), ("sh", _i), ("sw", _i), ("ph", _i), ("pw", _i), ("k", _i), ("n_oc", _i)]
 
 
+class ConvGeomAbDesc(C.Structure):
+    """lrpx_conv_geom_ab_desc: the transposed direction with two coefficients (general alpha-beta rule)"""
+    _fields_ = [("base", ConvGeomExDesc), ("q2", _f), ("scale", C.c_float), ("scale2", C.c_float), ("kr", _i)]
+
+
 class VggOpts(C.Structure):
     """lrpx_vgg16_opts: the per-call context of the VGG16 chains (conv mode, forward switch, per-layer timing)"""
     _fields_ = [("conv_mode", _i), ("forward_f16", _i), ("layer_ms", C.POINTER(C.c_float))]
@@ -231,7 +236,10 @@ SIGNATURES = {
     "lrpx_conv_geom_packed_bf16x3_bytes": (_sz, [_i, _i, _i]),
     "lrpx_conv_geom_pack_bf16x3": (_i, [_f, _i, _i, _i, _i, _i, _f, _f]),
     "lrpx_conv_geom_ex_b6": (_i, [C.POINTER(ConvGeomExDesc), _f]),
+    "lrpx_conv_geom_ab": (_i, [C.POINTER(ConvGeomAbDesc), _f]),
+    "lrpx_conv_geom_ab_b6": (_i, [C.POINTER(ConvGeomAbDesc), _f]),
     "lrpx_resnet_bn_act_coef": (_i, [_f, _i, _f, _f, _f, _f, _l, _i, _i, _f]),
+    "lrpx_resnet_coef_neg": (_i, [_f, _i, _f, _f, _f, _l, _i, _f]),
     "lrpx_resnet_add_relu_coef": (_i, [_f, _f, _f, _f, _f, _l, _f]),
     "lrpx_resnet_maxpool_fwd": (_i, [_f, _f] + [_i] * 12 + [_f]),
     "lrpx_resnet_maxpool_rel": (_i, [_f, _f, _f, _f] + [_i] * 13 + [_f]),

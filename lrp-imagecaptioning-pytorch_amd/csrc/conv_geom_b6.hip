@@ -9,6 +9,8 @@
 //   B   split at pack time (lrpx_conv_geom_pack_bf16x3): [n_oc / 32][taps][K / 32][k-step 2][plane 3][64 lanes][8 bf16]; element j of
 //       lane l is W[k = 32 chunk + 16 ks + 8 (l >> 5) + j][column 32 ocb + (l & 31)], zero beyond K and n_oc: a fragment is one
 //       contiguous 1 KiB load
+// The general alpha-beta rule (lrpx_conv_geom_ab_b6): the dual-coefficient A gather of conv_geom_ex.hip, (R q) s in
+// fp32, THEN split3 - over the stacked rows [W+ ; W-] packed by lrpx_conv_geom_pack_bf16x3 as one tensor of 2 kr rows.
 // split3 of +-inf leaves NaN in the lower planes: an overflowing in * q gives NaN here where the fp32 kernel gives inf.
 #include "conv_geom.h"
 #include "conv_bf16x6.h"
@@ -31,6 +33,10 @@ struct Cg6Params {
     const int32_t* map2img;
     float* out;
     int n, H, W, OH, OW, kh, kw, sh, sw, ph, pw, K, n_oc, nchunk, taps;
+    // AB only: row length of in / q / q2 (K = kr or 2 kr), the second half's coefficient and the two scalars
+    int kr;
+    const float* q2;
+    float scale, scale2;
 };
 
 // one thread per element of [ocb][tap][chunk][k-step][lane][j]; it writes the element's three planes
@@ -61,7 +67,9 @@ __global__ void conv_geom_pack_bf16x3_kernel(const float* __restrict__ w, unsign
 
 // DIR = LRPX_GEOM_FWD: output pixels are the (OH, OW) map, sources the (H, W) map.
 // DIR = LRPX_GEOM_BWD: output pixels are the (H, W) map in sub-pixel classes (blockIdx.z), sources the (OH, OW) map.
-template <int DIR>
+// AB (transposed direction only) 1: the dual-coefficient gather over the W+ half alone (K = kr);  2: over both halves (K = 2 kr), with the
+// cross products in an accumulator of their own.
+template <int DIR, int AB = 0>
 __global__ __launch_bounds__(256) void conv_geom_b6_kernel(const Cg6Params p) {
     __shared__ __attribute__((aligned(16))) char a_lds[CG_TM * CG6_ROWB];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -111,9 +119,14 @@ __global__ __launch_bounds__(256) void conv_geom_b6_kernel(const Cg6Params p) {
 
     f32x4 ra[2];
     u32x4 bcur[6], bnext[6];                        // [k-step][plane]
-    f32x16 acc;
+    f32x16 acc, acc_lo;
 #pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+    for (int e = 0; e < 16; ++e) acc[e] = acc_lo[e] = 0.f;
+    // AB = 2: the five cross products (2^-8 of a term and below) collect in an accumulator of their own, joined to the a0 b0 sums once at
+    // the end.  The W+ and W- sums cancel, so the running sum is large against the result, and every MFMA that adds into it rounds at
+    // the running sum's size: two per stage then, not twelve.  Otherwise this is the one accumulator of the parent - AB = 1 sums in the
+    // parent's order, so that scale 1 gives the parent's bytes.
+    f32x16& lo = AB == 2 ? acc_lo : acc;
 #pragma unroll
     for (int g = 0; g < 6; ++g) bcur[g] = bnext[g] = u32x4{0, 0, 0, 0};
 
@@ -128,11 +141,14 @@ __global__ __launch_bounds__(256) void conv_geom_b6_kernel(const Cg6Params p) {
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
             if (pn[u] >= 0 && sy >= 0 && sy < SY && sx >= 0 && sx < SX && kc < p.K) {
                 const long pix = (long)sy * SX + sx;
-                v = *reinterpret_cast<const f32x4*>(p.in + ((long)pn[u] * SY * SX + pix) * p.K + kc);
+                const bool neg = AB && kc >= p.kr;                 // the W- half of the stacked contraction
+                const int c = neg ? kc - p.kr : kc, ld = AB ? p.kr : p.K;
+                v = *reinterpret_cast<const f32x4*>(p.in + ((long)pn[u] * SY * SX + pix) * ld + c);
                 if (DIR == LRPX_GEOM_BWD && p.q) {
-                    const f32x4 qv = *reinterpret_cast<const f32x4*>(p.q + ((long)pim[u] * SY * SX + pix) * p.K + kc);
+                    const f32x4 qv = *reinterpret_cast<const f32x4*>((neg ? p.q2 : p.q) + ((long)pim[u] * SY * SX + pix) * ld + c);
                     v = v * qv;
                 }
+                if (AB) v = v * (neg ? p.scale2 : p.scale);        // (R q) s in this order: s = 1 leaves the preset's operand
             }
             ra[u] = v;
         }
@@ -171,11 +187,11 @@ __global__ __launch_bounds__(256) void conv_geom_b6_kernel(const Cg6Params p) {
                 const bf16x8 b0 = __builtin_bit_cast(bf16x8, bcur[3 * ks]);
                 const bf16x8 b1 = __builtin_bit_cast(bf16x8, bcur[3 * ks + 1]);
                 const bf16x8 b2 = __builtin_bit_cast(bf16x8, bcur[3 * ks + 2]);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b0, acc, 0, 0, 0);      // small terms first
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b2, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc, 0, 0, 0);
+                lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b0, lo, 0, 0, 0);        // small terms first
+                lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, lo, 0, 0, 0);
+                lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b2, lo, 0, 0, 0);
+                lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, lo, 0, 0, 0);
+                lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, lo, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc, 0, 0, 0);
             }
         }
@@ -183,6 +199,7 @@ __global__ __launch_bounds__(256) void conv_geom_b6_kernel(const Cg6Params p) {
         for (int g = 0; g < 6; ++g) bcur[g] = bnext[g];
     }
 
+    if (AB == 2) acc = acc + acc_lo;
     // epilogue: accumulator register e of lane l is tile row (e & 3) + 8 (e >> 2) + 4 (l >> 5), column l & 31
     const int oc = ocb * 32 + (lane & 31);
     if (oc >= p.n_oc) return;
@@ -257,7 +274,8 @@ int lrpx_conv_geom_ex_b6(const lrpx_conv_geom_ex_desc* d, void* stream) {
     LRPX_CHECK_PTRS("lrpx_conv_geom_ex_b6", {d->in, "in"}, {d->wpacked, "wpacked"}, {d->bias, "bias"}, {d->x, "x"}, {d->q, "q"},
                     {d->addend, "addend"}, {d->map2img, "map2img"}, {d->out, "out"});
     Cg6Params p = {d->in, (const char*)d->wpacked, d->bias, d->x, d->q, d->addend, d->map2img, d->out, d->n, d->h, d->w, d->oh, d->ow,
-                   d->kh, d->kw, d->sh, d->sw, d->ph, d->pw, d->k, d->n_oc, (int)ceil_div(d->k, CG_KC), d->kh * d->kw};
+                   d->kh, d->kw, d->sh, d->sw, d->ph, d->pw, d->k, d->n_oc, (int)ceil_div(d->k, CG_KC), d->kh * d->kw,
+                   0, nullptr, 0.f, 0.f};
     const unsigned gy = (unsigned)ceil_div(d->n_oc, CG_TN);
     LRPX_REQUIRE(gy < 65536 && d->sh * d->sw < 65536, "conv_geom_ex_b6: too many output channels or stride classes");
     hipStream_t st = (hipStream_t)stream;
@@ -270,6 +288,22 @@ int lrpx_conv_geom_ex_b6(const lrpx_conv_geom_ex_desc* d, void* stream) {
                            dim3(256), 0, st, p);
     }
     return check_launch("conv_geom_ex_b6");
+}
+
+int lrpx_conv_geom_ab_b6(const lrpx_conv_geom_ab_desc* a, void* stream) {
+    LRPX_TRY(conv_geom_ab_check(a, "lrpx_conv_geom_ab_b6"));
+    const lrpx_conv_geom_ex_desc* d = &a->base;
+    Cg6Params p = {d->in, (const char*)d->wpacked, nullptr, d->x, d->q, d->addend, d->map2img, d->out, d->n, d->h, d->w, d->oh, d->ow,
+                   d->kh, d->kw, d->sh, d->sw, d->ph, d->pw, d->k, d->n_oc, (int)ceil_div(d->k, CG_KC), d->kh * d->kw,
+                   a->kr, a->q2, a->scale, a->scale2};
+    const long pc = (long)d->n * ceil_div(d->h, d->sh) * ceil_div(d->w, d->sw);      // class (0, 0) holds the most pixels
+    const dim3 grid((unsigned)ceil_div(pc, CG_TM), (unsigned)ceil_div(d->n_oc, CG_TN), (unsigned)(d->sh * d->sw));
+    if (a->q2) {
+        hipLaunchKernelGGL((conv_geom_b6_kernel<LRPX_GEOM_BWD, 2>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    } else {
+        hipLaunchKernelGGL((conv_geom_b6_kernel<LRPX_GEOM_BWD, 1>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    }
+    return check_launch("conv_geom_ab_b6");
 }
 
 }  // extern "C"

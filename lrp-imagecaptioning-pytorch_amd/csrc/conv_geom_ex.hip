@@ -6,6 +6,10 @@
 //   addend    out = x * acc + addend  (the two relevances that meet at a block's input)
 // The forward direction is the plain convolution; the trace stacks [W | W+] along the output columns to get the conv's output
 // and Z+ from one gather of the A tile.
+// The general alpha-beta rule (lrpx_conv_geom_ab) is the same transposed kernel with a DUAL-coefficient A gather:
+// the contraction runs over the stacked index kappa in [0, 2 kr) against the weight rows [W+ ; W-] (packed by lrpx_conv_geom_pack as
+// one tensor of 2 kr rows), and the operand is A(kappa) = (R[c] * qh[c]) * sh with c = kappa mod kr and (qh, sh) = (q, scale) below kr,
+// (q2, scale2) from kr on.  kr % 4 == 0, so a thread's float4 never straddles the halves, wherever the boundary falls in a chunk.
 #include "conv_geom.h"
 
 namespace lrpx {
@@ -23,11 +27,16 @@ struct CgxParams {
     const int32_t* map2img;
     float* out;
     int n, H, W, OH, OW, kh, kw, sh, sw, ph, pw, K, n_oc, nchunk, taps;
+    // AB only: row length of in / q / q2 (K = kr or 2 kr), the second half's coefficient and the two scalars
+    int kr;
+    const float* q2;
+    float scale, scale2;
 };
 
 // DIR = LRPX_GEOM_FWD: output pixels are the (OH, OW) map, sources the (H, W) map.
 // DIR = LRPX_GEOM_BWD: output pixels are the (H, W) map in sub-pixel classes (blockIdx.z), sources the (OH, OW) map.
-template <int DIR>
+// AB (transposed direction only): the dual-coefficient gather described at the top of the file.
+template <int DIR, bool AB = false>
 __global__ __launch_bounds__(256) void conv_geom_ex_kernel(const CgxParams p) {
     __shared__ __attribute__((aligned(16))) float a_lds[CG_TM * CG_LDA];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -93,11 +102,14 @@ __global__ __launch_bounds__(256) void conv_geom_ex_kernel(const CgxParams p) {
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
             if (pn[u] >= 0 && sy >= 0 && sy < SY && sx >= 0 && sx < SX && kc < p.K) {
                 const long pix = (long)sy * SX + sx;
-                v = *reinterpret_cast<const f32x4*>(p.in + ((long)pn[u] * SY * SX + pix) * p.K + kc);
+                const bool neg = AB && kc >= p.kr;                 // the W- half of the stacked contraction
+                const int c = neg ? kc - p.kr : kc, ld = AB ? p.kr : p.K;
+                v = *reinterpret_cast<const f32x4*>(p.in + ((long)pn[u] * SY * SX + pix) * ld + c);
                 if (DIR == LRPX_GEOM_BWD && p.q) {
-                    const f32x4 qv = *reinterpret_cast<const f32x4*>(p.q + ((long)pim[u] * SY * SX + pix) * p.K + kc);
+                    const f32x4 qv = *reinterpret_cast<const f32x4*>((neg ? p.q2 : p.q) + ((long)pim[u] * SY * SX + pix) * ld + c);
                     v = v * qv;
                 }
+                if (AB) v = v * (neg ? p.scale2 : p.scale);        // (R q) s in this order: s = 1 leaves the preset's operand
             }
             ra[u] = v;
         }
@@ -183,7 +195,8 @@ int lrpx_conv_geom_ex(const lrpx_conv_geom_ex_desc* d, void* stream) {
     LRPX_CHECK_PTRS("lrpx_conv_geom_ex", {d->in, "in"}, {d->wpacked, "wpacked"}, {d->bias, "bias"}, {d->x, "x"}, {d->q, "q"},
                     {d->addend, "addend"}, {d->map2img, "map2img"}, {d->out, "out"});
     CgxParams p = {d->in, d->wpacked, d->bias, d->x, d->q, d->addend, d->map2img, d->out, d->n, d->h, d->w, d->oh, d->ow,
-                   d->kh, d->kw, d->sh, d->sw, d->ph, d->pw, d->k, d->n_oc, (int)ceil_div(d->k, CG_KC), d->kh * d->kw};
+                   d->kh, d->kw, d->sh, d->sw, d->ph, d->pw, d->k, d->n_oc, (int)ceil_div(d->k, CG_KC), d->kh * d->kw,
+                   0, nullptr, 0.f, 0.f};
     const unsigned gy = (unsigned)ceil_div(d->n_oc, CG_TN);
     LRPX_REQUIRE(gy < 65536 && d->sh * d->sw < 65536, "conv_geom_ex: too many output channels or stride classes");
     hipStream_t st = (hipStream_t)stream;
@@ -196,6 +209,19 @@ int lrpx_conv_geom_ex(const lrpx_conv_geom_ex_desc* d, void* stream) {
                            dim3(256), 0, st, p);
     }
     return check_launch("conv_geom_ex");
+}
+
+int lrpx_conv_geom_ab(const lrpx_conv_geom_ab_desc* a, void* stream) {
+    LRPX_TRY(conv_geom_ab_check(a, "lrpx_conv_geom_ab"));
+    const lrpx_conv_geom_ex_desc* d = &a->base;
+    CgxParams p = {d->in, d->wpacked, nullptr, d->x, d->q, d->addend, d->map2img, d->out, d->n, d->h, d->w, d->oh, d->ow,
+                   d->kh, d->kw, d->sh, d->sw, d->ph, d->pw, d->k, d->n_oc, (int)ceil_div(d->k, CG_KC), d->kh * d->kw,
+                   a->kr, a->q2, a->scale, a->scale2};
+    const long pc = (long)d->n * ceil_div(d->h, d->sh) * ceil_div(d->w, d->sw);      // class (0, 0) holds the most pixels
+    hipLaunchKernelGGL((conv_geom_ex_kernel<LRPX_GEOM_BWD, true>),
+                       dim3((unsigned)ceil_div(pc, CG_TM), (unsigned)ceil_div(d->n_oc, CG_TN), (unsigned)(d->sh * d->sw)), dim3(256), 0,
+                       (hipStream_t)stream, p);
+    return check_launch("conv_geom_ab");
 }
 
 }  // extern "C"

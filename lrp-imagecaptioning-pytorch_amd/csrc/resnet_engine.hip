@@ -2,6 +2,8 @@
 //   trace (once per image)
 //     lrpx_resnet_bn_act_coef   eval-mode BN affine (+ ReLU) of a conv's output and the conv's relevance coefficient
 //                               q = safe_divide(|y w|, |y w| + |b|) / safe(Z+)      LRPtools/lrp_modules.py:210-215, utils.py:16-18
+//     lrpx_resnet_coef_neg      the second coefficient of the general alpha-beta rule, qn = (the same fraction) / safe(Z-), from
+//                               [y | Z-]: made at the first alpha-beta call after a forward, not by the trace      
 //     lrpx_resnet_add_relu_coef Add + ReLU and the two split coefficients of the Add rule      lrp_modules.py:262-275
 //     lrpx_resnet_maxpool_fwd   MaxPool2d of any window                                        models/resnet.py:168
 //   relevance (per map, the per-image operands through map2img)
@@ -35,6 +37,20 @@ __global__ void resnet_bn_act_coef_kernel(const float* __restrict__ yz, int ld, 
     const float den = xw + fabsf(bc);
     const float frac = xw / (den + kZEps * (den == 0.f ? 1.f : 0.f)); // safe_divide, :214
     q[i] = frac / (z + kZEps * (z == 0.f ? 1.f : 0.f));               // S = R / safe(Z), utils.py:28
+}
+
+// yz: the conv's output y in columns [0, c), Z- of the general rule in [c, 2c).  The fraction is evaluated exactly as above.
+__global__ void resnet_coef_neg_kernel(const float* __restrict__ yz, int ld, const float* __restrict__ w, const float* __restrict__ b,
+                                       float* __restrict__ qn, long rows, int c) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * c) return;
+    const long r = i / c;
+    const int ch = (int)(i - r * c);
+    const float y = yz[r * ld + ch], z = yz[r * ld + c + ch];
+    const float xw = fabsf(y * w[ch]);
+    const float den = xw + fabsf(b[ch]);
+    const float frac = xw / (den + kZEps * (den == 0.f ? 1.f : 0.f));
+    qn[i] = frac / (z + kZEps * (z == 0.f ? 1.f : 0.f));
 }
 
 __global__ void resnet_add_relu_coef_kernel(const float* __restrict__ x1, const float* __restrict__ x2, float* __restrict__ out,
@@ -162,6 +178,14 @@ int lrpx_resnet_bn_act_coef(const float* yz, int ld, const float* w, const float
     hipLaunchKernelGGL(resnet_bn_act_coef_kernel, dim3(blocks_of(rows * c)), dim3(256), 0, (hipStream_t)stream, yz, ld, w, b, act, q, rows, c,
                        relu ? 1 : 0);
     return check_launch("resnet_bn_act_coef");
+}
+
+int lrpx_resnet_coef_neg(const float* yz, int ld, const float* w, const float* b, float* qn, long rows, int c, void* stream) {
+    LRPX_REQUIRE(yz && w && b && qn, "resnet_coef_neg: null pointer");
+    LRPX_REQUIRE(rows > 0 && c > 0 && ld >= 2 * c && rows * (long)ld < (1L << 38), "resnet_coef_neg: bad sizes (rows %ld, c %d, ld %d)", rows, c, ld);
+    LRPX_CHECK_PTRS("lrpx_resnet_coef_neg", {yz, "yz"}, {w, "w"}, {b, "b"}, {qn, "qn"});
+    hipLaunchKernelGGL(resnet_coef_neg_kernel, dim3(blocks_of(rows * c)), dim3(256), 0, (hipStream_t)stream, yz, ld, w, b, qn, rows, c);
+    return check_launch("resnet_coef_neg");
 }
 
 int lrpx_resnet_add_relu_coef(const float* x1, const float* x2, float* out, float* c1, float* c2, long n, void* stream) {

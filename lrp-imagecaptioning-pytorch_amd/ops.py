@@ -756,12 +756,53 @@ def conv_geom_ex(inp, wpacked, direction, n, hw, ohw, geom, k, n_oc, bias=None, 
     return out
 
 
+def conv_geom_ab(inp, wpacked, n, hw, ohw, geom, kr, n_oc, x, q, q2=None, scale=1., scale2=0., addend=None, map2img=None, n_img=None,
+                 out=None, validate=True, b6=False):
+    """`lrpx_conv_geom_ab` (b6: `lrpx_conv_geom_ab_b6`): the transposed direction of `conv_geom_ex` with two coefficients, the general
+    alpha-beta rule of a conv without bias (include/lrpx.h).  inp (n maps, OH OW, kr) -> out (n, H W, n_oc) =
+    x[img] * (convT((inp q[img]) scale, W+) + convT((inp q2[img]) scale2, W-)) + addend; q / q2 (n_img, OH OW, kr).  wpacked: the
+    transposed pack of the rows [W+ ; W-] (2 kr of them) - or, with q2 None (beta == 0), of W+ alone: the contraction then runs over
+    kr only.  LAUNCHES counts the two under 'conv_geom_ab_dual' and 'conv_geom_ab' (b6: + '_b6')."""
+    n_img = n if n_img is None else n_img
+    if x is None or tuple(x.shape) != (n_img, hw[0] * hw[1], n_oc):
+        raise ValueError("conv_geom_ab: x must be (n_img, H W, n_oc)")
+    for name, t in (("q", q), ("q2", q2)):
+        if (t is None and name == "q") or (t is not None and tuple(t.shape) != (n_img, ohw[0] * ohw[1], kr)):
+            raise ValueError("conv_geom_ab: {} must be (n_img, OH OW, kr)".format(name))
+    if addend is not None and tuple(addend.shape) != (n, hw[0] * hw[1], n_oc):
+        raise ValueError("conv_geom_ab: addend must have the output's shape")
+    if map2img is not None and validate:
+        map2img = check_map2img(map2img, n, n_img)
+    if inp.numel() != n * ohw[0] * ohw[1] * kr:
+        raise ValueError("conv_geom_ab: the input must hold n x pixels x kr = {} x {} x {} floats".format(n, ohw[0] * ohw[1], kr))
+    if out is None:
+        out = torch.empty(n, hw[0] * hw[1], n_oc, dtype=torch.float32, device=inp.device)
+    elif out.numel() != n * hw[0] * hw[1] * n_oc:
+        raise ValueError("conv_geom_ab: the output must hold n x pixels x n_oc floats")
+    k = kr if q2 is None else 2 * kr
+    base = _lib.ConvGeomExDesc(ptr(_dev(inp)), ptr(_dev(wpacked)), None, ptr(_dev(x)), ptr(_dev(q)), ptr(_dev(addend)), ptr(_dev(map2img)),
+                               ptr(_dev(out)), _lib.GEOM_BWD, n, n_img, hw[0], hw[1], ohw[0], ohw[1], *geom, k, n_oc)
+    d = _lib.ConvGeomAbDesc(base, ptr(_dev(q2)), scale, scale2, kr)
+    name = "conv_geom_ab" + ("" if q2 is None else "_dual") + ("_b6" if b6 else "")
+    _count(name, _lib.GEOM_BWD)
+    lib = _lib.load()
+    check((lib.lrpx_conv_geom_ab_b6 if b6 else lib.lrpx_conv_geom_ab)(C.byref(d), stream_ptr()))
+    return out
+
+
 def resnet_bn_act_coef(yz, w, b, act, q, relu):
     """yz (n, pix, 2c) = [conv output | Z of its rule] -> act = BN affine (+ ReLU), q = the conv's relevance coefficient (include/lrpx.h)"""
     c = w.shape[0]
     _count("resnet_bn_act_coef")
     check(_lib.load().lrpx_resnet_bn_act_coef(ptr(_dev(yz)), yz.shape[-1], ptr(_dev(w)), ptr(_dev(b)), ptr(_dev(act)), ptr(_dev(q)),
                                               yz.numel() // yz.shape[-1], c, 1 if relu else 0, stream_ptr()))
+
+
+def resnet_coef_neg(yz, w, b, qn):
+    """yz (n, pix, 2c) = [conv output | Z- of the general rule] -> qn, the second coefficient of `conv_geom_ab` (include/lrpx.h)"""
+    _count("resnet_coef_neg")
+    check(_lib.load().lrpx_resnet_coef_neg(ptr(_dev(yz)), yz.shape[-1], ptr(_dev(w)), ptr(_dev(b)), ptr(_dev(qn)),
+                                           yz.numel() // yz.shape[-1], w.shape[0], stream_ptr()))
 
 
 def resnet_add_relu_coef(x1, x2, out, c1, c2):
@@ -918,7 +959,8 @@ class ResNetEncoder:
     identity, winner-take-all pool (lrp_wrapper.py:7-12,42-56).  DESIGN.md 5.8.
     conv_mode: the arithmetic of every contraction of the trace and of the maps - 0: fp32 MFMA (`lrpx_conv_geom_ex`); 1: the exact
     bf16 split, six plane products on the bf16 MFMA (`lrpx_conv_geom_ex_b6`).  The engine's own choice: it does not
-    follow `lrpx_set_conv_mode`.  `replica()` shares packs and mode."""
+    follow `lrpx_set_conv_mode`.  `replica()` shares packs and mode.
+    `relevance_alpha_beta` runs the general alpha-beta rule on the same trace, in either mode."""
 
     CONV_MODES = (0, 1)
 
@@ -956,11 +998,13 @@ class ResNetEncoder:
                 bwd = pack(zrow, _lib.GEOM_BWD)
                 k_in = self.c2
             self.packs.append(dict(fwd=fwd, bwd=bwd, w=w, b=b, k_in=k_in, cout=cv["cout"], geom=cv["geom"]))
+        self._ab_packs = []                           # the general rule's packs, built at its first call; replicas share the list
         torch.cuda.current_stream().synchronize()
         self._reset()
 
     def _reset(self):
         self.trace, self.shape, self._ws, self.n_img = None, None, {}, 0
+        self._serial, self._qn, self._qn_serial = 0, None, -1
 
     def replica(self):
         """Same packed weights, own trace / workspace buffers (for a second batch in flight on another stream)."""
@@ -995,12 +1039,13 @@ class ResNetEncoder:
             hw = o
         return dims, pool, hw
 
-    def trace_bytes(self, B, H, W):
-        """bytes of the trace `forward` keeps for B images of H x W pixels (activations, q per conv, c1 / c2 per Add)"""
+    def trace_bytes(self, B, H, W, alpha_beta=False):
+        """bytes of the trace `forward` keeps for B images of H x W pixels (activations, q per conv, c1 / c2 per Add); alpha_beta: plus
+        the second coefficient per conv that `relevance_alpha_beta` keeps beside it"""
         dims, pool, _ = self._layout(H, W)
         f = H * W * self.c2 + pool[1][0] * pool[1][1] * self.packs[0]["cout"]
         for i, pk in enumerate(self.packs):
-            f += 2 * dims[i][1][0] * dims[i][1][1] * pk["cout"]                    # act + q
+            f += (3 if alpha_beta else 2) * dims[i][1][0] * dims[i][1][1] * pk["cout"]    # act + q (+ qn)
         for blk in self.plan.blocks:
             o = dims[blk["conv3"]][1]
             f += 3 * o[0] * o[1] * self.packs[blk["conv3"]]["cout"]                # the block's output, c1, c2
@@ -1032,6 +1077,7 @@ class ResNetEncoder:
             self.dims, self.pool_dims, self.feat_hw = dims, pool, feat_hw
         t = self.trace
         self.n_img = B
+        self._serial += 1
         lib = _lib.load()
         check(lib.lrpx_nchw_to_nhwc_posneg(ptr(img), ptr(t["xs"]), B, self.cin, H * W, self.c2, stream_ptr()))
 
@@ -1112,6 +1158,121 @@ class ResNetEncoder:
         pk0 = self.packs[0]
         rp = ws["a"][: n_maps * t["act"][0][0].numel()].view(n_maps, *t["act"][0].shape[1:])
         resnet_maxpool_rel(t["act"][0], r, map2img, rp, n_maps, B, self.pool_dims[0], self.pool_dims[1], pk0["cout"], self.plan.pool)
+        rs = convT(0, rp, t["xs"], None, ws["b"])
+        resnet_stem_fold(rs, out, n_maps, self.cin, self.cin, self.c2, H * W)
+        return out
+
+    # ---- the general alpha-beta rule -------------------------------------------------------------------------------
+    def _ab_state(self):
+        """per conv: `fwd`, the forward pack of the columns [W | W-] (the stem on the split image: Z- = x+ W- + x- W+, row block
+        [W- | W+ | pad]) and `bwd`, the transposed pack of the stacked rows [W+ ; W-] (the stem: [W+ | W- | pad ; W- | W+ | pad]).
+        Built once per engine from the model's weights, at the first alpha-beta call."""
+        if not self._ab_packs:
+            pack = conv_geom_pack_bf16x3 if self.b6 else conv_geom_pack
+            for cv in self.plan.convs:
+                wt = cv["module"].weight.detach().to(torch.float32)
+                wpos, wneg = wt.clamp(min=0), wt.clamp(max=0)
+                if cv["nonneg"]:
+                    zneg, rows = wneg, torch.cat([wpos, wneg], 0)
+                    y = wt
+                else:
+                    pad = torch.zeros(wt.shape[0], self.c2 - 2 * self.cin, *wt.shape[2:], device=self.device)
+                    zneg = torch.cat([wneg, wpos, pad], 1)
+                    rows = torch.cat([torch.cat([wpos, wneg, pad], 1), zneg], 0)
+                    y = torch.cat([wt, wt, pad], 1)
+                self._ab_packs.append(dict(fwd=pack(torch.cat([y, zneg], 0), _lib.GEOM_FWD), bwd=pack(rows, _lib.GEOM_BWD)))
+            torch.cuda.current_stream().synchronize()
+        return self._ab_packs
+
+    def _ab_coef(self):
+        """qn per conv = BatchNorm fraction / safe(Z-), per IMAGE, from the trace's stored inputs: one stacked forward contraction
+        [y | Z-] and one streaming pass per conv at the first alpha-beta call after a `forward`, kept until the next one"""
+        if self._qn_serial == self._serial:
+            return self._qn
+        ab, t, B = self._ab_state(), self.trace, self.n_img
+        if self._qn is None or self._qn[0].shape != t["q"][0].shape:
+            self._qn = [torch.empty_like(q) for q in t["q"]]
+        inputs = {0: t["xs"]}
+        for bi, blk in enumerate(self.plan.blocks):
+            x = t["out"][bi - 1] if bi > 0 else t["pool"]
+            inputs[blk["conv1"]], inputs[blk["conv2"]], inputs[blk["conv3"]] = x, t["act"][blk["conv1"]], t["act"][blk["conv2"]]
+            if blk["downsample"] is not None:
+                inputs[blk["downsample"]] = x
+        for i, pk in enumerate(self.packs):
+            hw, ohw = self.dims[i]
+            yz = t["yz"][: B * ohw[0] * ohw[1] * 2 * pk["cout"]].view(B, ohw[0] * ohw[1], 2 * pk["cout"])
+            conv_geom_ex(inputs[i], ab[i]["fwd"], _lib.GEOM_FWD, B, hw, ohw, pk["geom"], pk["k_in"], 2 * pk["cout"], out=yz, b6=self.b6)
+            resnet_coef_neg(yz, pk["w"], pk["b"], self._qn[i])
+        self._qn_serial = self._serial
+        return self._qn
+
+    def relevance_alpha_beta(self, r_feat_nhwc, map2img=None, alpha=2., beta=1., out=None, layer_ms=None):
+        """`relevance` with the preset's Conv2d rule replaced by the general alpha-beta rule without bias, R = alpha lrp_backward(PosNetConv)
+        - beta lrp_backward(NegNetConv) (LRPtools/lrp_modules.py:124-150): same arguments, same result shape, same map2img contract, in
+        the engine's conv mode.  BatchNorm, ReLU, Add and MaxPool2d rules are those of `relevance`.  Per conv one transposed contraction
+        over the stacked rows [W+ ; W-] with the operand (R qp) alpha | (R qn) (-beta) formed while the tile is gathered
+        (`conv_geom_ab`); beta == 0 contracts over W+ alone.  alpha and beta are launch arguments: qp is the trace's q, qn is made per
+        image at the first call after a `forward` (`_ab_coef`) and kept; another (alpha, beta) on the same trace does no forward
+        work.  The dual packs come from the model's weights as they are at the first call.  alpha = 1, beta = 0 is `relevance`, bit
+        for bit.  |R| grows by about (alpha + beta) per conv where beta != 0: a deep net can leave fp32's range."""
+        alpha, beta = float(alpha), float(beta)
+        if not (alpha == alpha and beta == beta and abs(alpha) != float("inf") and abs(beta) != float("inf")):
+            raise ValueError("ResNetEncoder.relevance_alpha_beta: alpha and beta must be finite")
+        if self.trace is None:
+            raise ValueError("ResNetEncoder.relevance_alpha_beta: no trace - call forward() first")
+        B = self.n_img
+        t, dims = self.trace, self.dims
+        r = _dev(r_feat_nhwc)
+        c_feat = self.packs[self.plan.blocks[-1]["conv3"]]["cout"]
+        if r.dim() != 3 or tuple(r.shape[1:]) != (self.feat_hw[0] * self.feat_hw[1], c_feat) or r.dtype != torch.float32:
+            raise ValueError("ResNetEncoder.relevance_alpha_beta: r_feat_nhwc must be float32 (n_maps, {}, {}), got {}".format(
+                self.feat_hw[0] * self.feat_hw[1], c_feat, tuple(r.shape)))
+        n_maps = r.shape[0]
+        if n_maps == 0:
+            raise ValueError("ResNetEncoder.relevance_alpha_beta: no maps")
+        if map2img is None:
+            if n_maps != B:
+                raise ValueError("ResNetEncoder.relevance_alpha_beta: without map2img there is one map per image of the trace ({} maps, "
+                                 "{} images)".format(n_maps, B))
+        else:
+            map2img = check_map2img(map2img, n_maps, B)
+        H, W = self.shape[1], self.shape[2]
+        if out is None:
+            out = torch.empty(n_maps, self.cin, H, W, dtype=torch.float32, device=self.device)
+        elif tuple(out.shape) != (n_maps, self.cin, H, W) or not out.is_contiguous():
+            raise ValueError("ResNetEncoder.relevance_alpha_beta: out must be contiguous (n_maps, {}, {}, {})".format(self.cin, H, W))
+        r = r.contiguous()
+        dual = beta != 0.
+        qn = self._ab_coef() if dual else None
+        ab = self._ab_packs
+        ws = self._workspace(n_maps)
+
+        def convT(i, r_out, x, addend, dst):
+            pk = self.packs[i]
+            ev = _events(layer_ms)
+            hw, ohw = dims[i]
+            n_oc = x.shape[2]
+            o = dst[: n_maps * hw[0] * hw[1] * n_oc].view(n_maps, hw[0] * hw[1], n_oc)
+            conv_geom_ab(r_out, ab[i]["bwd"] if dual else pk["bwd"], n_maps, hw, ohw, pk["geom"], pk["cout"], n_oc, x, t["q"][i],
+                         q2=qn[i] if dual else None, scale=alpha, scale2=-beta if dual else 0., addend=addend, map2img=map2img, n_img=B,
+                         out=o, validate=False, b6=self.b6)
+            _events_done(ev, layer_ms, self.plan.convs[i]["name"])
+            return o
+        cur = 0
+        for bi in range(len(self.plan.blocks) - 1, -1, -1):
+            blk = self.plan.blocks[bi]
+            x = t["out"][bi - 1] if bi > 0 else t["pool"]
+            r1 = ws["r1"][: r.numel()].view(r.shape)
+            r2 = ws["r2"][: r.numel()].view(r.shape)
+            resnet_add_split(r, t["c1"][bi], t["c2"][bi], map2img, r1, r2, n_maps, B)
+            ra = convT(blk["conv3"], r1, t["act"][blk["conv2"]], None, ws["a"])
+            rb = convT(blk["conv2"], ra, t["act"][blk["conv1"]], None, ws["b"])
+            if blk["downsample"] is not None:
+                r2 = convT(blk["downsample"], r2, x, None, ws["a"])
+            r = convT(blk["conv1"], rb, x, r2, ws["r"][cur])
+            cur = 1 - cur
+        rp = ws["a"][: n_maps * t["act"][0][0].numel()].view(n_maps, *t["act"][0].shape[1:])
+        resnet_maxpool_rel(t["act"][0], r, map2img, rp, n_maps, B, self.pool_dims[0], self.pool_dims[1], self.packs[0]["cout"], self.plan.pool)
         rs = convT(0, rp, t["xs"], None, ws["b"])
         resnet_stem_fold(rs, out, n_maps, self.cin, self.cin, self.c2, H * W)
         return out

@@ -5,6 +5,7 @@ tests/golden/make_golden_resnet.py (`bottleneck_net(base=64, blocks=[3, 4, 6, 3]
     python tools/resnet_lrp_timing.py [--out profiles/resnet_lrp_timing.txt] [--batch 4] [--iters 3]
     python tools/resnet_lrp_timing.py --engine [--engine-out profiles/resnet_engine_timing.txt] [--words 5]
     python tools/resnet_lrp_timing.py --engine --conv-mode both --batch 16 [--engine-only] [--engine-out profiles/resnet_engine_b6_timing.txt]
+    python tools/resnet_lrp_timing.py --engine --alpha 2 --beta 1 [--conv-mode 0|1] [--engine-only]      (profiles/resnet_engine_ab_timing.txt)
 
 Reports the whole call, the milliseconds per leaf type (HIP events around each rule call, layout conversions and the rule's checks
 included) and every distinct launch of the runtime-geometry conv engine (csrc/conv_geom.hip) with its flop as issued -
@@ -22,7 +23,16 @@ is met; which layers hold it back is read off the per-layer table.
 in mode 0 and then compares the modes: both engines in this process, warmed, mode 0 and mode 1 ALTERNATING for --reps repetitions
 each (at least 5), HIP events around `forward` and around `relevance`; then the per-layer tables of both.  Baseline: the mode-0 engine
 of the same run.  Noise: the spread (max - min) of mode 0 over its repetitions - a difference inside it is reported as "no
-difference".  --engine-only skips the generic driver (the first report and the engine leg's comparison against it)."""
+difference".  --engine-only skips the generic driver (the first report and the engine leg's comparison against it).
+
+--alpha / --beta (with --engine) run the general alpha-beta rule instead (`ops.ResNetEncoder.relevance_alpha_beta`): in
+one process, warmed and ALTERNATING for --reps repetitions (at least 5), the alpha-beta map pass, the preset's map pass on the same
+engine and the generic driver under the same lrp_params on replicated images; then the time of a forward plus the first alpha-beta
+call (which makes qn) and the per-layer table of both map passes.  It prints medians, the spread (max - min) of the repetitions as the
+noise, and the measured ratios; no ratio is fixed.  By flop count the alpha-beta map pass is 2 x the preset's and the generic driver
+does about 4 x the preset's conv work per map.  The targets are scaled by 1e-8: with beta != 0 the relevance grows by up to
+(alpha + beta) per conv, and the generic driver refuses a non-finite result.  Writes --engine-out, by default
+profiles/resnet_engine_ab_timing.txt."""
 import argparse
 import collections
 import os
@@ -43,7 +53,13 @@ def main():
     ap.add_argument("--conv-mode", choices=["0", "1", "both"], default="0", help="--engine: the engine's arithmetic; both: compare them")
     ap.add_argument("--reps", type=int, default=5, help="--conv-mode both: alternating repetitions per mode (at least 5)")
     ap.add_argument("--engine-only", action="store_true", help="--engine: skip the generic driver's legs")
+    ap.add_argument("--alpha", type=float, default=None, help="--engine: time the general alpha-beta rule (with --beta)")
+    ap.add_argument("--beta", type=float, default=None)
     a = ap.parse_args()
+    if (a.alpha is None) != (a.beta is None) or (a.alpha is not None and not a.engine):
+        ap.error("--alpha and --beta go together, and with --engine")
+    if a.alpha is not None and a.conv_mode == "both":
+        ap.error("--alpha / --beta: one conv mode per run")
     import numpy as np
     import torch
     sys.path.insert(0, ROOT)
@@ -58,6 +74,8 @@ def main():
     lrp_wrapper.add_lrp(net)
     g = torch.Generator().manual_seed(0)
     x = torch.randn(a.batch, 3, 224, 224, generator=g).cuda()
+    if a.alpha is not None:
+        return ab_leg(a, net, x)
     if a.engine and a.engine_only:
         return engine_leg(a, net, x)
     with torch.no_grad():
@@ -269,6 +287,91 @@ def mode_leg(a, net, x, t_nhwc, map2img, eng0):
     lines.append(f"  {'all conv layers':<24} {'':<6} {'':<6} {'':<9} {'':>5} {'':>5} {tot['f0']:9.3f} {tot['f1']:9.3f} {tot['f0'] / tot['f1']:6.2f} "
                  f"{tot['r0']:8.3f} {tot['r1']:8.3f} {tot['r0'] / tot['r1']:6.2f}")
     return lines
+
+
+def ab_leg(a, net, x):
+    """the general alpha-beta rule on the engine against the preset on the same engine and against the generic driver under the same
+    parameters, alternating in this process"""
+    import torch
+    from lrp_amd import _lib, ops
+    from lrp_amd.LRPtools import lrp_wrapper
+    g = torch.Generator().manual_seed(1)
+    n_maps, reps, mode = a.batch * a.words, max(5, a.reps), int(a.conv_mode)
+    map2img = torch.arange(n_maps, dtype=torch.int32).div(a.words, rounding_mode="floor").to(torch.int32).cuda()
+    with torch.no_grad():
+        feat_shape = tuple(net(x[:1]).shape[1:])
+    targets = torch.randn((n_maps,) + feat_shape, generator=g).cuda() * 1e-8
+    x_rep = x[map2img.long()].contiguous()
+    lrp_wrapper.add_lrp(net, lrp_params={"alpha": a.alpha, "beta": a.beta})
+    eng = ops.ResNetEncoder(net, conv_mode=mode)
+    t_nhwc = ops.nchw_to_nhwc(targets)
+
+    def once(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+    legs = {"ab": lambda: eng.relevance_alpha_beta(t_nhwc, map2img, a.alpha, a.beta), "preset": lambda: eng.relevance(t_nhwc, map2img),
+            "first": lambda: (eng.forward(x), eng.relevance_alpha_beta(t_nhwc, map2img, a.alpha, a.beta))}
+    generic_note = "skipped"
+    if not a.engine_only:
+        legs["generic"] = lambda: net.compute_lrp(x_rep.clone(), target=targets)
+    eng.forward(x)
+    try:
+        for fn in legs.values():                  # warm-up: packs, qn, workspaces, every kernel loaded
+            fn()
+        generic_note = ""
+    except _lib.LrpxError as err:                 # the generic driver's finite / non-zero check
+        legs.pop("generic", None)
+        generic_note = "refused its result: " + str(err)[:60]
+    torch.cuda.synchronize()
+    r_ab = legs["ab"]()
+    finite = bool(torch.isfinite(r_ab).all())
+    ms = {k: [] for k in legs}
+    for _ in range(reps):
+        for k, fn in legs.items():
+            ms[k].append(once(fn))
+    lay_ab, lay_pre = {}, {}
+    for _ in range(a.iters):
+        eng.relevance_alpha_beta(t_nhwc, map2img, a.alpha, a.beta, layer_ms=lay_ab)
+        eng.relevance(t_nhwc, map2img, layer_ms=lay_pre)
+    med = lambda v: sorted(v)[len(v) // 2]
+    row = lambda name, v: f"  {name:<46} {med(v):10.3f} {min(v):10.3f} {max(v):10.3f} {max(v) - min(v):10.3f}"
+    lines = [f"# tools/resnet_lrp_timing.py --engine --alpha {a.alpha:g} --beta {a.beta:g} --conv-mode {mode} --batch {a.batch} --words {a.words} "
+             f"--reps {reps} --iters {a.iters}" + (" --engine-only" if a.engine_only else ""),
+             f"== bottleneck_net(base=64, blocks=[3,4,6,3]), {a.batch} images x {a.words} words = {n_maps} maps at 224 x 224, "
+             f"{torch.cuda.get_device_name(0)}, engine conv mode {mode}, alpha {a.alpha:g} beta {a.beta:g}; the alpha-beta maps are "
+             f"{'finite' if finite else 'NOT finite'}",
+             f"{reps} alternating repetitions, ms per call", f"  {'':<46} {'median':>10} {'min':>10} {'max':>10} {'spread':>10}",
+             row(f"engine, alpha-beta map pass ({n_maps} maps)", ms["ab"]), row(f"engine, preset map pass ({n_maps} maps)", ms["preset"]),
+             row("engine, forward + first alpha-beta call (qn)", ms["first"])]
+    if "generic" in ms:
+        lines.append(row(f"generic driver, {n_maps} replicated images", ms["generic"]))
+    else:
+        lines.append(f"  generic driver: {generic_note}")
+    lines += ["", f"alpha-beta map pass / preset map pass      : {med(ms['ab']) / med(ms['preset']):6.2f} x   (2 x by flop count)"]
+    if "generic" in ms:
+        lines += [f"generic driver / alpha-beta map pass       : {med(ms['generic']) / med(ms['ab']):6.2f} x",
+                  f"generic driver / (forward + first call)    : {med(ms['generic']) / med(ms['first']):6.2f} x"]
+    lines += [f"trace memory with qn                       : {eng.trace_bytes(a.batch, 224, 224, alpha_beta=True) / 2**20 / a.batch:6.1f} MiB "
+              f"per image ({eng.trace_bytes(a.batch, 224, 224) / 2**20 / a.batch:.1f} without)", "",
+              f"per layer, one HIP-event wait per layer, mean of {a.iters} passes (ms; the transposed conv of each layer)",
+              f"  {'layer':<24} {'kernel':<6} {'stride':<6} {'map':<9} {'cin':>5} {'cout':>5} {'preset':>8} {'alpha-beta':>10} {'ratio':>6}"]
+    tot = [0.0, 0.0]
+    for i, cv in enumerate(eng.plan.convs):
+        kh, kw, sh, sw, _, _ = cv["geom"]
+        hw = eng.dims[i][0]
+        p, q = lay_pre[cv["name"]] / a.iters, lay_ab[cv["name"]] / a.iters
+        tot[0] += p
+        tot[1] += q
+        lines.append(f"  {cv['name']:<24} {kh}x{kw:<4} {sh}x{sw:<4} {hw[0]}x{hw[1]:<5} {cv['cin']:5d} {cv['cout']:5d} {p:8.3f} {q:10.3f} {q / p:6.2f}")
+    lines.append(f"  {'all conv layers':<24} {'':<6} {'':<6} {'':<9} {'':>5} {'':>5} {tot[0]:8.3f} {tot[1]:10.3f} {tot[1] / tot[0]:6.2f}")
+    report = "\n".join(lines) + "\n"
+    sys.stdout.write(report)
+    with open(a.engine_out or os.path.join(ROOT, "profiles", "resnet_engine_ab_timing.txt"), "w") as f:
+        f.write(report)
 
 
 if __name__ == "__main__":
