@@ -164,7 +164,7 @@ typedef struct lrpx_conv_desc {
  * LRPtools/utils.py:21-31 `lrp_backward` and torch.matmul/sum inside `lrp_linear_eps`. */
 int lrpx_conv_mfma(const lrpx_conv_desc* d, void* stream);
 
-/* ---- the contraction engine at any conv geometry (csrc/conv_geom.hip; the ResNet encoders' 7x7 s2, 1x1, 1x1 s2, 3x3 s2) ------ */
+/* ---- the contraction engine at any conv geometry (csrc/conv_geom_kernel.h, fp32 entries in csrc/conv_geom.hip; the ResNet encoders' 7x7 s2, 1x1, 1x1 s2, 3x3 s2) ------ */
 enum { LRPX_GEOM_FWD = 0,   /* out[n,oh,ow,co] = sum in[n, oh*sh-ph+r, ow*sw-pw+s, ci] * w[co,ci,r,s] (+ bias[co]) */
        LRPX_GEOM_BWD = 1 }; /* the transposed conv autograd runs inside lrp_backward (LRPtools/utils.py:21-31), times x:
                                out[n,h,w,ci] = x[n,h,w,ci] * sum in[n,oh,ow,co] * w[co,ci,r,s] over oh*sh-ph+r = h, ow*sw-pw+s = w */
@@ -188,8 +188,8 @@ size_t lrpx_conv_geom_packed_floats(int n_oc, int k, int taps);
  * FWD: k = cin, n_oc = cout;  BWD: k = cout, n_oc = cin. */
 int lrpx_conv_geom_pack(const float* w, int cout, int cin, int kh, int kw, int dir, float* packed, void* stream);
 
-/* ---- the same engine with the operands of a BATCHED relevance pass (csrc/conv_geom_ex.hip; ops.ResNetEncoder) ----
- * Same tiling, packed weights (lrpx_conv_geom_pack) and arithmetic as lrpx_conv_geom.  FWD is the plain convolution: the trace stacks
+/* ---- the same engine with the operands of a BATCHED relevance pass (csrc/conv_geom.hip; ops.ResNetEncoder) ----
+ * The kernel, packed weights (lrpx_conv_geom_pack) and arithmetic of lrpx_conv_geom, which is this entry without q, addend and map2img.  FWD is the plain convolution: the trace stacks
  * [W | W+] along the output columns (the caller, before packing) and gets the conv's output and Z+ of its rule from ONE gather of
  * the input tile.  BWD answers for the transposed conv inside lrp_backward (LRPtools/utils.py:21-31) with the division
  * S = R / safe(Z) (utils.py:28) and the BatchNorm rule above the conv (lrp_modules.py:210-215) folded into a per-image multiplier:

@@ -84,7 +84,7 @@ class ConvGeomDesc(C.Structure):
 
 
 class ConvGeomExDesc(C.Structure):
-    """lrpx_conv_geom_ex_desc: the runtime-geometry conv engine with map2img, input multiplier and addend (csrc/conv_geom_ex.hip)"""
+    """lrpx_conv_geom_ex_desc: the runtime-geometry conv engine with map2img, input multiplier and addend (csrc/conv_geom.hip)"""
     _fields_ = [("in_", _f), ("wpacked", _f), ("bias", _f), ("x", _f), ("q", _f), ("addend", _f), ("map2img", _f), ("out", _f),
                 ("dir", _i), ("n", _i), ("n_img", _i), ("h", _i), ("w", _i), ("oh", _i), ("ow", _i),
                 ("kh", _i), ("kw", _i), ("sh", _i), ("sw", _i), ("ph", _i), ("pw", _i), ("k", _i), ("n_oc", _i)]

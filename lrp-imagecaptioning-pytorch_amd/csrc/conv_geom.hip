@@ -1,161 +1,40 @@
-// Conv2d relevance at any kernel size / stride / padding: the runtime-geometry contraction engine (conv_geom.h) and its packer.
-// Arithmetic grade of conv mode 0 and of the general alpha-beta path: fp32 operands, fp32 accumulation on
-// v_mfma_f32_32x32x2_f32, one fmaf chain per output over (tap, channel).  The signed-input / alpha / beta / bias handling
+// Conv2d relevance at any kernel size / stride / padding: the fp32 entries of the runtime-geometry contraction engine
+// (conv_geom_kernel.h) and their packer.  Arithmetic grade of conv mode 0 and of the general alpha-beta path: fp32 operands, fp32
+// accumulation on v_mfma_f32_32x32x2_f32, one fmaf chain per output over (tap, channel).  The signed-input / alpha / beta / bias handling
 // stays outside (lrpx_nchw_to_nhwc_posneg, weight stacks built by the caller, lrpx_divide_stab / lrpx_divide_alpha_beta,
-// lrpx_fold_halves): this file is a plain convolution (+ bias) and a plain transposed convolution (* x).
-#include "conv_geom.h"
+// lrpx_fold_halves): lrpx_conv_geom is a plain convolution (+ bias) and a plain transposed convolution (* x), lrpx_conv_geom_ex the same
+// with the operands of a batched relevance pass, lrpx_conv_geom_ab its transposed direction with two coefficients.
+#include "conv_geom_kernel.h"
 
 namespace lrpx {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-struct CgParams {
-    const float* in;
-    const float* wp;
-    const float* bias;
-    const float* x;
-    float* out;
-    int n, H, W, OH, OW, kh, kw, sh, sw, ph, pw, K, n_oc, nchunk, taps;
+// A   LDS row of a pixel: the chunk's 32 floats + 4 of padding (CG_LDA = 36 floats), so that 16 consecutive rows of a b128 read cover
+//     all 64 banks.
+// B   packed weights: [n_oc / 32][taps][K / CG_KC][CG_KC / 8][64 lanes][4], zero-padded in both channel axes.  Element e of lane l in
+//     k-step group g of a chunk is B[k = chunk * 32 + 8 g + 4 (l >> 5) + e][column = 32 ocb + (l & 31)]: the operand of the e-th
+//     v_mfma_f32_32x32x2_f32 of that group, so a wave's fragment is one contiguous 1 KiB float4 load.
+struct CgF32 {
+    static constexpr int CG_LDA = 36;
+    static constexpr int ROWB = CG_LDA * 4;
+    typedef f32x4 BFrag;
+    static constexpr int NB = 4;
+    static __device__ __forceinline__ void store_a(char* row, int c4, f32x4 v) { *reinterpret_cast<f32x4*>(row + c4 * 4) = v; }
+    static __device__ __forceinline__ void mma(const char* ap, const BFrag* b, f32x16& acc, f32x16&) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const f32x4 av = *reinterpret_cast<const f32x4*>(ap + 32 * g);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[e], b[g][e], acc, 0, 0, 0);
+        }
+    }
 };
 
-// wpacked[idx] from w (cout, cin, kh, kw) as nn.Conv2d stores it.  FWD: K = cin, columns = cout; BWD: K = cout, columns = cin.
-__global__ void conv_geom_pack_kernel(const float* __restrict__ w, float* __restrict__ packed, long total, int cin, int taps, int K,
-                                      int n_oc, int nchunk, int dir) {
+// one thread per element of [ocb][tap][chunk][g][lane][e]
+__global__ void conv_geom_pack_kernel(const CgPack a, float* __restrict__ packed) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total) return;
+    if (idx >= a.total) return;
     const int e = (int)(idx & 3), lane = (int)((idx >> 2) & 63), g = (int)((idx >> 8) & 3);
-    long rest = idx >> 10;
-    const int chunk = (int)(rest % nchunk);
-    rest /= nchunk;
-    const int tap = (int)(rest % taps);
-    const int ocb = (int)(rest / taps);
-    const int k = chunk * CG_KC + 8 * g + 4 * (lane >> 5) + e;
-    const int col = ocb * 32 + (lane & 31);
-    float v = 0.f;
-    if (k < K && col < n_oc) {
-        const long co = dir == LRPX_GEOM_FWD ? col : k, ci = dir == LRPX_GEOM_FWD ? k : col;
-        v = w[(co * cin + ci) * taps + tap];
-    }
-    packed[idx] = v;
-}
-
-// DIR = LRPX_GEOM_FWD: output pixels are the (OH, OW) map, sources the (H, W) map.
-// DIR = LRPX_GEOM_BWD: output pixels are the (H, W) map in sub-pixel classes (blockIdx.z), sources the (OH, OW) map.
-template <int DIR>
-__global__ __launch_bounds__(256) void conv_geom_kernel(const CgParams p) {
-    __shared__ __attribute__((aligned(16))) float a_lds[CG_TM * CG_LDA];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave & 1, wn = wave >> 1;
-
-    // the class of this workgroup: output rows ch, ch + cs_h, ..., columns cw, cw + cs_w, ...
-    const int ch = DIR == LRPX_GEOM_BWD ? (int)blockIdx.z / p.sw : 0, cw = DIR == LRPX_GEOM_BWD ? (int)blockIdx.z % p.sw : 0;
-    const int cs_h = DIR == LRPX_GEOM_BWD ? p.sh : 1, cs_w = DIR == LRPX_GEOM_BWD ? p.sw : 1;
-    const int OY = DIR == LRPX_GEOM_BWD ? p.H : p.OH, OX = DIR == LRPX_GEOM_BWD ? p.W : p.OW;     // output map
-    const int SY = DIR == LRPX_GEOM_BWD ? p.OH : p.H, SX = DIR == LRPX_GEOM_BWD ? p.OW : p.W;     // source map
-    const int Hc = ch < OY ? (OY - ch + cs_h - 1) / cs_h : 0, Wc = cw < OX ? (OX - cw + cs_w - 1) / cs_w : 0;
-    const long npix = (long)p.n * Hc * Wc;
-    const long pix0 = (long)blockIdx.x * CG_TM;
-    if (pix0 >= npix) return;                      // the grid is sized for the largest class
-
-    // the taps that reach this class: r = r0 + i * rstep < kh, s = s0 + j * sstep < kw
-    int r0 = 0, s0 = 0, nr = p.kh, ns = p.kw, yb = 0, xb = 0;
-    if (DIR == LRPX_GEOM_BWD) {
-        r0 = (ch + p.ph) % p.sh;
-        s0 = (cw + p.pw) % p.sw;
-        nr = r0 < p.kh ? (p.kh - r0 + p.sh - 1) / p.sh : 0;
-        ns = s0 < p.kw ? (p.kw - s0 + p.sw - 1) / p.sw : 0;
-        yb = (ch + p.ph) / p.sh;                   // source row of tap r0 for class row 0: oh = hi + yb - i
-        xb = (cw + p.pw) / p.sw;
-    }
-    const int nst = nr * ns * p.nchunk;            // 0: no tap reaches the class, its pixels are zeros
-
-    // staging: thread -> pixel rows (tid >> 3) and (tid >> 3) + 32 of the tile, channels 4 (tid & 7) .. + 3 of the chunk
-    const int c4 = 4 * (tid & 7);
-    int pn[2], phi[2], pwi[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const long q = pix0 + (tid >> 3) + 32 * i;
-        if (q < npix) {
-            const long img = q / ((long)Hc * Wc);
-            const int rem = (int)(q - img * Hc * Wc);
-            pn[i] = (int)img;
-            phi[i] = rem / Wc;
-            pwi[i] = rem - phi[i] * Wc;
-        } else {
-            pn[i] = -1;
-            phi[i] = pwi[i] = 0;
-        }
-    }
-    const int ocb = blockIdx.y * 2 + wn;
-    const bool active = ocb * 32 < p.n_oc;          // a wave whose 32 columns lie beyond n_oc only helps staging
-
-    f32x4 ra[2], bcur[4], bnext[4];
-    f32x16 acc;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) bcur[g] = bnext[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    auto load_stage = [&](int st, f32x4* b) {
-        const int t = st / p.nchunk, chunk = st - t * p.nchunk;
-        const int i = t / ns, j = t - i * ns;
-        const int kc = chunk * CG_KC + c4;
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int sy = DIR == LRPX_GEOM_BWD ? phi[u] + yb - i : phi[u] * p.sh - p.ph + i;
-            const int sx = DIR == LRPX_GEOM_BWD ? pwi[u] + xb - j : pwi[u] * p.sw - p.pw + j;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (pn[u] >= 0 && sy >= 0 && sy < SY && sx >= 0 && sx < SX && kc < p.K)
-                v = *reinterpret_cast<const f32x4*>(p.in + (((long)pn[u] * SY + sy) * SX + sx) * p.K + kc);
-            ra[u] = v;
-        }
-        if (active) {
-            const int r = DIR == LRPX_GEOM_BWD ? r0 + i * p.sh : i, s = DIR == LRPX_GEOM_BWD ? s0 + j * p.sw : j;
-            const float* bp = p.wp + (((long)ocb * p.taps + (r * p.kw + s)) * p.nchunk + chunk) * CG_FRAG + lane * 4;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) b[g] = *reinterpret_cast<const f32x4*>(bp + g * 256);
-        }
-    };
-
-    if (nst > 0) load_stage(0, bcur);
-    for (int st = 0; st < nst; ++st) {
-        __syncthreads();                            // the previous stage's fragments have been read
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-            *reinterpret_cast<f32x4*>(a_lds + ((tid >> 3) + 32 * u) * CG_LDA + c4) = ra[u];
-        __syncthreads();
-        if (st + 1 < nst) load_stage(st + 1, bnext);   // in flight under this stage's MFMAs
-        if (active) {
-            const float* ap = a_lds + (wm * 32 + (lane & 31)) * CG_LDA + 4 * (lane >> 5);
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 av = *reinterpret_cast<const f32x4*>(ap + 8 * g);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[e], bcur[g][e], acc, 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int g = 0; g < 4; ++g) bcur[g] = bnext[g];
-    }
-
-    // epilogue: accumulator register e of lane l is tile row (e & 3) + 8 (e >> 2) + 4 (l >> 5), column l & 31
-    const int oc = ocb * 32 + (lane & 31);
-    if (oc >= p.n_oc) return;
-    const float bias = (DIR == LRPX_GEOM_FWD && p.bias) ? p.bias[oc] : 0.f;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-        const long q = pix0 + wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-        if (q >= npix) continue;
-        const long img = q / ((long)Hc * Wc);
-        const int rem = (int)(q - img * Hc * Wc);
-        const int hi = rem / Wc, wi = rem - hi * Wc;
-        const long off = ((img * OY + (ch + hi * cs_h)) * OX + (cw + wi * cs_w)) * p.n_oc + oc;
-        if (DIR == LRPX_GEOM_FWD)
-            p.out[off] = acc[e] + bias;
-        else
-            p.out[off] = nst > 0 ? acc[e] * p.x[off] : 0.f;
-    }
+    packed[idx] = conv_geom_weight(a, idx >> 10, 8 * g + 4 * (lane >> 5) + e, lane & 31);
 }
 
 }  // namespace lrpx
@@ -166,54 +45,29 @@ extern "C" {
 
 size_t lrpx_conv_geom_packed_floats(int n_oc, int k, int taps) {
     if (n_oc <= 0 || k <= 0 || taps <= 0) return 0;
-    return conv_geom_floats(n_oc, k, taps);
+    return conv_geom_frags(n_oc, k, taps) * 1024;
 }
 
 int lrpx_conv_geom_pack(const float* w, int cout, int cin, int kh, int kw, int dir, float* packed, void* stream) {
-    LRPX_REQUIRE(w && packed, "conv_geom_pack: null pointer");
-    LRPX_REQUIRE(cout > 0 && cin > 0 && kh > 0 && kw > 0 && kh * kw <= 1024, "conv_geom_pack: bad shape (%d,%d,%d,%d)", cout, cin, kh, kw);
-    LRPX_REQUIRE(dir == LRPX_GEOM_FWD || dir == LRPX_GEOM_BWD, "conv_geom_pack: unknown direction %d", dir);
-    LRPX_CHECK_PTRS("lrpx_conv_geom_pack", {w, "w"}, {packed, "packed"});
-    const int K = dir == LRPX_GEOM_FWD ? cin : cout, n_oc = dir == LRPX_GEOM_FWD ? cout : cin, taps = kh * kw;
-    const long total = (long)conv_geom_floats(n_oc, K, taps);
-    LRPX_REQUIRE(ceil_div(total, 256) < (1L << 31), "conv_geom_pack: weight tensor too large");
-    hipLaunchKernelGGL(conv_geom_pack_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, w, packed, total,
-                       cin, taps, K, n_oc, (int)ceil_div(K, CG_KC), dir);
-    return check_launch("conv_geom_pack");
+    CgPack a;
+    LRPX_TRY(conv_geom_pack_check(w, cout, cin, kh, kw, dir, packed, "lrpx_conv_geom_pack", &a));
+    hipLaunchKernelGGL(conv_geom_pack_kernel, dim3((unsigned)ceil_div(a.total, 256)), dim3(256), 0, (hipStream_t)stream, a, packed);
+    return check_launch("lrpx_conv_geom_pack");
 }
 
+// the batched kernel without the batched operands: one map per image, no q, no addend
 int lrpx_conv_geom(const lrpx_conv_geom_desc* d, void* stream) {
-    LRPX_REQUIRE(d, "conv_geom: null descriptor");
-    LRPX_REQUIRE(d->in && d->wpacked && d->out, "conv_geom: null pointer");
-    LRPX_REQUIRE(d->dir == LRPX_GEOM_FWD || d->dir == LRPX_GEOM_BWD, "conv_geom: unknown direction %d", d->dir);
-    LRPX_REQUIRE(d->dir == LRPX_GEOM_FWD || d->x, "conv_geom: the transposed direction needs the multiplicand x");
-    LRPX_REQUIRE(d->dir == LRPX_GEOM_BWD || !d->x, "conv_geom: x belongs to the transposed direction");
-    LRPX_REQUIRE(d->dir == LRPX_GEOM_FWD || !d->bias, "conv_geom: bias belongs to the forward direction");
-    LRPX_REQUIRE(d->n > 0 && d->h > 0 && d->w > 0 && d->oh > 0 && d->ow > 0 && d->k > 0 && d->n_oc > 0, "conv_geom: bad sizes");
-    LRPX_REQUIRE(d->kh > 0 && d->kw > 0 && d->kh * d->kw <= 1024 && d->sh > 0 && d->sw > 0 && d->ph >= 0 && d->pw >= 0,
-                 "conv_geom: bad window (kernel %dx%d stride %dx%d padding %dx%d)", d->kh, d->kw, d->sh, d->sw, d->ph, d->pw);
-    LRPX_REQUIRE(d->h + 2 * d->ph >= d->kh && d->w + 2 * d->pw >= d->kw && d->oh == (d->h + 2 * d->ph - d->kh) / d->sh + 1 &&
-                     d->ow == (d->w + 2 * d->pw - d->kw) / d->sw + 1,
-                 "conv_geom: output %dx%d is not what input %dx%d gives", d->oh, d->ow, d->h, d->w);
-    LRPX_REQUIRE(d->k % 4 == 0 && ((uintptr_t)d->in & 15) == 0 && ((uintptr_t)d->wpacked & 15) == 0,
-                 "conv_geom: the contraction channels (%d) must be a multiple of 4 and in / wpacked 16-byte aligned", d->k);
-    const long pix_in = (long)d->n * d->h * d->w, pix_out = (long)d->n * d->oh * d->ow;
-    LRPX_REQUIRE(pix_in < (1L << 31) && pix_out < (1L << 31), "conv_geom: more than 2^31 pixels");
-    LRPX_CHECK_PTRS("lrpx_conv_geom", {d->in, "in"}, {d->wpacked, "wpacked"}, {d->bias, "bias"}, {d->x, "x"}, {d->out, "out"});
-    CgParams p = {d->in, d->wpacked, d->bias, d->x, d->out, d->n, d->h, d->w, d->oh, d->ow, d->kh, d->kw, d->sh, d->sw, d->ph, d->pw,
-                  d->k, d->n_oc, (int)ceil_div(d->k, CG_KC), d->kh * d->kw};
-    const unsigned gy = (unsigned)ceil_div(d->n_oc, CG_TN);
-    LRPX_REQUIRE(gy < 65536 && d->sh * d->sw < 65536, "conv_geom: too many output channels or stride classes");
-    hipStream_t st = (hipStream_t)stream;
-    if (d->dir == LRPX_GEOM_FWD) {
-        hipLaunchKernelGGL((conv_geom_kernel<LRPX_GEOM_FWD>), dim3((unsigned)ceil_div(pix_out, CG_TM), gy, 1), dim3(256), 0, st, p);
-    } else {
-        // class (0, 0) holds the most pixels
-        const long pc = (long)d->n * ceil_div(d->h, d->sh) * ceil_div(d->w, d->sw);
-        hipLaunchKernelGGL((conv_geom_kernel<LRPX_GEOM_BWD>), dim3((unsigned)ceil_div(pc, CG_TM), gy, (unsigned)(d->sh * d->sw)), dim3(256),
-                           0, st, p);
-    }
-    return check_launch("conv_geom");
+    LRPX_REQUIRE(d, "lrpx_conv_geom: null descriptor");
+    const lrpx_conv_geom_ex_desc e = {d->in, d->wpacked, d->bias, d->x, nullptr, nullptr, nullptr, d->out, d->dir, d->n, d->n, d->h, d->w,
+                                      d->oh, d->ow, d->kh, d->kw, d->sh, d->sw, d->ph, d->pw, d->k, d->n_oc};
+    return conv_geom_run<CgF32, 0>(&e, nullptr, stream, "lrpx_conv_geom");
+}
+
+int lrpx_conv_geom_ex(const lrpx_conv_geom_ex_desc* d, void* stream) { return conv_geom_run<CgF32, 0>(d, nullptr, stream, "lrpx_conv_geom_ex"); }
+
+int lrpx_conv_geom_ab(const lrpx_conv_geom_ab_desc* a, void* stream) {
+    LRPX_REQUIRE(a, "lrpx_conv_geom_ab: null descriptor");
+    return conv_geom_run<CgF32, 1>(&a->base, a, stream, "lrpx_conv_geom_ab");
 }
 
 }  // extern "C"

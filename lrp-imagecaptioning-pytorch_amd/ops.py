@@ -723,7 +723,7 @@ def check_map2img(map2img, n_maps, n_img):
 
 def conv_geom_ex(inp, wpacked, direction, n, hw, ohw, geom, k, n_oc, bias=None, x=None, q=None, addend=None, map2img=None, n_img=None,
                  out=None, validate=True, b6=False):
-    """`lrpx_conv_geom_ex` (csrc/conv_geom_ex.hip; b6: `lrpx_conv_geom_ex_b6`, csrc/conv_geom_b6.hip, the exact bf16-split arithmetic of
+    """`lrpx_conv_geom_ex` (csrc/conv_geom.hip; b6: `lrpx_conv_geom_ex_b6`, csrc/conv_geom_b6.hip, the exact bf16-split arithmetic of
     conv mode 1, with wpacked from `conv_geom_pack_bf16x3`), NHWC fp32; hw / ohw / geom as `conv_geom`.  GEOM_FWD: inp (n, H W, k) -> out
     (n, OH OW, n_oc) (+ bias).  GEOM_BWD: inp (n maps, OH OW, k) -> out (n, H W, n_oc) = x[img] * convT(inp * q[img]) + addend with
     img = map2img[m] (None: identity); x (n_img, H W, n_oc), q (n_img, OH OW, k), addend like out.  validate: check map2img on the host
