@@ -301,7 +301,9 @@ int lrpx_unpool_winner(const float* s_lo, const uint8_t* am, const int32_t* map2
 /* amax[n] = float bits of max |s[n,:]| (zeroes amax first): the per-map operand scale of the f16x3 convolution */
 int lrpx_amax_maps(const float* s, int n_maps, long per, uint32_t* amax, void* stream);
 /* running sum over the maps of one image: out[b,t] = sum_{t'<=t} in[b,t']  (the reference's
- * `sample.grad` accumulation, LRPtools/lrp_wrapper.py:64-82); per = floats per map */
+ * `sample.grad` accumulation, LRPtools/lrp_wrapper.py:64-82); per = floats per map, any positive count (float4 accesses where it is
+ * a multiple of four, as for 224 x 224 and 448 x 448 maps; element by element otherwise - the same sums).  lrpx_scatter_maps and
+ * lrpx_accumulate likewise. */
 int lrpx_cumsum_maps(const float* in, float* out, int n_img, int t_per_img, long per, void* stream);
 /* Captions of unequal length (the reference explains whatever length its beam search returns, models/gridTDmodel.py:935-937,
  * 1147-1153): `in` holds only the VALID (image, word) maps, image b's lens[b] maps starting at map offs[b]; `out` is the padded

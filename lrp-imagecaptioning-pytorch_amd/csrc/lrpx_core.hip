@@ -902,40 +902,44 @@ __global__ void divide_safe_blk_kernel(const float* __restrict__ r, const float*
     *reinterpret_cast<f32x4*>(s_blk + n * (long)(c4 >> 2) * cs + blk_off(pix, 4 * cq, cs)) = o;
 }
 
+// V = f32x4 where a map's floats are a multiple of four (every 224 x 224 / 448 x 448 map), V = float otherwise (maps of odd image sizes:
+// their rows do not start on 16-byte boundaries); the sums are the same per element either way
+template <typename V>
 __global__ void cumsum_maps_kernel(const float* __restrict__ in, float* __restrict__ out, int t_per_img, long per4,
                                    long total) {
-    long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;   // float4 units over n_img*per4
+    long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;   // V units over n_img*per4
     if (idx >= total) return;
     long b = idx / per4, i = idx - b * per4;
-    f32x4 run = {0.f, 0.f, 0.f, 0.f};
+    V run = {};
     for (int t = 0; t < t_per_img; ++t) {
         long o = (b * t_per_img + t) * per4 + i;
-        f32x4 v = reinterpret_cast<const f32x4*>(in)[o];
+        V v = reinterpret_cast<const V*>(in)[o];
         run = (t == 0) ? v : run + v;
-        reinterpret_cast<f32x4*>(out)[o] = run;
+        reinterpret_cast<V*>(out)[o] = run;
     }
 }
 
 // Variable caption lengths: `in` holds only the valid (image, word) rows, image b's len[b] rows starting at row off[b]; `out` is the
 // padded [n_img][t_per_img] layout: running sums (accumulate, lrp_wrapper.py:64-82 quirk) or copies of the valid rows, exact zeros
 // behind an image's last word.
+template <typename V>      // f32x4 / float as cumsum_maps_kernel
 __global__ void scatter_maps_kernel(const float* __restrict__ in, float* __restrict__ out, int t_per_img,
                                     const int* __restrict__ lens, const int* __restrict__ offs, long per4, long total,
                                     int accumulate) {
-    long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;   // float4 units over n_img*per4
+    long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;   // V units over n_img*per4
     if (idx >= total) return;
     long b = idx / per4, i = idx - b * per4;
     const int len = min(lens[b], t_per_img);
     const long src0 = offs[b];
-    f32x4 run = {0.f, 0.f, 0.f, 0.f};
+    V run = {};
     for (int t = 0; t < t_per_img; ++t) {
-        f32x4 o = {0.f, 0.f, 0.f, 0.f};
+        V o = {};
         if (t < len) {
-            f32x4 v = reinterpret_cast<const f32x4*>(in)[(src0 + t) * per4 + i];
+            V v = reinterpret_cast<const V*>(in)[(src0 + t) * per4 + i];
             run = (t == 0 || !accumulate) ? v : run + v;
             o = run;
         }
-        reinterpret_cast<f32x4*>(out)[(b * t_per_img + t) * per4 + i] = o;
+        reinterpret_cast<V*>(out)[(b * t_per_img + t) * per4 + i] = o;
     }
 }
 
@@ -1038,10 +1042,11 @@ __global__ void maxpool_guided_bwd_kernel(const float* __restrict__ x, const flo
     if constexpr (AMAX) amax_commit(amax, n, mabs);
 }
 
+template <typename V>      // f32x4, or float where n is no multiple of four
 __global__ void accumulate_kernel(float* __restrict__ dst, const float* __restrict__ src, long n4) {
     long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n4) return;
-    reinterpret_cast<f32x4*>(dst)[idx] += reinterpret_cast<const f32x4*>(src)[idx];
+    reinterpret_cast<V*>(dst)[idx] += reinterpret_cast<const V*>(src)[idx];
 }
 
 // out[row][c] = in[row][c] + in[row][c + half]   (x+ and x- halves of a split relevance tensor)
@@ -1388,20 +1393,32 @@ int lrpx_divide_stab(const float* r, const float* z, const int32_t* map2img, flo
 
 int lrpx_cumsum_maps(const float* in, float* out, int n_img, int t_per_img, long per, void* stream) {
     LRPX_CHECK_PTRS("lrpx_cumsum_maps", {in, "in"}, {out, "out"});
-    LRPX_REQUIRE(in && out && (per % 4 == 0) && t_per_img > 0, "cumsum_maps: bad arguments");
-    long total = (long)n_img * (per / 4);
-    hipLaunchKernelGGL(cumsum_maps_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, in, out,
-                       t_per_img, per / 4, total);
+    LRPX_REQUIRE(in && out && per > 0 && t_per_img > 0 && n_img > 0, "cumsum_maps: bad arguments");
+    if (per % 4 == 0) {
+        long total = (long)n_img * (per / 4);
+        hipLaunchKernelGGL(cumsum_maps_kernel<f32x4>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, in, out,
+                           t_per_img, per / 4, total);
+    } else {        // maps of an odd image size (3 x 45 x 51): element by element
+        long total = (long)n_img * per;
+        hipLaunchKernelGGL(cumsum_maps_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, in, out,
+                           t_per_img, per, total);
+    }
     return check_launch("cumsum_maps");
 }
 
 int lrpx_scatter_maps(const float* in, float* out, int n_img, int t_per_img, const int32_t* lens, const int32_t* offs,
                       long per, int accumulate, void* stream) {
     LRPX_CHECK_PTRS_OPT("lrpx_scatter_maps", {in, "in"}, {out, "out"}, {lens, "lens"}, {offs, "offs"});
-    LRPX_REQUIRE(in && out && lens && offs && (per % 4 == 0) && t_per_img > 0 && n_img > 0, "scatter_maps: bad arguments");
-    long total = (long)n_img * (per / 4);
-    hipLaunchKernelGGL(scatter_maps_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, in, out, t_per_img,
-                       lens, offs, per / 4, total, accumulate);
+    LRPX_REQUIRE(in && out && lens && offs && per > 0 && t_per_img > 0 && n_img > 0, "scatter_maps: bad arguments");
+    if (per % 4 == 0) {
+        long total = (long)n_img * (per / 4);
+        hipLaunchKernelGGL(scatter_maps_kernel<f32x4>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, in, out, t_per_img,
+                           lens, offs, per / 4, total, accumulate);
+    } else {
+        long total = (long)n_img * per;
+        hipLaunchKernelGGL(scatter_maps_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, in, out, t_per_img,
+                           lens, offs, per, total, accumulate);
+    }
     return check_launch("scatter_maps");
 }
 
@@ -1497,8 +1514,11 @@ int lrpx_gradcam(const float* feats, const float* grads, const int32_t* map2img,
 
 int lrpx_accumulate(float* dst, const float* src, long n, void* stream) {
     LRPX_CHECK_PTRS_OPT("lrpx_accumulate", {dst, "dst"}, {src, "src"});
-    LRPX_REQUIRE(dst && src && n > 0 && n % 4 == 0, "accumulate: bad arguments");
-    hipLaunchKernelGGL(accumulate_kernel, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, dst, src, n / 4);
+    LRPX_REQUIRE(dst && src && n > 0, "accumulate: bad arguments");
+    if (n % 4 == 0)
+        hipLaunchKernelGGL(accumulate_kernel<f32x4>, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, dst, src, n / 4);
+    else
+        hipLaunchKernelGGL(accumulate_kernel<float>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, dst, src, n);
     return check_launch("accumulate");
 }
 

@@ -37,20 +37,51 @@ def load_image(img_filepath, height, width, mean, std, device):
     return x.unsqueeze(0).contiguous().to(device)
 
 
+def resnet_encoder_keys(state):
+    """does the state dict hold a bottleneck ResNet under `img_encoder.encoder.` (key names of models/resnet.py) rather than VGG16's
+    numbered `features` layers?"""
+    return VGG_PREFIX + "conv1.weight" in state
+
+
 class GridTDEngine:
     """Device-resident gridTD model + trace/relevance pipelines.  `state` is the reference model's
-    `state_dict` (torch tensors or numpy arrays, names of models/gridTDmodel.py:111-130)."""
+    `state_dict` (torch tensors or numpy arrays, names of models/gridTDmodel.py:111-130).
 
-    def __init__(self, state, device="cuda"):
+    The encoder (models/gridTDmodel.py:23-37) is `self.cnn`: `ops.Vgg16` built from the VGG16 keys under `img_encoder.encoder.`
+    (`self.vgg` is then the same object), or `ops.ResNetEncoder` - from `encoder=`, an nn.Module on the GPU that
+    `ops.match_bottleneck_resnet` accepts, or from a state dict whose encoder keys are those of models/resnet.py
+    (`ops.bottleneck_resnet_from_state`).  `encoder_conv_mode` (0 / 1, default 1: the exact bf16 split) is the ResNet engine's
+    arithmetic, fixed here; the decoder GEMMs of such an engine are never on the fp16 split products.  Image and feature-map sizes
+    come from the images and the encoder; the decoder's own sizes C (`img_projector`) and P (`AdaAttention.W_v_proj`: 196 in the
+    reference, :127 - a stride-32 ResNet therefore runs at 448 x 448) must match them (`encode` checks).  DESIGN.md 5.11."""
+
+    ENCODER_CONV_MODES = (0, 1)
+
+    def __init__(self, state, device="cuda", encoder=None, encoder_conv_mode=1):
+        if isinstance(encoder_conv_mode, bool) or encoder_conv_mode not in self.ENCODER_CONV_MODES:
+            raise ValueError("GridTDEngine: encoder_conv_mode {!r}: the ResNet encoder engine has modes 0 (fp32 MFMA) and 1 (exact bf16 "
+                             "split)".format(encoder_conv_mode))
+        self.encoder_conv_mode = encoder_conv_mode
+        from_state = encoder is None and resnet_encoder_keys(state)
+        if encoder is not None:
+            ops.match_bottleneck_resnet(encoder)          # host logic: a net the engine does not run is refused before any device work
+        elif from_state:
+            encoder = ops.bottleneck_resnet_from_state(state, VGG_PREFIX)
         _lib.load()   # fail loudly without the HIP library
         if not torch.cuda.is_available():
             raise _lib.LrpxError("the LRP hot path needs an MI355X; there is no CPU fallback")
         dev = torch.device(device)
         self.device = dev
         sd = {k: _t(v, dev) for k, v in state.items() if not k.startswith(VGG_PREFIX)}
-        names = [k for k in state if k.startswith(VGG_PREFIX) and k.endswith(".weight")]
-        self.vgg = ops.Vgg16([_t(state[k], dev) for k in names],
-                             [_t(state[k.replace(".weight", ".bias")], dev) for k in names])
+        if encoder is not None:
+            self.vgg = None
+            self.cnn = ops.ResNetEncoder(encoder.to(dev) if from_state else encoder, conv_mode=encoder_conv_mode)
+        else:
+            names = [k for k in state if k.startswith(VGG_PREFIX) and k.endswith(".weight")]
+            self.vgg = ops.Vgg16([_t(state[k], dev) for k in names],
+                                 [_t(state[k.replace(".weight", ".bias")], dev) for k in names])
+            self.cnn = self.vgg
+        self.resnet = encoder is not None
         self.sd = sd
         self.V, self.E = sd["embedding.weight"].shape
         self.H = sd["fc.weight"].shape[1]
@@ -133,14 +164,39 @@ class GridTDEngine:
         tr["_c"] = c
         return tr
 
+    def feature_shape(self, images):
+        """(h, w, C) of the encoder's feature map for these images (host arithmetic)"""
+        if self.resnet:
+            if images.dim() != 4:
+                raise ValueError("GridTDEngine: images must be (B, 3, H, W), got {}".format(tuple(images.shape)))
+            return self.cnn.feature_shape(int(images.shape[2]), int(images.shape[3]))
+        return self.cnn.feat_hw + (512,)
+
+    def _check_sizes(self, images):
+        """the decoder is built for P pixels of C channels (`AdaAttention.W_v_proj`, `img_projector`): refuse other images here, before
+        any kernel runs.  Returns the feature map's (h, w)."""
+        h, w, c = self.feature_shape(images)
+        if h * w != self.P or c != self.C:
+            raise ValueError("GridTDEngine: {}x{} images give a {}x{} feature map = {} pixels of {} channels; the decoder is built for {} "
+                             "pixels (AdaAttention.W_v_proj) of {} channels (img_projector)".format(
+                                 int(images.shape[2]), int(images.shape[3]), h, w, h * w, c, self.P, self.C))
+        return h, w
+
+    def _refuse_resnet(self, entry, missing):
+        if self.resnet:
+            raise NotImplementedError("GridTDEngine.{}: not built for a ResNet encoder - {}".format(entry, missing))
+
+    GRADIENT_MISSING = "the gradient chain through the ResNet encoder (guided backprop / plain gradient of ops.ResNetEncoder) is missing"
+
     def encode(self, images):
-        """VGG16 forward + the image-side constants of get_hidden_parameters (gridTDmodel.py:941-950)."""
+        """Encoder forward + the image-side constants of get_hidden_parameters (gridTDmodel.py:941-950)."""
         lib = _lib.load()
         st = stream_ptr()
         B = images.shape[0]
         H, E, Cc, P = self.H, self.E, self.C, self.P
+        self._check_sizes(images)
         images = images.to(self.device, torch.float32).contiguous()
-        feats = self.vgg.forward(images)                                   # (B,P,C) NHWC view into the trace
+        feats = self.cnn.forward(images)                                   # (B,P,C) NHWC view into the trace
         enc = dict(B=B, feats=feats)
         enc["avg"] = torch.empty(B, Cc, device=self.device)
         check(lib.lrpx_mean_pixels(ptr(feats), ptr(enc["avg"]), B, P, Cc, st))
@@ -441,6 +497,7 @@ class GridTDEngine:
         of a step (decoder trace and lock-step relevance are launch-bound) are issued by one hipGraphLaunch instead
         of the Python loop.  Inputs are copied into the graph's static buffers; the returned tensors are the graph's
         static outputs (overwritten by the next call with the same shape)."""
+        self._refuse_resnet("explain_batch_graph", "the ResNet engine's trace has not been captured in a HIP graph (the recording is missing)")
         images = images.to(self.device, torch.float32)
         captions = captions.to(self.device, torch.int64)
         key = (tuple(images.shape), tuple(captions.shape), bool(accumulate), bool(predictions), self._f16())
@@ -473,6 +530,8 @@ class GridTDEngine:
         interpreter's ~9 us per launch.  Bit-identical to `explain_batch` by construction.  Like a graph's, the returned tensors are
         the recording's static outputs: overwritten by the next call of the same shape on this engine (take `replica()`s for batches
         in flight).  Captions of equal length only (`lens` makes the launch sequence data-dependent)."""
+        self._refuse_resnet("explain_batch_replay", "the recording of the ResNet engine's step (_lib.Recording has only been built and "
+                            "checked around the VGG16 chain's calls) is missing")
         src = images
         src = src.to(self.device, torch.float32)
         captions = captions.to(self.device, torch.int64)
@@ -561,6 +620,7 @@ class GridTDEngine:
         scores (B,T,T).  (No running sums here: the reference zeroes the image gradient per word, :1717.)
         gradcam=True: `ExplainGridTDGuidedGradCam` (:1796-1836) - every map times the 16x expanded Grad-CAM heat map of the
         same (guided) decoder gradient."""
+        self._refuse_resnet("explain_batch_guided", self.GRADIENT_MISSING)
         images = images.to(self.device, torch.float32).contiguous()
         captions = captions.to(self.device, torch.int64).contiguous()
         B, T = captions.shape[0], captions.shape[1] - 1
@@ -587,6 +647,7 @@ class GridTDEngine:
         """Batched `ExplainGridTDGradient.explain_caption` (models/gridTDmodel.py:1214-1539): plain
         decoder gradient + autograd gradient through the encoder -> maps (B,T,3,224,224), word scores (B,T,T).
         cam=True: `ExplainGridTDGradCam` (:1752-1771) - the per-word result is the Grad-CAM heat map (B,T,196)."""
+        self._refuse_resnet("explain_batch_gradient", self.GRADIENT_MISSING)
         images = images.to(self.device, torch.float32).contiguous()
         captions = captions.to(self.device, torch.int64).contiguous()
         B, T = captions.shape[0], captions.shape[1] - 1
@@ -619,8 +680,9 @@ class GridTDEngine:
         return cam
 
     def explain_batch(self, images, captions, lens=None, accumulate=False, return_features=False, predictions=False):
-        """Batched `explain_caption` (gridTDmodel.py:1141-1156): images (B,3,224,224), captions (B,T+1) int64.
-        Returns maps (B,T,3,224,224) and r_words (B,T,T) (row t holds t+1 valid entries).
+        """Batched `explain_caption` (gridTDmodel.py:1141-1156): images (B,3,H,W) - 224 x 224 for VGG16, what gives P feature pixels for
+        a ResNet encoder (448 x 448 at P = 196) - captions (B,T+1) int64.
+        Returns maps (B,T,3,H,W) and r_words (B,T,T) (row t holds t+1 valid entries).
         accumulate=True reproduces the running sums the reference returns (lrp_wrapper.py:64-82 quirk).
         predictions=True also computes the (B,T,V) scores the reference's explainer keeps (`self.predictions`, :1011; read
         by evaluation.py:109) and returns them as a third tensor."""
@@ -634,15 +696,15 @@ class GridTDEngine:
         if rg is not None and not rg.full:
             # unequal caption lengths (models/gridTDmodel.py:1147-1153 explains `caption_length` words): the chain runs on
             # the sum(lens) valid maps; the result goes back to the padded layout (running sums per image over ITS words)
-            maps = self.vgg.relevance(r_feat, row2img) if rg.n else r_feat.new_zeros(0, 3, 224, 224)
+            maps = self.cnn.relevance(r_feat, row2img) if rg.n else r_feat.new_zeros(0, *images.shape[1:])
             maps = ops.scatter_maps(maps, rg, accumulate=accumulate)
             if return_features:
                 r_feat = ops.scatter_maps(r_feat, rg)
         else:
-            maps = self.vgg.relevance(r_feat, row2img)
+            maps = self.cnn.relevance(r_feat, row2img)
             if accumulate:
                 maps = ops.cumsum_maps(maps, B, T)
-        out = (maps.view(B, T, 3, 224, 224), r_words.view(B, T, T))
+        out = (maps.view(B, T, *images.shape[1:]), r_words.view(B, T, T))
         if predictions:
             out = out + (tr["pred"],)
         if return_features:
@@ -651,9 +713,12 @@ class GridTDEngine:
 
     def _f16(self):
         """the decoder GEMMs on the fp16 split products?  (ops.decoder_f16: with conv modes 2 / 3 only - the engine's own `vgg.conv_mode` or the
-        process default; `force_f16` overrides per engine)"""
+        process default; `force_f16` overrides per engine).  With a ResNet encoder the mode is the engine's `encoder_conv_mode` (0 / 1):
+        never, whatever `lrpx_set_conv_mode` says."""
         if self.force_f16 is not None:
             return bool(self.force_f16)
+        if self.resnet:
+            return ops.decoder_f16(self.encoder_conv_mode)
         return ops.decoder_f16(self.vgg.conv_mode if self.vgg is not None else None)
 
     def replica(self):
@@ -661,7 +726,8 @@ class GridTDEngine:
         trace / workspace buffers, so two batches can be in flight on two HIP streams."""
         import copy
         r = copy.copy(self)
-        r.vgg = self.vgg.replica()
+        r.cnn = self.cnn.replica()
+        r.vgg = None if self.resnet else r.cnn
         r._idx_cache = {}
         for k in ("_graphs", "_replicas", "_streams", "_recordings"):     # a replica never shares another engine's streams / buffer sets
             r.__dict__.pop(k, None)
@@ -717,9 +783,16 @@ class ExplainGridTDAttention(object):
     `model` may be the reference's `GridTDModel` (any nn.Module with that `state_dict`), a `state_dict`, or None
     (then `args.weight` is loaded like :717-718).  Without `caption_encode=` the image is captioned as the reference does
     it (`beam_search(beam_size=2, max_cap_length=50)`, :935-937; `GridTDEngine.beam_search`), so the same caption is
-    explained.  Nothing is written to disk (visualisation is out of scope)."""
+    explained.  Nothing is written to disk (visualisation is out of scope).
+
+    ResNet encoders (`args.encoder` 'resnet101' / 'renset50', models/gridTDmodel.py:26-31): a `GridTDModel` hands over its
+    `model.img_encoder.encoder` (used as it is when it lives on the GPU, rebuilt from the state dict otherwise); a state dict or
+    `args.weight` with models/resnet.py key names is built by `ops.bottleneck_resnet_from_state`.  `args.height` / `args.width` size
+    the images (448 x 448 for the reference's 196 attention pixels); `args.encoder_conv_mode` (optional, default 1) is the
+    engine's.  The gradient-family subclasses refuse such a model (NotImplementedError)."""
     EPS = 0.01
     EX_TYPE = 'lrp'
+    NEEDS_ENCODER_GRADIENT = False      # the gradient family: VGG16 only
 
     def __init__(self, args, word_map, model=None):
         self.args = args
@@ -727,19 +800,35 @@ class ExplainGridTDAttention(object):
         self.vocab_size = len(word_map)
         # one device engine per weight set (explainers/engine_cache.py): evaluation.py:806-838 builds an explainer per image
         from . import engine_cache
-        key = engine_cache.fingerprint("gridtd", args.weight if model is None else model)
+        mode = getattr(args, "encoder_conv_mode", 1)
+        key = engine_cache.fingerprint("gridtd", args.weight if model is None else model, extra=() if mode == 1 else (("encoder_conv_mode", mode),))
+        cls = type(self).__name__
+
+        def refuse():
+            raise NotImplementedError("{}: not built for a ResNet encoder - {}".format(cls, GridTDEngine.GRADIENT_MISSING))
 
         def build():
+            encoder = None
             if model is None:
                 state = torch.load(args.weight, map_location="cpu")['state_dict']
             elif hasattr(model, "state_dict"):
                 state = model.state_dict()
+                enc = getattr(getattr(model, "img_encoder", None), "encoder", None)
+                if resnet_encoder_keys(state) and isinstance(enc, torch.nn.Module) and all(
+                        t.device.type == "cuda" for t in list(enc.parameters()) + list(enc.buffers())):
+                    encoder = enc                  # the model's own module (else: rebuilt from the same tensors by the engine)
             else:
                 state = model
-            return GridTDEngine(state)
+            if self.NEEDS_ENCODER_GRADIENT and resnet_encoder_keys(state):
+                refuse()                           # before anything is uploaded
+            return GridTDEngine(state, encoder=encoder, encoder_conv_mode=mode)
         self.model = model
         # the weights are shared, the trace / workspace buffers are this explainer's own: two live explainers never see each other's image
-        self.engine = engine_cache.get(key, build, hold=engine_cache.source_tensors(model)).replica()
+        # (the state dict of a model holds its encoder's tensors too: key and `hold` cover the module as they cover the state)
+        engine = engine_cache.get(key, build, hold=engine_cache.source_tensors(model))
+        if self.NEEDS_ENCODER_GRADIENT and engine.resnet:
+            refuse()
+        self.engine = engine.replica()
         self.mean = list(IMAGENET_MEAN)
         self.std = list(IMAGENET_STD)
         self.rev_word_map = {v: k for k, v in word_map.items()}
@@ -750,7 +839,7 @@ class ExplainGridTDAttention(object):
                           self.engine.device)
 
     def get_hidden_parameters(self, img, caption_encode=None, max_cap_length=50):
-        """Forward trace (:933-1012).  `img`: file path or a (1,3,224,224) tensor."""
+        """Forward trace (:933-1012).  `img`: file path or a (1,3,H,W) tensor of the encoder's image size (224 x 224 for VGG16)."""
         self.img = self.preprocess_img(img) if isinstance(img, str) else img.to(self.engine.device, torch.float32)
         eng = self.engine
         # a caption that is handed over goes to the device BEFORE the encoder is enqueued: the copy of a pageable host list waits for the
@@ -773,7 +862,7 @@ class ExplainGridTDAttention(object):
         cap = cap_dev if cap_dev is not None else torch.tensor([self.beam_caption_encode], dtype=torch.int64, device=eng.device)
         self._cap_dev = cap
         self._tr = eng.trace(self._enc, cap, predictions=True)
-        self.image_features = ops.nhwc_to_nchw(self._enc["feats"].contiguous(), eng.C, 14, 14)
+        self.image_features = ops.nhwc_to_nchw(self._enc["feats"].contiguous(), eng.C, *eng.cnn.feat_hw)
         self.num_pixels = eng.P
         self.predictions = self._tr["pred"][0]
         self.alphas = self._tr["alpha"][0]
@@ -789,14 +878,14 @@ class ExplainGridTDAttention(object):
         """(:1014-1135) -> (r_img_feature (1,C,h,w), r_words (t+1,))"""
         assert t < self.caption_length
         r_feat, r_words, _ = self._relevance()
-        r = ops.nhwc_to_nchw(r_feat[t:t + 1].contiguous(), self.engine.C, 14, 14)
+        r = ops.nhwc_to_nchw(r_feat[t:t + 1].contiguous(), self.engine.C, *self.engine.cnn.feat_hw)
         return r, r_words[t, :t + 1].clone()
 
     def explain_cnn(self, r_img_feature):
         """(:1137-1139) — `compute_lrp` on `self.img`; like the reference the result accumulates over calls on
         the same image (`sample.grad`, lrp_wrapper.py:64-82)."""
         t_nhwc = ops.nchw_to_nhwc(r_img_feature.to(torch.float32))
-        r = self.engine.vgg.relevance(t_nhwc, torch.zeros(r_img_feature.shape[0], dtype=torch.int32,
+        r = self.engine.cnn.relevance(t_nhwc, torch.zeros(r_img_feature.shape[0], dtype=torch.int32,
                                                           device=self.engine.device))
         if getattr(self, "_img_grad", None) is None:
             self._img_grad = r
@@ -813,7 +902,7 @@ class ExplainGridTDAttention(object):
             return [], []
         self._img_grad = None
         r_feat, r_words, row2img = self._relevance()
-        maps = self.engine.vgg.relevance(r_feat, row2img)
+        maps = self.engine.cnn.relevance(r_feat, row2img)
         maps = ops.cumsum_maps(maps, 1, self.caption_length)
         ops.check_relevance(maps, finite=True, nonzero=True)
         relevance_imgs = [maps[t:t + 1] for t in range(self.caption_length)]
@@ -841,6 +930,7 @@ class ExplainiGridTDGuidedGradient(ExplainGridTDAttention):
     the reference's): guided backprop instead of LRP, same `explain_caption` surface."""
     EX_TYPE = 'GuidedBackpropagate'
     TF_MODEL_BIAS = True
+    NEEDS_ENCODER_GRADIENT = True
 
     def get_hidden_parameters(self, img, caption_encode=None, max_cap_length=50):
         super().get_hidden_parameters(img, caption_encode, max_cap_length)

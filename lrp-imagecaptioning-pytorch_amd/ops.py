@@ -431,6 +431,7 @@ class Vgg16:
     # (log-normal rows, tests/test_gpu_vgg.py::test_chain_hostile_weights_all_modes): 64 keeps a 4x margin to the contract where the
     # model above would allow ~21 in the worst case and the data allow ~2^13.  Conv mode 1 (the default) has no such rule: exact splits.
     GRAD_SPREAD_MAX = 64.0
+    feat_hw = (14, 14)              # the feature map of the 224 x 224 images this context is built for (ResNetEncoder.feat_hw: per trace)
 
     def _opts(self, layer_ms=None, grad=False):
         o = _lib.VggOpts()
@@ -950,6 +951,133 @@ def match_bottleneck_resnet(model):
     return ResNetPlan(convs, blocks, pk + ps + pp)
 
 
+def bottleneck_resnet_from_state(sd, prefix=""):
+    """A bottleneck ResNet module from a checkpoint's tensors alone: the keys of models/resnet.py (ResNet + Bottleneck, :93-236) under
+    `prefix` - conv1.weight, bn1.{weight, bias, running_mean, running_var}, layerN.M.conv1..3.weight, layerN.M.bn1..3.*,
+    layerN.M.downsample.0.weight / .downsample.1.* - as torch tensors or numpy arrays.  Widths and block counts are read from the
+    tensor shapes; what a state dict does not hold is that file's: the stem conv has stride 2 and padding (k - 1) / 2 (:164), the pool
+    is MaxPool2d(3, 2, 1) (:168), a block's middle conv has padding (k - 1) / 2, and the first block of layer2 and later has stride 2
+    on its middle conv and its shortcut (:111, :205 - the ResNet V1.5 placement).  The class's unused `fc.*` head (:177) and the
+    BatchNorms' `num_batches_tracked` are ignored; any other key under the prefix, a missing tensor or a shape that does not fit
+    raises ValueError naming the key.  The result is in eval mode, on the CPU, with an explicit `add` member per block:
+    `match_bottleneck_resnet` accepts it, `.to(device)` makes it a `ResNetEncoder`'s module.  Host logic: no device."""
+    import re
+    import numpy as np
+    import torch.nn as nn
+
+    def fail(key, msg):
+        raise ValueError("bottleneck_resnet_from_state: {!r}: {}".format(prefix + key, msg))
+    own = {}
+    for k, v in sd.items():
+        if not k.startswith(prefix):
+            continue
+        k = k[len(prefix):]
+        if k.startswith("fc.") or k.endswith("num_batches_tracked"):
+            continue
+        v = torch.from_numpy(np.asarray(v)) if not torch.is_tensor(v) else v
+        own[k] = v.detach().to(device="cpu", dtype=torch.float32).clone()
+    used = set()
+
+    def take(key, shape=None, dim=None):
+        if key not in own:
+            fail(key, "missing")
+        t = own[key]
+        if dim is not None and t.dim() != dim:
+            fail(key, "expected a {}-d tensor, got shape {}".format(dim, tuple(t.shape)))
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            fail(key, "expected shape {}, got {}".format(tuple(shape), tuple(t.shape)))
+        used.add(key)
+        return t
+
+    def conv(name, cin, stride, cout=None, k=None):
+        w = take(name + ".weight", dim=4)
+        if w.shape[1] != cin or (cout is not None and w.shape[0] != cout) or w.shape[2] != w.shape[3] or w.shape[2] % 2 == 0 or \
+                (k is not None and w.shape[2] != k):
+            fail(name + ".weight", "shape {} does not fit ({} input channels{}{}, a square odd kernel)".format(
+                tuple(w.shape), cin, "" if cout is None else ", {} output channels".format(cout), "" if k is None else ", {0}x{0}".format(k)))
+        m = nn.Conv2d(cin, w.shape[0], w.shape[2], stride=stride, padding=(w.shape[2] - 1) // 2, bias=False)
+        m.weight.data = w
+        return m
+
+    def bn(name, c):
+        m = nn.BatchNorm2d(c)
+        m.weight.data, m.bias.data = take(name + ".weight", (c,)), take(name + ".bias", (c,))
+        m.running_mean, m.running_var = take(name + ".running_mean", (c,)), take(name + ".running_var", (c,))
+        return m
+
+    class Add(nn.Module):                  # the explicit residual sum (models/resnet.py:32-37)
+        def forward(self, x, y):
+            return x + y
+
+    class Bottleneck(nn.Module):
+        def __init__(self, name, cin, stride):
+            super().__init__()
+            self.conv1 = conv(name + ".conv1", cin, 1, k=1)
+            width = self.conv1.out_channels
+            self.bn1 = bn(name + ".bn1", width)
+            self.conv2 = conv(name + ".conv2", width, stride, cout=width)
+            self.bn2 = bn(name + ".bn2", width)
+            self.conv3 = conv(name + ".conv3", width, 1, k=1)
+            cout = self.conv3.out_channels
+            self.bn3 = bn(name + ".bn3", cout)
+            self.relu = nn.ReLU(inplace=True)
+            self.downsample = None
+            if name + ".downsample.0.weight" in own:
+                self.downsample = nn.Sequential(conv(name + ".downsample.0", cin, stride, cout=cout, k=1), bn(name + ".downsample.1", cout))
+            elif stride != 1 or cin != cout:
+                fail(name + ".downsample.0.weight", "missing (the block changes {} channels into {} with stride {})".format(cin, cout, stride))
+            self.add = Add()
+
+        def forward(self, x):
+            out = self.relu(self.bn1(self.conv1(x)))
+            out = self.relu(self.bn2(self.conv2(out)))
+            out = self.bn3(self.conv3(out))
+            identity = x if self.downsample is None else self.downsample(x)
+            return self.relu(self.add(out, identity))
+
+    class BottleneckResNet(nn.Module):
+        def __init__(self):
+            super().__init__()
+            if "conv1.weight" not in own:
+                fail("conv1.weight", "missing")
+            self.conv1 = conv("conv1", own["conv1.weight"].shape[1] if own["conv1.weight"].dim() == 4 else 0, 2)
+            self.bn1 = bn("bn1", self.conv1.out_channels)
+            self.relu = nn.ReLU(inplace=True)
+            self.maxpool = nn.MaxPool2d(kernel_size=3, stride=2, padding=1)
+            counts = {}
+            for k in own:
+                m = re.match(r"layer(\d+)\.(\d+)\.", k)
+                if m:
+                    counts.setdefault(int(m.group(1)), set()).add(int(m.group(2)))
+            if not counts:
+                fail("layer1.0.conv1.weight", "missing (no layerN.M.* keys)")
+            cin = self.conv1.out_channels
+            self.layer_names = []
+            for n in range(1, max(counts) + 1):
+                if n not in counts or sorted(counts[n]) != list(range(len(counts[n]))):
+                    fail("layer{}.{}.conv1.weight".format(n, 0 if n not in counts else min(set(range(len(counts[n]) + 1)) - counts[n])),
+                         "missing (layers and blocks are numbered without gaps)")
+                blocks = []
+                for b in range(len(counts[n])):
+                    blocks.append(Bottleneck("layer{}.{}".format(n, b), cin, 2 if (b == 0 and n > 1) else 1))
+                    cin = blocks[-1].conv3.out_channels
+                setattr(self, "layer{}".format(n), nn.Sequential(*blocks))
+                self.layer_names.append("layer{}".format(n))
+            self.feat_dim = cin
+
+        def forward(self, x):
+            x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
+            for n in self.layer_names:
+                x = getattr(self, n)(x)
+            return x
+
+    net = BottleneckResNet()
+    for k in own:
+        if k not in used:
+            fail(k, "not a key of a bottleneck ResNet (conv1, bn1, layerN.M.conv1..3 / bn1..3 / downsample.0 / downsample.1)")
+    return net.eval()
+
+
 class ResNetEncoder:
     """The reference's bottleneck ResNet encoders (models/resnet.py resnet50 / resnet101, any `layers`) as a device-resident, batched LRP
     engine in the pattern of `Vgg16`: `forward` traces B images once - activations and, per conv, the relevance coefficient q that folds
@@ -1038,6 +1166,10 @@ class ResNetEncoder:
                 raise ValueError("ResNetEncoder: {}: the residual branch gives {}x{}, the shortcut {}x{}".format(blk["name"], *o, *short))
             hw = o
         return dims, pool, hw
+
+    def feature_shape(self, H, W):
+        """(h, w, C) of the feature map of an H x W image (host arithmetic; ValueError where a window does not fit)"""
+        return tuple(self._layout(H, W)[2]) + (self.packs[self.plan.blocks[-1]["conv3"]]["cout"],)
 
     def trace_bytes(self, B, H, W, alpha_beta=False):
         """bytes of the trace `forward` keeps for B images of H x W pixels (activations, q per conv, c1 / c2 per Add); alpha_beta: plus

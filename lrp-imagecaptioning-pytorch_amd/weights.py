@@ -80,6 +80,18 @@ def make_gridtd_state(seed=0, vocab_size=9586, embed_dim=512, hidden_dim=512, fe
     """state_dict (numpy float32) for the reference `GridTDModel` (models/gridTDmodel.py:111-130)."""
     rs = np.random.RandomState(seed)
     sd = _vgg_state(rs, "img_encoder.encoder.", vgg_bias_std)
+    return _gridtd_decoder_state(rs, sd, vocab_size, embed_dim, hidden_dim, feat_dim, num_pixels)
+
+
+def make_gridtd_resnet_state(seed=0, vocab_size=9586, embed_dim=512, hidden_dim=512, feat_dim=2048, num_pixels=196):
+    """The decoder part of `make_gridtd_state` for a ResNet encoder of `feat_dim` channels and a feature map of `num_pixels` pixels
+    (resnet50 / resnet101: 2048 channels, 14 x 14 at 448 x 448; models/gridTDmodel.py:26-31,127): no `img_encoder.encoder.` keys - the
+    encoder comes as a module (`GridTDEngine(state, encoder=...)`) or its keys are added by the caller.  The draws start at the seed:
+    they are not the tail of `make_gridtd_state`'s stream."""
+    return _gridtd_decoder_state(np.random.RandomState(seed), OrderedDict(), vocab_size, embed_dim, hidden_dim, feat_dim, num_pixels)
+
+
+def _gridtd_decoder_state(rs, sd, vocab_size, embed_dim, hidden_dim, feat_dim, num_pixels):
     b = 1.0 / math.sqrt(feat_dim)
     sd["img_projector.weight"] = _uniform(rs, (hidden_dim, feat_dim, 1, 1), b)
     sd["img_projector.bias"] = _uniform(rs, (hidden_dim,), b)
