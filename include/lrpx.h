@@ -37,7 +37,8 @@ enum {
  * of the symbols (dlsym / hasattr on the loaded library).
  * The same holds for the batched ResNet engine's entries (lrpx_conv_geom_ex, lrpx_resnet_*) and their conv mode 1 siblings
  * (lrpx_conv_geom_packed_bf16x3_bytes, lrpx_conv_geom_pack_bf16x3, lrpx_conv_geom_ex_b6), and for the general alpha-beta rule on
- * that engine (lrpx_conv_geom_ab, lrpx_conv_geom_ab_b6, lrpx_resnet_coef_neg).
+ * that engine (lrpx_conv_geom_ab, lrpx_conv_geom_ab_b6, lrpx_resnet_coef_neg), and for its gradient chain (lrpx_conv_geom_grad,
+ * lrpx_conv_geom_grad_b6, lrpx_resnet_relu_grad, lrpx_resnet_maxpool_grad).
  * 101: the alpha-beta Conv2d rule (LRPX_PACK_*_PN*, lrpx_divide_alpha_beta, lrpx_maxpool2x2_relevance_ab); 100 before it */
 int lrpx_version(void);
 const char* lrpx_last_error_string(void);
@@ -246,6 +247,26 @@ int lrpx_conv_geom_ab(const lrpx_conv_geom_ab_desc* d, void* stream);      /* fp
 /* exact bf16 split (split3 after both multiplications); the cross products collect in an accumulator of their own, joined to the
  * a0 b0 sums once per output: W+ against W- cancels, and fewer roundings at the running sum's size keep the result fp32 grade */
 int lrpx_conv_geom_ab_b6(const lrpx_conv_geom_ab_desc* d, void* stream);
+
+/* ---- the transposed direction of both engines for the GRADIENT chain through conv -> BatchNorm (eval) -> ReLU
+ * (ops.ResNetEncoder.gradient / guided_backprop): plain autograd (ExplainGridTDGradient.explain_cnn,
+ * models/gridTDmodel.py:1510-1521) and guided backprop (:1677-1691).  wpacked is the transposed pack of the RAW weights W (K = cout):
+ *   out[m,h,w,ci] = sum A[m,oh,ow,co] * w[co,ci,r,s]  (+ addend[m,h,w,ci]),   img = map2img[m],
+ *   A = scale[co] * (mask[img,oh,ow,co] > 0 ? (clamp ? max(in, 0) : in) : 0)
+ * formed in fp32 in the order clamp, mask, scale while the A tile is gathered (the b6 entry splits afterwards).  mask is the ReLU's
+ * OUTPUT (or input: only its sign is read; NaN passes), scale the BatchNorm factor gamma / sqrt(var + eps).  There is no multiplicand:
+ * x is never read, and a stride class no tap reaches is addend or 0.  No divisions.  Tiling, stages, sub-pixel classes and zero
+ * pattern are those of lrpx_conv_geom_ex / _ex_b6: with mask all positive, scale NULL and clamp 0 the result is lrpx_conv_geom_ex's with
+ * q = 1 and x = 1, byte for byte.  Detected by the presence of the symbols, like the other ResNet entries. */
+typedef struct lrpx_conv_geom_grad_desc {
+    lrpx_conv_geom_ex_desc base; /* dir = LRPX_GEOM_BWD only; x, q, bias NULL; in (n maps, OH OW, k) -> out (n, H W, n_oc);
+                                    addend, map2img, n_img as lrpx_conv_geom_ex */
+    const float* mask;           /* (n_img, OH OW, k) or NULL; 16-byte aligned */
+    const float* scale;          /* (k) or NULL; 16-byte aligned */
+    int clamp;                   /* 0 / 1 */
+} lrpx_conv_geom_grad_desc;
+int lrpx_conv_geom_grad(const lrpx_conv_geom_grad_desc* d, void* stream);     /* fp32 MFMA */
+int lrpx_conv_geom_grad_b6(const lrpx_conv_geom_grad_desc* d, void* stream);  /* exact bf16 split; wpacked from lrpx_conv_geom_pack_bf16x3 */
 
 /* ---- elementwise / layout kernels -------------------------------------------------------------- */
 /* NHWC <-> BLOCKED (csrc/blocked.h): n_groups tensors of pix_per_group pixels x c channels (c %% 16 == 0), each its own block set
@@ -777,6 +798,16 @@ int lrpx_resnet_add_split(const float* r, const float* c1, const float* c2, cons
  * holds the two terms in columns [0,cin) and [half, half+cin), half + cin <= ld (the layout of lrpx_nchw_to_nhwc_posneg: half = cin);
  * out [n_maps][cin][pix] (NCHW) = their sum. */
 int lrpx_resnet_stem_fold(const float* r_split, float* out, int n_maps, int cin, int half, int ld, long pix, void* stream);
+/* Gradient chain, per map, per-image operands through map2img as above.
+ * ReLU backward at a block's output: out = (clamp ? max(g, 0) : g) * (act[img] > 0); g / out [n_maps][per_map], act [n_img][per_map]
+ * the ReLU's output.  clamp 1 is guided backprop at this ReLU.  out may be g. */
+int lrpx_resnet_relu_grad(const float* g, const float* act, const int32_t* map2img, float* out, int n_maps, int n_img, long per_map,
+                          int clamp, void* stream);
+/* nn.MaxPool2d backward in NHWC: x [n_img][h*w][c] the pool's input, g_out [n_maps][oh*ow][c] -> g_in [n_maps][h*w][c]: each window's
+ * gradient goes to its first maximum (kernel rows outer, a NaN wins) - the gather and winner logic of lrpx_resnet_maxpool_rel without
+ * the division and without the x factor; windows added in ascending (oh, ow) order, no atomics, no workspace. */
+int lrpx_resnet_maxpool_grad(const float* x, const float* g_out, const int32_t* map2img, float* g_in, int n_maps, int n_img, int h, int w,
+                             int oh, int ow, int c, int kh, int kw, int sh, int sw, int ph, int pw, void* stream);
 /* max |a - b| into one device float (Dropout.propagate_relevance's check, LRPtools/lrp_modules.py:251; NaN counts as inf) */
 int lrpx_max_abs_diff(const float* a, const float* b, long n, float* out_dev, void* stream);
 

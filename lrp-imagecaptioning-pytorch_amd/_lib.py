@@ -95,6 +95,11 @@ class ConvGeomAbDesc(C.Structure):
     _fields_ = [("base", ConvGeomExDesc), ("q2", _f), ("scale", C.c_float), ("scale2", C.c_float), ("kr", _i)]
 
 
+class ConvGeomGradDesc(C.Structure):
+    """lrpx_conv_geom_grad_desc: the transposed direction of the gradient chain (raw weights; clamp, mask, scale in the gather)"""
+    _fields_ = [("base", ConvGeomExDesc), ("mask", _f), ("scale", _f), ("clamp", _i)]
+
+
 class VggOpts(C.Structure):
     """lrpx_vgg16_opts: the per-call context of the VGG16 chains (conv mode, forward switch, per-layer timing)"""
     _fields_ = [("conv_mode", _i), ("forward_f16", _i), ("layer_ms", C.POINTER(C.c_float))]
@@ -238,6 +243,10 @@ SIGNATURES = {
     "lrpx_conv_geom_ex_b6": (_i, [C.POINTER(ConvGeomExDesc), _f]),
     "lrpx_conv_geom_ab": (_i, [C.POINTER(ConvGeomAbDesc), _f]),
     "lrpx_conv_geom_ab_b6": (_i, [C.POINTER(ConvGeomAbDesc), _f]),
+    "lrpx_conv_geom_grad": (_i, [C.POINTER(ConvGeomGradDesc), _f]),
+    "lrpx_conv_geom_grad_b6": (_i, [C.POINTER(ConvGeomGradDesc), _f]),
+    "lrpx_resnet_relu_grad": (_i, [_f, _f, _f, _f, _i, _i, _l, _i, _f]),
+    "lrpx_resnet_maxpool_grad": (_i, [_f, _f, _f, _f] + [_i] * 13 + [_f]),
     "lrpx_resnet_bn_act_coef": (_i, [_f, _i, _f, _f, _f, _f, _l, _i, _i, _f]),
     "lrpx_resnet_coef_neg": (_i, [_f, _i, _f, _f, _f, _l, _i, _f]),
     "lrpx_resnet_add_relu_coef": (_i, [_f, _f, _f, _f, _f, _l, _f]),

@@ -72,14 +72,27 @@ inline int conv_geom_ab_check(const lrpx_conv_geom_ab_desc* a, const char* fn) {
     return LRPX_OK;
 }
 
-// The refusals shared by lrpx_conv_geom, _ex, _ex_b6, _ab and _ab_b6 (the last two: d = &ab->base).  `fn` names the entry in the message
+// What the gradient entries (lrpx_conv_geom_grad, lrpx_conv_geom_grad_b6) add to conv_geom_check: the transposed direction alone, no
+// multiplicand, coefficient or bias, and the refusals of mask / scale / clamp.
+inline int conv_geom_grad_check(const lrpx_conv_geom_grad_desc* g, const char* fn) {
+    const lrpx_conv_geom_ex_desc* d = &g->base;
+    LRPX_REQUIRE(d->dir == LRPX_GEOM_BWD, "%s: the transposed direction only (dir %d): the gradient of a conv's input", fn, d->dir);
+    LRPX_REQUIRE(!d->x && !d->q && !d->bias, "%s: x, q and bias must be null: the gradient has no multiplicand, coefficient or bias", fn);
+    LRPX_REQUIRE(((uintptr_t)g->mask & 15) == 0 && ((uintptr_t)g->scale & 15) == 0, "%s: mask and scale must be 16-byte aligned", fn);
+    LRPX_REQUIRE(g->clamp == 0 || g->clamp == 1, "%s: clamp is 0 or 1 (%d)", fn, g->clamp);
+    return LRPX_OK;
+}
+
+// The refusals shared by lrpx_conv_geom, _ex, _ex_b6, _ab, _ab_b6, _grad and _grad_b6 (d = &ab->base, d = &gr->base).  `fn` names the entry in the message
 // and in the pointer check, which comes last: it asks the runtime.
-inline int conv_geom_check(const lrpx_conv_geom_ex_desc* d, const char* fn, const lrpx_conv_geom_ab_desc* ab = nullptr) {
+inline int conv_geom_check(const lrpx_conv_geom_ex_desc* d, const char* fn, const lrpx_conv_geom_ab_desc* ab = nullptr,
+                           const lrpx_conv_geom_grad_desc* gr = nullptr) {
     LRPX_REQUIRE(d, "%s: null descriptor", fn);
     LRPX_REQUIRE(d->in && d->wpacked && d->out, "%s: null pointer", fn);
     LRPX_REQUIRE(d->dir == LRPX_GEOM_FWD || d->dir == LRPX_GEOM_BWD, "%s: unknown direction %d", fn, d->dir);
     if (ab) LRPX_TRY(conv_geom_ab_check(ab, fn));
-    LRPX_REQUIRE(d->dir == LRPX_GEOM_FWD || d->x, "%s: the transposed direction needs the multiplicand x", fn);
+    if (gr) LRPX_TRY(conv_geom_grad_check(gr, fn));
+    LRPX_REQUIRE(d->dir == LRPX_GEOM_FWD || d->x || gr, "%s: the transposed direction needs the multiplicand x", fn);
     LRPX_REQUIRE(d->dir == LRPX_GEOM_BWD || (!d->x && !d->q && !d->addend && !d->map2img),
                  "%s: x, q, addend and map2img belong to the transposed direction", fn);
     LRPX_REQUIRE(d->dir == LRPX_GEOM_FWD || !d->bias, "%s: bias belongs to the forward direction", fn);
@@ -98,7 +111,8 @@ inline int conv_geom_check(const lrpx_conv_geom_ex_desc* d, const char* fn, cons
     LRPX_REQUIRE(pix_in < (1L << 31) && pix_out < (1L << 31), "%s: more than 2^31 pixels", fn);
     LRPX_REQUIRE(ceil_div(d->n_oc, CG_TN) < 65536 && d->sh * d->sw < 65536, "%s: too many output channels or stride classes", fn);
     LRPX_CHECK_PTRS(fn, {d->in, "in"}, {d->wpacked, "wpacked"}, {d->bias, "bias"}, {d->x, "x"}, {d->q, "q"}, {ab ? ab->q2 : nullptr, "q2"},
-                    {d->addend, "addend"}, {d->map2img, "map2img"}, {d->out, "out"});
+                    {d->addend, "addend"}, {d->map2img, "map2img"}, {d->out, "out"}, {gr ? gr->mask : nullptr, "mask"},
+                    {gr ? gr->scale : nullptr, "scale"});
     return LRPX_OK;
 }
 

@@ -3,7 +3,8 @@
 // accumulation on v_mfma_f32_32x32x2_f32, one fmaf chain per output over (tap, channel).  The signed-input / alpha / beta / bias handling
 // stays outside (lrpx_nchw_to_nhwc_posneg, weight stacks built by the caller, lrpx_divide_stab / lrpx_divide_alpha_beta,
 // lrpx_fold_halves): lrpx_conv_geom is a plain convolution (+ bias) and a plain transposed convolution (* x), lrpx_conv_geom_ex the same
-// with the operands of a batched relevance pass, lrpx_conv_geom_ab its transposed direction with two coefficients.
+// with the operands of a batched relevance pass, lrpx_conv_geom_ab its transposed direction with two coefficients, lrpx_conv_geom_grad
+// the transposed direction of the gradient chain (raw weights, the operand clamped / masked / scaled in the gather, no multiplicand).
 #include "conv_geom_kernel.h"
 
 namespace lrpx {
@@ -68,6 +69,11 @@ int lrpx_conv_geom_ex(const lrpx_conv_geom_ex_desc* d, void* stream) { return co
 int lrpx_conv_geom_ab(const lrpx_conv_geom_ab_desc* a, void* stream) {
     LRPX_REQUIRE(a, "lrpx_conv_geom_ab: null descriptor");
     return conv_geom_run<CgF32, 1>(&a->base, a, stream, "lrpx_conv_geom_ab");
+}
+
+int lrpx_conv_geom_grad(const lrpx_conv_geom_grad_desc* g, void* stream) {
+    LRPX_REQUIRE(g, "lrpx_conv_geom_grad: null descriptor");
+    return conv_geom_run<CgF32, 3>(&g->base, nullptr, stream, "lrpx_conv_geom_grad", g);
 }
 
 }  // extern "C"

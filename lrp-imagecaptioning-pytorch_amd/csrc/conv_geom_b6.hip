@@ -93,4 +93,10 @@ int lrpx_conv_geom_ab_b6(const lrpx_conv_geom_ab_desc* a, void* stream) {
     return a->q2 ? conv_geom_run<CgB6, 2>(&a->base, a, stream, "lrpx_conv_geom_ab_b6") : conv_geom_run<CgB6, 1>(&a->base, a, stream, "lrpx_conv_geom_ab_b6");
 }
 
+// clamp, mask and scale are applied in fp32 before the split: the operand is lrpx_conv_geom_grad's
+int lrpx_conv_geom_grad_b6(const lrpx_conv_geom_grad_desc* g, void* stream) {
+    LRPX_REQUIRE(g, "lrpx_conv_geom_grad_b6: null descriptor");
+    return conv_geom_run<CgB6, 3>(&g->base, nullptr, stream, "lrpx_conv_geom_grad_b6", g);
+}
+
 }  // extern "C"

@@ -14,6 +14,9 @@
 // over the stacked index kappa in [0, 2 kr) against the weight rows [W+ ; W-] (packed as one tensor of 2 kr rows), and the operand is
 // A(kappa) = (R[c] * qh[c]) * sh with c = kappa mod kr and (qh, sh) = (q, scale) below kr, (q2, scale2) from kr on.  kr % 4 == 0, so a
 // thread's float4 never straddles the halves, wherever the boundary falls in a chunk.
+// The gradient chain (AB = 3) is the transposed kernel with the raw weights and an operand shaped while it is gathered:
+// A = scale[c] * (mask[img] > 0 ? (clamp ? max(in, 0) : in) : 0), each of the three optional, and the epilogue out = acc + addend: no
+// multiplicand, p.x is never read.
 #pragma once
 #include "conv_geom.h"
 
@@ -36,16 +39,21 @@ struct CgParams {
     int kr;
     const float* q2;
     float scale, scale2;
+    // AB = 3 only: per-image ReLU mask (indexed like q), per-channel factor (K floats), clamp the operand at 0 first
+    const float* mask;
+    const float* chscale;
+    int clamp;
 };
 
 // DIR = LRPX_GEOM_FWD: output pixels are the (OH, OW) map, sources the (H, W) map.
 // DIR = LRPX_GEOM_BWD: output pixels are the (H, W) map in sub-pixel classes (blockIdx.z), sources the (OH, OW) map.
 // AB (transposed direction only) 1: the dual-coefficient gather;  2: the same, with the policy's cross products in an accumulator of their
-// own (CgB6 over both halves, K = 2 kr).
+// own (CgB6 over both halves, K = 2 kr);  3: the gradient chain's gather and epilogue.
 template <typename Arith, int DIR, int AB>
 __global__ __launch_bounds__(256) void conv_geom_kernel(const CgParams p) {
     typedef typename Arith::BFrag BFrag;
     constexpr int NB = Arith::NB;
+    constexpr bool DUAL = AB == 1 || AB == 2, GRAD = AB == 3;
     __shared__ __attribute__((aligned(16))) char a_lds[CG_TM * Arith::ROWB];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave & 1, wn = wave >> 1;
@@ -113,14 +121,25 @@ __global__ __launch_bounds__(256) void conv_geom_kernel(const CgParams p) {
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
             if (pn[u] >= 0 && sy >= 0 && sy < SY && sx >= 0 && sx < SX && kc < p.K) {
                 const long pix = (long)sy * SX + sx;
-                const bool neg = AB && kc >= p.kr;                 // the W- half of the stacked contraction
-                const int c = neg ? kc - p.kr : kc, ld = AB ? p.kr : p.K;
+                const bool neg = DUAL && kc >= p.kr;                 // the W- half of the stacked contraction
+                const int c = neg ? kc - p.kr : kc, ld = DUAL ? p.kr : p.K;
                 v = *reinterpret_cast<const f32x4*>(p.in + ((long)pn[u] * SY * SX + pix) * ld + c);
-                if (DIR == LRPX_GEOM_BWD && p.q) {
+                if (DIR == LRPX_GEOM_BWD && !GRAD && p.q) {
                     const f32x4 qv = *reinterpret_cast<const f32x4*>((neg ? p.q2 : p.q) + ((long)pim[u] * SY * SX + pix) * ld + c);
                     v = v * qv;
                 }
-                if (AB) v = v * (neg ? p.scale2 : p.scale);        // (R q) s in this order: s = 1 leaves the preset's operand
+                if (DUAL) v = v * (neg ? p.scale2 : p.scale);      // (R q) s in this order: s = 1 leaves the preset's operand
+                if (GRAD) {                                        // clamp, mask, scale in this order, all in fp32
+                    if (p.clamp)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+                    if (p.mask) {
+                        const f32x4 mv = *reinterpret_cast<const f32x4*>(p.mask + ((long)pim[u] * SY * SX + pix) * ld + c);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) v[e] = mv[e] <= 0.f ? 0.f : v[e];
+                    }
+                    if (p.chscale) v = v * *reinterpret_cast<const f32x4*>(p.chscale + c);
+                }
             }
             ra[u] = v;
         }
@@ -160,6 +179,10 @@ __global__ __launch_bounds__(256) void conv_geom_kernel(const CgParams p) {
         const long off = (m * OY * OX + pix) * p.n_oc + oc;
         if (DIR == LRPX_GEOM_FWD) {
             p.out[off] = acc[e] + bias;
+        } else if (GRAD) {
+            float v = nst > 0 ? acc[e] : 0.f;
+            if (p.addend) v += p.addend[off];
+            p.out[off] = v;
         } else {
             const long img = p.map2img ? p.map2img[m] : m;
             float v = nst > 0 ? acc[e] * p.x[(img * OY * OX + pix) * p.n_oc + oc] : 0.f;
@@ -169,14 +192,16 @@ __global__ __launch_bounds__(256) void conv_geom_kernel(const CgParams p) {
     }
 }
 
-// Check the descriptor (`ab`: the dual-coefficient entries, d = &ab->base) and launch its direction: conv_geom_kernel<Arith, FWD, 0> on
+// Check the descriptor (`ab`: the dual-coefficient entries, d = &ab->base; `gr`: the gradient entries, d = &gr->base, AB = 3) and launch its direction: conv_geom_kernel<Arith, FWD, 0> on
 // ceil(output pixels / CG_TM) tiles, or <Arith, BWD, AB> on the tiles of the largest class, (0, 0), for each of the sh * sw classes.
 template <typename Arith, int AB>
-int conv_geom_run(const lrpx_conv_geom_ex_desc* d, const lrpx_conv_geom_ab_desc* ab, void* stream, const char* fn) {
-    LRPX_TRY(conv_geom_check(d, fn, ab));
+int conv_geom_run(const lrpx_conv_geom_ex_desc* d, const lrpx_conv_geom_ab_desc* ab, void* stream, const char* fn,
+                  const lrpx_conv_geom_grad_desc* gr = nullptr) {
+    LRPX_TRY(conv_geom_check(d, fn, ab, gr));
     const CgParams p = {d->in, (const char*)d->wpacked, d->bias, d->x, d->q, d->addend, d->map2img, d->out, d->n, d->h, d->w, d->oh, d->ow,
                         d->kh, d->kw, d->sh, d->sw, d->ph, d->pw, d->k, d->n_oc, (int)ceil_div(d->k, CG_KC), d->kh * d->kw,
-                        ab ? ab->kr : 0, ab ? ab->q2 : nullptr, ab ? ab->scale : 0.f, ab ? ab->scale2 : 0.f};
+                        ab ? ab->kr : 0, ab ? ab->q2 : nullptr, ab ? ab->scale : 0.f, ab ? ab->scale2 : 0.f,
+                        gr ? gr->mask : nullptr, gr ? gr->scale : nullptr, gr ? gr->clamp : 0};
     const unsigned gy = (unsigned)ceil_div(d->n_oc, CG_TN);
     if (d->dir == LRPX_GEOM_FWD) {
         const long pix_out = (long)d->n * d->oh * d->ow;

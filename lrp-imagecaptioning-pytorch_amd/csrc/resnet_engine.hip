@@ -10,6 +10,9 @@
 //     lrpx_resnet_add_split     R1 = R c1[img], R2 = R c2[img]: the Add rule behind the block's final ReLU (identity rule)
 //     lrpx_resnet_maxpool_rel   the Pool2d rule as a gather per input pixel (the logic of lrpx_maxpool_rule)   lrp_modules.py:182-195
 //     lrpx_resnet_stem_fold     [x+ convT | x- convT] halves of the stem's rule joined into the NCHW result    lrp_modules.py:81-84
+//   gradient chain (per map)
+//     lrpx_resnet_relu_grad     ReLU backward at a block's output, with guided backprop's clamp on request
+//     lrpx_resnet_maxpool_grad  MaxPool2d backward: the gather of lrpx_resnet_maxpool_rel without the division and the x factor
 // No kernel uses atomics: a map's result does not depend on the other maps of the call.
 #include <math.h>
 
@@ -132,6 +135,55 @@ __global__ void resnet_maxpool_rel_kernel(const float* __restrict__ x, const flo
     r_in[i] = xp[(long)p * c] * grad;
 }
 
+// the gather of resnet_maxpool_rel_kernel: the winning windows' gradients, added in ascending (oh, ow) order
+__global__ void resnet_maxpool_grad_kernel(const float* __restrict__ x, const float* __restrict__ g_out, const int32_t* __restrict__ map2img,
+                                           float* __restrict__ g_in, long n_maps, int c, RnPoolGeom g) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_maps * g.H * g.W * c) return;
+    const int ch = (int)(i % c);
+    long rest = i / c;
+    const int w = (int)(rest % g.W);
+    rest /= g.W;
+    const int h = (int)(rest % g.H);
+    const long m = rest / g.H;
+    const long img = map2img ? map2img[m] : m;
+    const int oh_lo = max(0, (h + g.ph - g.kh + g.sh) / g.sh), oh_hi = min(g.OH - 1, (h + g.ph) / g.sh);
+    const int ow_lo = max(0, (w + g.pw - g.kw + g.sw) / g.sw), ow_hi = min(g.OW - 1, (w + g.pw) / g.sw);
+    const float* xp = x + img * g.H * g.W * c + ch;
+    const float* gp = g_out + m * g.OH * g.OW * c + ch;
+    const int p = h * g.W + w;
+    float grad = 0.f;
+    for (int oh = oh_lo; oh <= oh_hi; ++oh) {
+        const int h0 = max(oh * g.sh - g.ph, 0), h1 = min(oh * g.sh - g.ph + g.kh, g.H);
+        for (int ow = ow_lo; ow <= ow_hi; ++ow) {
+            const int w0 = max(ow * g.sw - g.pw, 0), w1 = min(ow * g.sw - g.pw + g.kw, g.W);
+            int win = h0 * g.W + w0;
+            float mx = -INFINITY;
+            for (int ih = h0; ih < h1; ++ih)
+                for (int iw = w0; iw < w1; ++iw) {
+                    const float v = xp[((long)ih * g.W + iw) * c];
+                    if (v > mx || v != v) {
+                        mx = v;
+                        win = ih * g.W + iw;
+                    }
+                }
+            if (win == p) grad += gp[((long)oh * g.OW + ow) * c];
+        }
+    }
+    g_in[i] = grad;
+}
+
+__global__ void resnet_relu_grad_kernel(const float* __restrict__ g, const float* __restrict__ act, const int32_t* __restrict__ map2img,
+                                        float* __restrict__ out, long n_maps, long per, int clamp) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_maps * per) return;
+    const long m = i / per;
+    const long j = (map2img ? (long)map2img[m] : m) * per + (i - m * per);
+    float v = g[i];
+    if (clamp) v = fmaxf(v, 0.f);
+    out[i] = act[j] > 0.f ? v : 0.f;
+}
+
 __global__ void resnet_add_split_kernel(const float* __restrict__ r, const float* __restrict__ c1, const float* __restrict__ c2,
                                         const int32_t* __restrict__ map2img, float* __restrict__ r1, float* __restrict__ r2,
                                         long n_maps, long per) {
@@ -233,6 +285,33 @@ int lrpx_resnet_add_split(const float* r, const float* c1, const float* c2, cons
     hipLaunchKernelGGL(resnet_add_split_kernel, dim3(blocks_of(n_maps * per_map)), dim3(256), 0, (hipStream_t)stream, r, c1, c2, map2img, r1,
                        r2, (long)n_maps, per_map);
     return check_launch("resnet_add_split");
+}
+
+int lrpx_resnet_relu_grad(const float* g, const float* act, const int32_t* map2img, float* out, int n_maps, int n_img, long per_map,
+                          int clamp, void* stream) {
+    LRPX_REQUIRE(g && act && out, "resnet_relu_grad: null pointer");
+    LRPX_REQUIRE(n_maps > 0 && n_img > 0 && per_map > 0 && n_maps * per_map < (1L << 38), "resnet_relu_grad: bad sizes");
+    LRPX_REQUIRE(map2img || n_maps == n_img, "resnet_relu_grad: without map2img there is one map per image");
+    LRPX_REQUIRE(clamp == 0 || clamp == 1, "resnet_relu_grad: clamp is 0 or 1 (%d)", clamp);
+    LRPX_CHECK_PTRS("lrpx_resnet_relu_grad", {g, "g"}, {act, "act"}, {map2img, "map2img"}, {out, "out"});
+    hipLaunchKernelGGL(resnet_relu_grad_kernel, dim3(blocks_of(n_maps * per_map)), dim3(256), 0, (hipStream_t)stream, g, act, map2img, out,
+                       (long)n_maps, per_map, clamp);
+    return check_launch("resnet_relu_grad");
+}
+
+int lrpx_resnet_maxpool_grad(const float* x, const float* g_out, const int32_t* map2img, float* g_in, int n_maps, int n_img, int h, int w,
+                             int oh, int ow, int c, int kh, int kw, int sh, int sw, int ph, int pw, void* stream) {
+    LRPX_REQUIRE(x && g_out && g_in, "resnet_maxpool_grad: null pointer");
+    LRPX_REQUIRE(n_maps > 0 && n_img > 0 && c > 0 && pool_geom_ok(h, w, oh, ow, kh, kw, sh, sw, ph, pw),
+                 "resnet_maxpool_grad: bad sizes or window (maps %d images %d c %d, %dx%d -> %dx%d, kernel %dx%d stride %dx%d padding %dx%d)",
+                 n_maps, n_img, c, h, w, oh, ow, kh, kw, sh, sw, ph, pw);
+    LRPX_REQUIRE(map2img || n_maps == n_img, "resnet_maxpool_grad: without map2img there is one map per image");
+    LRPX_REQUIRE((long)n_maps * h * w * c < (1L << 38), "resnet_maxpool_grad: tensor too large");
+    LRPX_CHECK_PTRS("lrpx_resnet_maxpool_grad", {x, "x"}, {g_out, "g_out"}, {map2img, "map2img"}, {g_in, "g_in"});
+    const RnPoolGeom g = {h, w, oh, ow, kh, kw, sh, sw, ph, pw};
+    hipLaunchKernelGGL(resnet_maxpool_grad_kernel, dim3(blocks_of((long)n_maps * h * w * c)), dim3(256), 0, (hipStream_t)stream, x, g_out,
+                       map2img, g_in, (long)n_maps, c, g);
+    return check_launch("resnet_maxpool_grad");
 }
 
 int lrpx_resnet_stem_fold(const float* r_split, float* out, int n_maps, int cin, int half, int ld, long pix, void* stream) {

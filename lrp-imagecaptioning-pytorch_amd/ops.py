@@ -791,6 +791,55 @@ def conv_geom_ab(inp, wpacked, n, hw, ohw, geom, kr, n_oc, x, q, q2=None, scale=
     return out
 
 
+def conv_geom_grad(inp, wpacked, n, hw, ohw, geom, k, n_oc, mask=None, scale=None, clamp=False, addend=None, map2img=None, n_img=None,
+                   out=None, validate=True, b6=False):
+    """`lrpx_conv_geom_grad` (b6: `lrpx_conv_geom_grad_b6`): the transposed direction for the gradient chain (include/lrpx.h, DESIGN.md
+    5.12).  inp (n maps, OH OW, k) -> out (n, H W, n_oc) = convT(scale * (mask[img] > 0 ? (clamp ? max(inp, 0) : inp) : 0), W) + addend
+    with wpacked the transposed pack of the RAW weights; mask (n_img, OH OW, k), scale (k,), addend like out, each optional.
+    LAUNCHES counts it under 'conv_geom_grad' (b6: 'conv_geom_grad_b6')."""
+    n_img = n if n_img is None else n_img
+    if mask is not None and tuple(mask.shape) != (n_img, ohw[0] * ohw[1], k):
+        raise ValueError("conv_geom_grad: mask must be (n_img, OH OW, k)")
+    if scale is not None and tuple(scale.shape) != (k,):
+        raise ValueError("conv_geom_grad: scale must be (k,)")
+    if addend is not None and tuple(addend.shape) != (n, hw[0] * hw[1], n_oc):
+        raise ValueError("conv_geom_grad: addend must have the output's shape")
+    if map2img is not None and validate:
+        map2img = check_map2img(map2img, n, n_img)
+    if inp.numel() != n * ohw[0] * ohw[1] * k:
+        raise ValueError("conv_geom_grad: the input must hold n x pixels x k = {} x {} x {} floats".format(n, ohw[0] * ohw[1], k))
+    if out is None:
+        out = torch.empty(n, hw[0] * hw[1], n_oc, dtype=torch.float32, device=inp.device)
+    elif out.numel() != n * hw[0] * hw[1] * n_oc:
+        raise ValueError("conv_geom_grad: the output must hold n x pixels x n_oc floats")
+    base = _lib.ConvGeomExDesc(ptr(_dev(inp)), ptr(_dev(wpacked)), None, None, None, ptr(_dev(addend)), ptr(_dev(map2img)), ptr(_dev(out)),
+                               _lib.GEOM_BWD, n, n_img, hw[0], hw[1], ohw[0], ohw[1], *geom, k, n_oc)
+    d = _lib.ConvGeomGradDesc(base, ptr(_dev(mask)), ptr(_dev(scale)), 1 if clamp else 0)
+    _count("conv_geom_grad_b6" if b6 else "conv_geom_grad", _lib.GEOM_BWD)
+    lib = _lib.load()
+    check((lib.lrpx_conv_geom_grad_b6 if b6 else lib.lrpx_conv_geom_grad)(C.byref(d), stream_ptr()))
+    return out
+
+
+def conv_geom_grad_b6(*args, **kw):
+    """`conv_geom_grad` in the exact bf16-split arithmetic (wpacked from `conv_geom_pack_bf16x3`)"""
+    return conv_geom_grad(*args, b6=True, **kw)
+
+
+def resnet_relu_grad(g, act, map2img, out, n_maps, n_img, clamp):
+    """out = (clamp ? max(g, 0) : g) * (act[img] > 0): ReLU backward at a block's output (include/lrpx.h)"""
+    _count("resnet_relu_grad")
+    check(_lib.load().lrpx_resnet_relu_grad(ptr(_dev(g)), ptr(_dev(act)), ptr(map2img), ptr(_dev(out)), n_maps, n_img, g.numel() // n_maps,
+                                            1 if clamp else 0, stream_ptr()))
+
+
+def resnet_maxpool_grad(x, g_out, map2img, g_in, n_maps, n_img, hw, ohw, c, win):
+    """MaxPool2d backward on NHWC: each window's gradient to its first maximum (include/lrpx.h)"""
+    _count("resnet_maxpool_grad")
+    check(_lib.load().lrpx_resnet_maxpool_grad(ptr(_dev(x)), ptr(_dev(g_out)), ptr(map2img), ptr(_dev(g_in)), n_maps, n_img, hw[0], hw[1],
+                                               ohw[0], ohw[1], c, *win, stream_ptr()))
+
+
 def resnet_bn_act_coef(yz, w, b, act, q, relu):
     """yz (n, pix, 2c) = [conv output | Z of its rule] -> act = BN affine (+ ReLU), q = the conv's relevance coefficient (include/lrpx.h)"""
     c = w.shape[0]
@@ -1088,7 +1137,8 @@ class ResNetEncoder:
     conv_mode: the arithmetic of every contraction of the trace and of the maps - 0: fp32 MFMA (`lrpx_conv_geom_ex`); 1: the exact
     bf16 split, six plane products on the bf16 MFMA (`lrpx_conv_geom_ex_b6`).  The engine's own choice: it does not
     follow `lrpx_set_conv_mode`.  `replica()` shares packs and mode.
-    `relevance_alpha_beta` runs the general alpha-beta rule on the same trace, in either mode."""
+    `relevance_alpha_beta` runs the general alpha-beta rule on the same trace, in either mode.
+    `gradient` / `guided_backprop` run the autograd chain and guided backprop on the same trace, in either mode."""
 
     CONV_MODES = (0, 1)
 
@@ -1127,6 +1177,7 @@ class ResNetEncoder:
                 k_in = self.c2
             self.packs.append(dict(fwd=fwd, bwd=bwd, w=w, b=b, k_in=k_in, cout=cv["cout"], geom=cv["geom"]))
         self._ab_packs = []                           # the general rule's packs, built at its first call; replicas share the list
+        self._grad_packs = []                         # the gradient chain's raw-W transposed packs, likewise
         torch.cuda.current_stream().synchronize()
         self._reset()
 
@@ -1407,6 +1458,91 @@ class ResNetEncoder:
         resnet_maxpool_rel(t["act"][0], r, map2img, rp, n_maps, B, self.pool_dims[0], self.pool_dims[1], self.packs[0]["cout"], self.plan.pool)
         rs = convT(0, rp, t["xs"], None, ws["b"])
         resnet_stem_fold(rs, out, n_maps, self.cin, self.cin, self.c2, H * W)
+        return out
+
+    # ---- the gradient chain -----------------------------------------------------------------------------------------
+    def _grad_state(self):
+        """per conv: the transposed pack of the RAW weights W (K = cout; the stem onto its cin image channels) in the engine's mode.
+        Built once per engine from the model's weights, at the first gradient call."""
+        if not self._grad_packs:
+            pack = conv_geom_pack_bf16x3 if self.b6 else conv_geom_pack
+            for cv in self.plan.convs:
+                self._grad_packs.append(pack(cv["module"].weight.detach().to(torch.float32), _lib.GEOM_BWD))
+            torch.cuda.current_stream().synchronize()
+        return self._grad_packs
+
+    def gradient(self, d_feat_nhwc, map2img=None, out=None, layer_ms=None):
+        """The autograd gradient of the image (ExplainGridTDGradient.explain_cnn, models/gridTDmodel.py:1510-1521) for n_maps maps:
+        (n_maps, h w, C) gradient at the feature map -> (n_maps, cin, H, W); arguments and map2img contract of `relevance`.  ReLU:
+        the trace's mask; BatchNorm (eval): its factor; conv: transposed conv with the raw weights; Add: both branches; MaxPool2d: the
+        first maximum.  No forward work, no divisions; the trace is only read."""
+        return self._grad_chain("gradient", d_feat_nhwc, map2img, out, None, layer_ms)
+
+    def guided_backprop(self, d_feat_nhwc, map2img=None, out=None, relus="stem", layer_ms=None):
+        """Guided backprop on the trace, arguments as `gradient`.  relus="stem": the reference's behaviour
+        (ExplainiGridTDGuidedGradient.register_hooks, models/gridTDmodel.py:1677-1691, hooks the encoder's DIRECT children: on a ResNet
+        the stem's ReLU alone) - the plain gradient with max(g, 0) at the stem ReLU's output.  relus="all": max(g, 0) at every ReLU
+        output (stem, both inner ReLUs of each block, each block's ReLU behind the Add), canonical guided backprop."""
+        if relus not in ("stem", "all"):
+            raise ValueError("ResNetEncoder.guided_backprop: relus must be 'stem' or 'all', got {!r}".format(relus))
+        return self._grad_chain("guided_backprop", d_feat_nhwc, map2img, out, relus, layer_ms)
+
+    def _grad_chain(self, fn, d_feat_nhwc, map2img, out, relus, layer_ms):
+        if self.trace is None:
+            raise ValueError("ResNetEncoder.{}: no trace - call forward() first".format(fn))
+        B = self.n_img
+        t, dims = self.trace, self.dims
+        g = _dev(d_feat_nhwc)
+        c_feat = self.packs[self.plan.blocks[-1]["conv3"]]["cout"]
+        if g.dim() != 3 or tuple(g.shape[1:]) != (self.feat_hw[0] * self.feat_hw[1], c_feat) or g.dtype != torch.float32:
+            raise ValueError("ResNetEncoder.{}: d_feat_nhwc must be float32 (n_maps, {}, {}), got {}".format(
+                fn, self.feat_hw[0] * self.feat_hw[1], c_feat, tuple(g.shape)))
+        n_maps = g.shape[0]
+        if n_maps == 0:
+            raise ValueError("ResNetEncoder.{}: no maps".format(fn))
+        if map2img is None:
+            if n_maps != B:
+                raise ValueError("ResNetEncoder.{}: without map2img there is one map per image of the trace ({} maps, {} images)"
+                                 .format(fn, n_maps, B))
+        else:
+            map2img = check_map2img(map2img, n_maps, B)
+        H, W = self.shape[1], self.shape[2]
+        if out is None:
+            out = torch.empty(n_maps, self.cin, H, W, dtype=torch.float32, device=self.device)
+        elif tuple(out.shape) != (n_maps, self.cin, H, W) or not out.is_contiguous():
+            raise ValueError("ResNetEncoder.{}: out must be contiguous (n_maps, {}, {}, {})".format(fn, self.cin, H, W))
+        g = g.contiguous()
+        gp = self._grad_state()
+        ws = self._workspace(n_maps)
+        clamp_all, clamp_stem = relus == "all", relus is not None
+
+        def convT(i, g_out, n_oc, mask, clamp, addend, dst):
+            pk = self.packs[i]
+            ev = _events(layer_ms)
+            hw, ohw = dims[i]
+            o = dst[: n_maps * hw[0] * hw[1] * n_oc].view(n_maps, hw[0] * hw[1], n_oc)
+            conv_geom_grad(g_out, gp[i], n_maps, hw, ohw, pk["geom"], pk["cout"], n_oc, mask=mask, scale=pk["w"], clamp=clamp,
+                           addend=addend, map2img=map2img, n_img=B, out=o, validate=False, b6=self.b6)
+            _events_done(ev, layer_ms, self.plan.convs[i]["name"])
+            return o
+        cur = 0
+        for bi in range(len(self.plan.blocks) - 1, -1, -1):
+            blk = self.plan.blocks[bi]
+            c_in = (t["out"][bi - 1] if bi > 0 else t["pool"]).shape[2]
+            g0 = ws["r1"][: g.numel()].view(g.shape)                   # the gradient at the Add's sum
+            resnet_relu_grad(g, t["out"][bi], map2img, g0, n_maps, B, clamp_all)
+            ga = convT(blk["conv3"], g0, self.packs[blk["conv2"]]["cout"], None, False, None, ws["a"])
+            gb = convT(blk["conv2"], ga, self.packs[blk["conv1"]]["cout"], t["act"][blk["conv2"]], clamp_all, None, ws["b"])
+            short = g0
+            if blk["downsample"] is not None:
+                short = convT(blk["downsample"], g0, c_in, None, False, None, ws["a"])
+            g = convT(blk["conv1"], gb, c_in, t["act"][blk["conv1"]], clamp_all, short, ws["r"][cur])
+            cur = 1 - cur
+        c0 = self.packs[0]["cout"]
+        gs = ws["a"][: n_maps * t["act"][0][0].numel()].view(n_maps, *t["act"][0].shape[1:])
+        resnet_maxpool_grad(t["act"][0], g, map2img, gs, n_maps, B, self.pool_dims[0], self.pool_dims[1], c0, self.plan.pool)
+        gi = convT(0, gs, self.cin, t["act"][0], clamp_stem, None, ws["b"])
+        check(_lib.load().lrpx_nhwc_to_nchw(ptr(gi), ptr(out), n_maps, self.cin, H * W, self.cin, stream_ptr()))
         return out
 
     def _workspace(self, n_maps):

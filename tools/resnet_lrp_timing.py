@@ -6,6 +6,8 @@ tests/golden/make_golden_resnet.py (`bottleneck_net(base=64, blocks=[3, 4, 6, 3]
     python tools/resnet_lrp_timing.py --engine [--engine-out profiles/resnet_engine_timing.txt] [--words 5]
     python tools/resnet_lrp_timing.py --engine --conv-mode both --batch 16 [--engine-only] [--engine-out profiles/resnet_engine_b6_timing.txt]
     python tools/resnet_lrp_timing.py --engine --alpha 2 --beta 1 [--conv-mode 0|1] [--engine-only]      (profiles/resnet_engine_ab_timing.txt)
+    python tools/resnet_lrp_timing.py --engine --pass all --conv-mode both --batch 4 --words 10 --size 448 --blocks 3,4,23,3 --reps 3
+                                                                                                      (profiles/resnet_grad_timing.txt)
 
 Reports the whole call, the milliseconds per leaf type (HIP events around each rule call, layout conversions and the rule's checks
 included) and every distinct launch of the runtime-geometry conv engine (csrc/conv_geom.hip) with its flop as issued -
@@ -32,7 +34,15 @@ call (which makes qn) and the per-layer table of both map passes.  It prints med
 noise, and the measured ratios; no ratio is fixed.  By flop count the alpha-beta map pass is 2 x the preset's and the generic driver
 does about 4 x the preset's conv work per map.  The targets are scaled by 1e-8: with beta != 0 the relevance grows by up to
 (alpha + beta) per conv, and the generic driver refuses a non-finite result.  Writes --engine-out, by default
-profiles/resnet_engine_ab_timing.txt."""
+profiles/resnet_engine_ab_timing.txt.
+
+--pass gradient | guided | all (with --engine; `relevance`, the default, is the legs above) times the gradient chain of the engine
+(`ops.ResNetEncoder.gradient` / `guided_backprop`) beside `relevance` on the same trace: per conv mode (--conv-mode 0, 1
+or both) one engine, one forward of --batch images of --size x --size pixels through `bottleneck_net(64, --blocks)`, every pass
+warmed once, then the passes ALTERNATING for --reps repetitions (at least 3) on --batch x --words maps with HIP events around each
+call.  `gradient` times relevance and the plain gradient, `guided` relevance and guided backprop with relus = "stem" and "all", `all`
+the four.  It prints the median, the spread (min .. max) and the median per map, and each pass against `relevance`; nothing is
+asserted.  Writes --engine-out, by default profiles/resnet_grad_timing.txt."""
 import argparse
 import collections
 import os
@@ -55,11 +65,17 @@ def main():
     ap.add_argument("--engine-only", action="store_true", help="--engine: skip the generic driver's legs")
     ap.add_argument("--alpha", type=float, default=None, help="--engine: time the general alpha-beta rule (with --beta)")
     ap.add_argument("--beta", type=float, default=None)
+    ap.add_argument("--pass", dest="passes", choices=["relevance", "gradient", "guided", "all"], default="relevance",
+                    help="--engine: time the gradient chain beside relevance (DESIGN.md 5.12)")
+    ap.add_argument("--size", type=int, default=224, help="--pass: image side")
+    ap.add_argument("--blocks", default="3,4,6,3", help="--pass: blocks per stage (3,4,23,3 is the ResNet-101 shape)")
     a = ap.parse_args()
     if (a.alpha is None) != (a.beta is None) or (a.alpha is not None and not a.engine):
         ap.error("--alpha and --beta go together, and with --engine")
     if a.alpha is not None and a.conv_mode == "both":
         ap.error("--alpha / --beta: one conv mode per run")
+    if a.passes != "relevance" and (not a.engine or a.alpha is not None):
+        ap.error("--pass goes with --engine, without --alpha / --beta")
     import numpy as np
     import torch
     sys.path.insert(0, ROOT)
@@ -70,6 +86,8 @@ def main():
     from make_golden_resnet import bottleneck_net
     if not torch.cuda.is_available():
         raise SystemExit("resnet_lrp_timing: no GPU - a time is measured on the device or not at all")
+    if a.passes != "relevance":
+        return pass_leg(a)
     net = bottleneck_net(np.random.RandomState(0), lrp_modules.resAdd, 64, [3, 4, 6, 3]).cuda()
     lrp_wrapper.add_lrp(net)
     g = torch.Generator().manual_seed(0)
@@ -226,6 +244,57 @@ def engine_leg(a, net, x):
     if a.engine_out:
         with open(a.engine_out, "w") as f:
             f.write(report)
+
+
+def pass_leg(a):
+    """relevance and the gradient chain's passes on one trace per conv mode, alternating in this process"""
+    import numpy as np
+    import torch
+    from lrp_amd import ops
+    from lrp_amd.LRPtools import lrp_modules
+    from make_golden_resnet import bottleneck_net
+    blocks = [int(b) for b in a.blocks.split(",")]
+    reps, n_maps = max(a.reps, 3), a.batch * a.words
+    net = bottleneck_net(np.random.RandomState(0), lrp_modules.resAdd, 64, blocks).cuda()
+    g = torch.Generator().manual_seed(0)
+    x = torch.randn(a.batch, 3, a.size, a.size, generator=g).cuda()
+    map2img = torch.arange(n_maps, dtype=torch.int32).div(a.words, rounding_mode="floor").to(torch.int32).cuda()
+    names = {"gradient": ["relevance", "gradient"], "guided": ["relevance", "guided stem", "guided all"],
+             "all": ["relevance", "gradient", "guided stem", "guided all"]}[a.passes]
+    lines = [f"# tools/resnet_lrp_timing.py --engine --pass {a.passes} --conv-mode {a.conv_mode} --batch {a.batch} --words {a.words} "
+             f"--size {a.size} --blocks {a.blocks} --reps {reps}",
+             f"== bottleneck_net(base=64, blocks={blocks}), {a.batch} images x {a.words} words = {n_maps} maps at {a.size} x {a.size}, "
+             f"{torch.cuda.get_device_name(0)}; passes alternating, {reps} repetitions after one warm-up each, HIP events around each call"]
+    for mode in ([0, 1] if a.conv_mode == "both" else [int(a.conv_mode)]):
+        eng = ops.ResNetEncoder(net, conv_mode=mode)
+        h, w, c = eng.feature_shape(a.size, a.size)
+        d = torch.randn(n_maps, h * w, c, generator=g).cuda()
+        out = torch.empty(n_maps, 3, a.size, a.size, device="cuda")
+        eng.forward(x)
+        fns = {"relevance": lambda: eng.relevance(d, map2img, out=out), "gradient": lambda: eng.gradient(d, map2img, out=out),
+               "guided stem": lambda: eng.guided_backprop(d, map2img, out=out), "guided all": lambda: eng.guided_backprop(d, map2img, out=out, relus="all")}
+        ms = {n: [] for n in names}
+        for r in range(reps + 1):
+            for n in names:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fns[n]()
+                e1.record()
+                e1.synchronize()
+                if r:                              # repetition 0 warms up (and builds the gradient chain's packs)
+                    ms[n].append(e0.elapsed_time(e1))
+        med = {n: float(np.median(v)) for n, v in ms.items()}
+        lines += ["", f"conv mode {mode}  (trace {eng.trace_bytes(a.batch, a.size, a.size) / 2**30:.2f} GiB, peak device memory "
+                      f"{torch.cuda.max_memory_allocated() / 2**30:.1f} GiB)",
+                  f"  {'pass':<14} {'median ms':>10} {'min':>9} {'max':>9} {'ms per map':>11} {'vs relevance':>13}"]
+        for n in names:
+            lines.append(f"  {n:<14} {med[n]:10.2f} {min(ms[n]):9.2f} {max(ms[n]):9.2f} {med[n] / n_maps:11.3f} {med[n] / med['relevance']:12.3f}x")
+        del eng, d, out
+        torch.cuda.empty_cache()
+    report = "\n".join(lines) + "\n"
+    sys.stdout.write(report)
+    with open(a.engine_out or os.path.join(ROOT, "profiles", "resnet_grad_timing.txt"), "w") as f:
+        f.write(report)
 
 
 def mode_leg(a, net, x, t_nhwc, map2img, eng0):
