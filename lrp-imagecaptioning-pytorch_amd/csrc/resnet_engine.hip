@@ -9,10 +9,11 @@
 //   relevance (per map, the per-image operands through map2img)
 //     lrpx_resnet_add_split     R1 = R c1[img], R2 = R c2[img]: the Add rule behind the block's final ReLU (identity rule)
 //     lrpx_resnet_maxpool_rel   the Pool2d rule as a gather per input pixel (the logic of lrpx_maxpool_rule)   lrp_modules.py:182-195
+//                               (resnet_maxpool_gather_kernel<false>)
 //     lrpx_resnet_stem_fold     [x+ convT | x- convT] halves of the stem's rule joined into the NCHW result    lrp_modules.py:81-84
 //   gradient chain (per map)
 //     lrpx_resnet_relu_grad     ReLU backward at a block's output, with guided backprop's clamp on request
-//     lrpx_resnet_maxpool_grad  MaxPool2d backward: the gather of lrpx_resnet_maxpool_rel without the division and the x factor
+//     lrpx_resnet_maxpool_grad  MaxPool2d backward: the same gather without the division and the x factor (resnet_maxpool_gather_kernel<true>)
 // No kernel uses atomics: a map's result does not depend on the other maps of the call.
 #include <math.h>
 
@@ -25,6 +26,14 @@ namespace lrpx {
 static constexpr float kEps = 0.01f;      // LRPtools/utils.py:10 EPSILON
 static constexpr float kZEps = 1e-7f;     // LRPtools/utils.py:11 Z_EPSILON
 
+// the BatchNorm fraction safe_divide(|y w|, |y w| + |b|) over safe(z): a conv's relevance coefficient, z = Z+ (q) or Z- (qn)
+__device__ __forceinline__ float bn_coef(float y, float wc, float bc, float z) {
+    const float xw = fabsf(y * wc);                                   // lrp_modules.py:212
+    const float den = xw + fabsf(bc);
+    const float frac = xw / (den + kZEps * (den == 0.f ? 1.f : 0.f)); // safe_divide, :214
+    return frac / (z + kZEps * (z == 0.f ? 1.f : 0.f));               // S = R / safe(Z), utils.py:28
+}
+
 // yz: rows of `ld` floats, the conv's output y in columns [0, c), Z of its rule in [c, 2c) (the stacked forward contraction)
 __global__ void resnet_bn_act_coef_kernel(const float* __restrict__ yz, int ld, const float* __restrict__ w, const float* __restrict__ b,
                                           float* __restrict__ act, float* __restrict__ q, long rows, int c, int relu) {
@@ -36,24 +45,17 @@ __global__ void resnet_bn_act_coef_kernel(const float* __restrict__ yz, int ld, 
     const float wc = w[ch], bc = b[ch];
     const float a = y * wc + bc;
     act[i] = relu ? fmaxf(a, 0.f) : a;
-    const float xw = fabsf(y * wc);                                   // lrp_modules.py:212
-    const float den = xw + fabsf(bc);
-    const float frac = xw / (den + kZEps * (den == 0.f ? 1.f : 0.f)); // safe_divide, :214
-    q[i] = frac / (z + kZEps * (z == 0.f ? 1.f : 0.f));               // S = R / safe(Z), utils.py:28
+    q[i] = bn_coef(y, wc, bc, z);
 }
 
-// yz: the conv's output y in columns [0, c), Z- of the general rule in [c, 2c).  The fraction is evaluated exactly as above.
+// yz: the conv's output y in columns [0, c), Z- of the general rule in [c, 2c): the coefficient half of the kernel above
 __global__ void resnet_coef_neg_kernel(const float* __restrict__ yz, int ld, const float* __restrict__ w, const float* __restrict__ b,
                                        float* __restrict__ qn, long rows, int c) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= rows * c) return;
     const long r = i / c;
     const int ch = (int)(i - r * c);
-    const float y = yz[r * ld + ch], z = yz[r * ld + c + ch];
-    const float xw = fabsf(y * w[ch]);
-    const float den = xw + fabsf(b[ch]);
-    const float frac = xw / (den + kZEps * (den == 0.f ? 1.f : 0.f));
-    qn[i] = frac / (z + kZEps * (z == 0.f ? 1.f : 0.f));
+    qn[i] = bn_coef(yz[r * ld + ch], w[ch], b[ch], yz[r * ld + c + ch]);
 }
 
 __global__ void resnet_add_relu_coef_kernel(const float* __restrict__ x1, const float* __restrict__ x2, float* __restrict__ out,
@@ -97,9 +99,11 @@ __global__ void resnet_maxpool_fwd_kernel(const float* __restrict__ x, float* __
 }
 
 // one thread per INPUT element of a map: visits the windows that contain it in ascending (oh, ow) order, repeats the forward scan of
-// each and collects R_out / safe(max) of every window it wins (maxpool_rule_kernel of lrpx_rules.hip in NHWC, x through map2img)
-__global__ void resnet_maxpool_rel_kernel(const float* __restrict__ x, const float* __restrict__ r_out, const int32_t* __restrict__ map2img,
-                                          float* __restrict__ r_in, long n_maps, int c, RnPoolGeom g) {
+// each and adds up the term of every window it wins, x through map2img (maxpool_rule_kernel of lrpx_rules.hip in NHWC).
+// GRAD false, the Pool2d rule: term R_out / safe(max), result x * sum.  GRAD true, MaxPool2d backward: term g_out, result the sum.
+template <bool GRAD>
+__global__ void resnet_maxpool_gather_kernel(const float* __restrict__ x, const float* __restrict__ r_out, const int32_t* __restrict__ map2img,
+                                             float* __restrict__ r_in, long n_maps, int c, RnPoolGeom g) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_maps * g.H * g.W * c) return;
     const int ch = (int)(i % c);
@@ -129,48 +133,13 @@ __global__ void resnet_maxpool_rel_kernel(const float* __restrict__ x, const flo
                         win = ih * g.W + iw;
                     }
                 }
-            if (win == p) grad += rp[((long)oh * g.OW + ow) * c] / (mx + kZEps * (mx == 0.f ? 1.f : 0.f));
+            if (win == p) {
+                const float r = rp[((long)oh * g.OW + ow) * c];
+                grad += GRAD ? r : r / (mx + kZEps * (mx == 0.f ? 1.f : 0.f));
+            }
         }
     }
-    r_in[i] = xp[(long)p * c] * grad;
-}
-
-// the gather of resnet_maxpool_rel_kernel: the winning windows' gradients, added in ascending (oh, ow) order
-__global__ void resnet_maxpool_grad_kernel(const float* __restrict__ x, const float* __restrict__ g_out, const int32_t* __restrict__ map2img,
-                                           float* __restrict__ g_in, long n_maps, int c, RnPoolGeom g) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_maps * g.H * g.W * c) return;
-    const int ch = (int)(i % c);
-    long rest = i / c;
-    const int w = (int)(rest % g.W);
-    rest /= g.W;
-    const int h = (int)(rest % g.H);
-    const long m = rest / g.H;
-    const long img = map2img ? map2img[m] : m;
-    const int oh_lo = max(0, (h + g.ph - g.kh + g.sh) / g.sh), oh_hi = min(g.OH - 1, (h + g.ph) / g.sh);
-    const int ow_lo = max(0, (w + g.pw - g.kw + g.sw) / g.sw), ow_hi = min(g.OW - 1, (w + g.pw) / g.sw);
-    const float* xp = x + img * g.H * g.W * c + ch;
-    const float* gp = g_out + m * g.OH * g.OW * c + ch;
-    const int p = h * g.W + w;
-    float grad = 0.f;
-    for (int oh = oh_lo; oh <= oh_hi; ++oh) {
-        const int h0 = max(oh * g.sh - g.ph, 0), h1 = min(oh * g.sh - g.ph + g.kh, g.H);
-        for (int ow = ow_lo; ow <= ow_hi; ++ow) {
-            const int w0 = max(ow * g.sw - g.pw, 0), w1 = min(ow * g.sw - g.pw + g.kw, g.W);
-            int win = h0 * g.W + w0;
-            float mx = -INFINITY;
-            for (int ih = h0; ih < h1; ++ih)
-                for (int iw = w0; iw < w1; ++iw) {
-                    const float v = xp[((long)ih * g.W + iw) * c];
-                    if (v > mx || v != v) {
-                        mx = v;
-                        win = ih * g.W + iw;
-                    }
-                }
-            if (win == p) grad += gp[((long)oh * g.OW + ow) * c];
-        }
-    }
-    g_in[i] = grad;
+    r_in[i] = GRAD ? grad : xp[(long)p * c] * grad;
 }
 
 __global__ void resnet_relu_grad_kernel(const float* __restrict__ g, const float* __restrict__ act, const int32_t* __restrict__ map2img,
@@ -215,6 +184,31 @@ static bool pool_geom_ok(int h, int w, int oh, int ow, int kh, int kw, int sh, i
 }
 
 static inline unsigned blocks_of(long total) { return (unsigned)ceil_div(total, 256); }
+
+// what lrpx_resnet_add_split and lrpx_resnet_relu_grad refuse alike; `fn` is the entry's name in the messages
+static int per_map_ok(const char* fn, int n_maps, int n_img, long per_map, const int32_t* map2img) {
+    LRPX_REQUIRE(n_maps > 0 && n_img > 0 && per_map > 0 && n_maps * per_map < (1L << 38), "%s: bad sizes", fn);
+    LRPX_REQUIRE(map2img || n_maps == n_img, "%s: without map2img there is one map per image", fn);
+    return LRPX_OK;
+}
+
+// the two pool gathers (`what` = "rel" | "grad"): refusals, pointer check, launch
+template <bool GRAD>
+static int maxpool_gather(const char* what, const float* x, const float* r_out, const int32_t* map2img, float* r_in, int n_maps, int n_img,
+                          int h, int w, int oh, int ow, int c, int kh, int kw, int sh, int sw, int ph, int pw, void* stream) {
+    LRPX_REQUIRE(x && r_out && r_in, "resnet_maxpool_%s: null pointer", what);
+    LRPX_REQUIRE(n_maps > 0 && n_img > 0 && c > 0 && pool_geom_ok(h, w, oh, ow, kh, kw, sh, sw, ph, pw),
+                 "resnet_maxpool_%s: bad sizes or window (maps %d images %d c %d, %dx%d -> %dx%d, kernel %dx%d stride %dx%d padding %dx%d)",
+                 what, n_maps, n_img, c, h, w, oh, ow, kh, kw, sh, sw, ph, pw);
+    LRPX_REQUIRE(map2img || n_maps == n_img, "resnet_maxpool_%s: without map2img there is one map per image", what);
+    LRPX_REQUIRE((long)n_maps * h * w * c < (1L << 38), "resnet_maxpool_%s: tensor too large", what);
+    LRPX_CHECK_PTRS(GRAD ? "lrpx_resnet_maxpool_grad" : "lrpx_resnet_maxpool_rel", {x, "x"}, {r_out, GRAD ? "g_out" : "r_out"},
+                    {map2img, "map2img"}, {r_in, GRAD ? "g_in" : "r_in"});
+    const RnPoolGeom g = {h, w, oh, ow, kh, kw, sh, sw, ph, pw};
+    hipLaunchKernelGGL(resnet_maxpool_gather_kernel<GRAD>, dim3(blocks_of((long)n_maps * h * w * c)), dim3(256), 0, (hipStream_t)stream, x,
+                       r_out, map2img, r_in, (long)n_maps, c, g);
+    return check_launch(GRAD ? "resnet_maxpool_grad" : "resnet_maxpool_rel");
+}
 
 }  // namespace lrpx
 
@@ -263,24 +257,13 @@ int lrpx_resnet_maxpool_fwd(const float* x, float* y, int n, int h, int w, int o
 
 int lrpx_resnet_maxpool_rel(const float* x, const float* r_out, const int32_t* map2img, float* r_in, int n_maps, int n_img, int h, int w,
                             int oh, int ow, int c, int kh, int kw, int sh, int sw, int ph, int pw, void* stream) {
-    LRPX_REQUIRE(x && r_out && r_in, "resnet_maxpool_rel: null pointer");
-    LRPX_REQUIRE(n_maps > 0 && n_img > 0 && c > 0 && pool_geom_ok(h, w, oh, ow, kh, kw, sh, sw, ph, pw),
-                 "resnet_maxpool_rel: bad sizes or window (maps %d images %d c %d, %dx%d -> %dx%d, kernel %dx%d stride %dx%d padding %dx%d)",
-                 n_maps, n_img, c, h, w, oh, ow, kh, kw, sh, sw, ph, pw);
-    LRPX_REQUIRE(map2img || n_maps == n_img, "resnet_maxpool_rel: without map2img there is one map per image");
-    LRPX_REQUIRE((long)n_maps * h * w * c < (1L << 38), "resnet_maxpool_rel: tensor too large");
-    LRPX_CHECK_PTRS("lrpx_resnet_maxpool_rel", {x, "x"}, {r_out, "r_out"}, {map2img, "map2img"}, {r_in, "r_in"});
-    const RnPoolGeom g = {h, w, oh, ow, kh, kw, sh, sw, ph, pw};
-    hipLaunchKernelGGL(resnet_maxpool_rel_kernel, dim3(blocks_of((long)n_maps * h * w * c)), dim3(256), 0, (hipStream_t)stream, x, r_out,
-                       map2img, r_in, (long)n_maps, c, g);
-    return check_launch("resnet_maxpool_rel");
+    return maxpool_gather<false>("rel", x, r_out, map2img, r_in, n_maps, n_img, h, w, oh, ow, c, kh, kw, sh, sw, ph, pw, stream);
 }
 
 int lrpx_resnet_add_split(const float* r, const float* c1, const float* c2, const int32_t* map2img, float* r1, float* r2, int n_maps,
                           int n_img, long per_map, void* stream) {
     LRPX_REQUIRE(r && c1 && c2 && r1 && r2, "resnet_add_split: null pointer");
-    LRPX_REQUIRE(n_maps > 0 && n_img > 0 && per_map > 0 && n_maps * per_map < (1L << 38), "resnet_add_split: bad sizes");
-    LRPX_REQUIRE(map2img || n_maps == n_img, "resnet_add_split: without map2img there is one map per image");
+    LRPX_TRY(per_map_ok("resnet_add_split", n_maps, n_img, per_map, map2img));
     LRPX_CHECK_PTRS("lrpx_resnet_add_split", {r, "r"}, {c1, "c1"}, {c2, "c2"}, {map2img, "map2img"}, {r1, "r1"}, {r2, "r2"});
     hipLaunchKernelGGL(resnet_add_split_kernel, dim3(blocks_of(n_maps * per_map)), dim3(256), 0, (hipStream_t)stream, r, c1, c2, map2img, r1,
                        r2, (long)n_maps, per_map);
@@ -290,8 +273,7 @@ int lrpx_resnet_add_split(const float* r, const float* c1, const float* c2, cons
 int lrpx_resnet_relu_grad(const float* g, const float* act, const int32_t* map2img, float* out, int n_maps, int n_img, long per_map,
                           int clamp, void* stream) {
     LRPX_REQUIRE(g && act && out, "resnet_relu_grad: null pointer");
-    LRPX_REQUIRE(n_maps > 0 && n_img > 0 && per_map > 0 && n_maps * per_map < (1L << 38), "resnet_relu_grad: bad sizes");
-    LRPX_REQUIRE(map2img || n_maps == n_img, "resnet_relu_grad: without map2img there is one map per image");
+    LRPX_TRY(per_map_ok("resnet_relu_grad", n_maps, n_img, per_map, map2img));
     LRPX_REQUIRE(clamp == 0 || clamp == 1, "resnet_relu_grad: clamp is 0 or 1 (%d)", clamp);
     LRPX_CHECK_PTRS("lrpx_resnet_relu_grad", {g, "g"}, {act, "act"}, {map2img, "map2img"}, {out, "out"});
     hipLaunchKernelGGL(resnet_relu_grad_kernel, dim3(blocks_of(n_maps * per_map)), dim3(256), 0, (hipStream_t)stream, g, act, map2img, out,
@@ -301,17 +283,7 @@ int lrpx_resnet_relu_grad(const float* g, const float* act, const int32_t* map2i
 
 int lrpx_resnet_maxpool_grad(const float* x, const float* g_out, const int32_t* map2img, float* g_in, int n_maps, int n_img, int h, int w,
                              int oh, int ow, int c, int kh, int kw, int sh, int sw, int ph, int pw, void* stream) {
-    LRPX_REQUIRE(x && g_out && g_in, "resnet_maxpool_grad: null pointer");
-    LRPX_REQUIRE(n_maps > 0 && n_img > 0 && c > 0 && pool_geom_ok(h, w, oh, ow, kh, kw, sh, sw, ph, pw),
-                 "resnet_maxpool_grad: bad sizes or window (maps %d images %d c %d, %dx%d -> %dx%d, kernel %dx%d stride %dx%d padding %dx%d)",
-                 n_maps, n_img, c, h, w, oh, ow, kh, kw, sh, sw, ph, pw);
-    LRPX_REQUIRE(map2img || n_maps == n_img, "resnet_maxpool_grad: without map2img there is one map per image");
-    LRPX_REQUIRE((long)n_maps * h * w * c < (1L << 38), "resnet_maxpool_grad: tensor too large");
-    LRPX_CHECK_PTRS("lrpx_resnet_maxpool_grad", {x, "x"}, {g_out, "g_out"}, {map2img, "map2img"}, {g_in, "g_in"});
-    const RnPoolGeom g = {h, w, oh, ow, kh, kw, sh, sw, ph, pw};
-    hipLaunchKernelGGL(resnet_maxpool_grad_kernel, dim3(blocks_of((long)n_maps * h * w * c)), dim3(256), 0, (hipStream_t)stream, x, g_out,
-                       map2img, g_in, (long)n_maps, c, g);
-    return check_launch("resnet_maxpool_grad");
+    return maxpool_gather<true>("grad", x, g_out, map2img, g_in, n_maps, n_img, h, w, oh, ow, c, kh, kw, sh, sw, ph, pw, stream);
 }
 
 int lrpx_resnet_stem_fold(const float* r_split, float* out, int n_maps, int cin, int half, int ld, long pix, void* stream) {

@@ -722,6 +722,35 @@ def check_map2img(map2img, n_maps, n_img):
     return map2img.contiguous()
 
 
+def _conv_geom_desc(fn, direction, inp, wpacked, n, hw, ohw, geom, k, n_oc, k_inp, kname, operands, bias, x, q, addend, map2img, n_img, out,
+                    validate):
+    """What the `conv_geom_ex` / `_ab` / `_grad` wrappers share, each refusal once under the wrapper's name `fn`: the shapes of the
+    transposed direction's per-image `operands` = (name, tensor, kind, required), kind 'x' (n_img, H W, n_oc) | 'q' (n_img, OH OW, k_inp)
+    | 'k' (k_inp,), of the addend and of the input (k_inp channels, named `kname`; k is the contraction's length), `check_map2img`
+    where asked, `out` allocated or refused.  -> (the base ConvGeomExDesc, out)."""
+    bwd = direction == _lib.GEOM_BWD
+    pix_in, pix_out = (ohw[0] * ohw[1], hw[0] * hw[1]) if bwd else (hw[0] * hw[1], ohw[0] * ohw[1])
+    if bwd:
+        n_img = n if n_img is None else n_img
+        for name, t, kind, required in operands:
+            want = (n_img, pix_out, n_oc) if kind == "x" else (n_img, pix_in, k_inp) if kind == "q" else (k_inp,)
+            if (required if t is None else tuple(t.shape) != want):
+                raise ValueError("{}: {} must be {}".format(fn, name, {"x": "(n_img, H W, n_oc)", "q": "(n_img, OH OW, {})".format(kname),
+                                                                          "k": "({},)".format(kname)}[kind]))
+        if addend is not None and tuple(addend.shape) != (n, pix_out, n_oc):
+            raise ValueError("{}: addend must have the output's shape".format(fn))
+        if map2img is not None and validate:
+            map2img = check_map2img(map2img, n, n_img)
+    if inp.numel() != n * pix_in * k_inp:
+        raise ValueError("{}: the input must hold n x pixels x {} = {} x {} x {} floats".format(fn, kname, n, pix_in, k_inp))
+    if out is None:
+        out = torch.empty(n, pix_out, n_oc, dtype=torch.float32, device=inp.device)
+    elif out.numel() != n * pix_out * n_oc:
+        raise ValueError("{}: the output must hold n x pixels x n_oc floats".format(fn))
+    return _lib.ConvGeomExDesc(ptr(_dev(inp)), ptr(_dev(wpacked)), ptr(_dev(bias)), ptr(_dev(x)), ptr(_dev(q)), ptr(_dev(addend)),
+                               ptr(_dev(map2img)), ptr(_dev(out)), direction, n, n_img or 0, hw[0], hw[1], ohw[0], ohw[1], *geom, k, n_oc), out
+
+
 def conv_geom_ex(inp, wpacked, direction, n, hw, ohw, geom, k, n_oc, bias=None, x=None, q=None, addend=None, map2img=None, n_img=None,
                  out=None, validate=True, b6=False):
     """`lrpx_conv_geom_ex` (csrc/conv_geom.hip; b6: `lrpx_conv_geom_ex_b6`, csrc/conv_geom_b6.hip, the exact bf16-split arithmetic of
@@ -729,25 +758,8 @@ def conv_geom_ex(inp, wpacked, direction, n, hw, ohw, geom, k, n_oc, bias=None, 
     (n, OH OW, n_oc) (+ bias).  GEOM_BWD: inp (n maps, OH OW, k) -> out (n, H W, n_oc) = x[img] * convT(inp * q[img]) + addend with
     img = map2img[m] (None: identity); x (n_img, H W, n_oc), q (n_img, OH OW, k), addend like out.  validate: check map2img on the host
     first (`check_map2img`; a caller that already has passes False)."""
-    if direction == _lib.GEOM_BWD:
-        n_img = n if n_img is None else n_img
-        if x is None or tuple(x.shape) != (n_img, hw[0] * hw[1], n_oc):
-            raise ValueError("conv_geom_ex: x must be (n_img, H W, n_oc)")
-        if q is not None and tuple(q.shape) != (n_img, ohw[0] * ohw[1], k):
-            raise ValueError("conv_geom_ex: q must be (n_img, OH OW, k)")
-        if addend is not None and tuple(addend.shape) != (n, hw[0] * hw[1], n_oc):
-            raise ValueError("conv_geom_ex: addend must have the output's shape")
-        if map2img is not None and validate:
-            map2img = check_map2img(map2img, n, n_img)
-    pix_in, pix_out = (ohw[0] * ohw[1], hw[0] * hw[1]) if direction == _lib.GEOM_BWD else (hw[0] * hw[1], ohw[0] * ohw[1])
-    if inp.numel() != n * pix_in * k:
-        raise ValueError("conv_geom_ex: the input must hold n x pixels x k = {} x {} x {} floats".format(n, pix_in, k))
-    if out is None:
-        out = torch.empty(n, pix_out, n_oc, dtype=torch.float32, device=inp.device)
-    elif out.numel() != n * pix_out * n_oc:
-        raise ValueError("conv_geom_ex: the output must hold n x pixels x n_oc floats")
-    d = _lib.ConvGeomExDesc(ptr(_dev(inp)), ptr(_dev(wpacked)), ptr(_dev(bias)), ptr(_dev(x)), ptr(_dev(q)), ptr(_dev(addend)),
-                            ptr(_dev(map2img)), ptr(_dev(out)), direction, n, n_img or 0, hw[0], hw[1], ohw[0], ohw[1], *geom, k, n_oc)
+    d, out = _conv_geom_desc("conv_geom_ex", direction, inp, wpacked, n, hw, ohw, geom, k, n_oc, k, "k",
+                             (("x", x, "x", True), ("q", q, "q", False)), bias, x, q, addend, map2img, n_img, out, validate)
     if b6:
         _count("conv_geom_ex_b6", direction)
         check(_lib.load().lrpx_conv_geom_ex_b6(C.byref(d), stream_ptr()))
@@ -764,25 +776,9 @@ def conv_geom_ab(inp, wpacked, n, hw, ohw, geom, kr, n_oc, x, q, q2=None, scale=
     x[img] * (convT((inp q[img]) scale, W+) + convT((inp q2[img]) scale2, W-)) + addend; q / q2 (n_img, OH OW, kr).  wpacked: the
     transposed pack of the rows [W+ ; W-] (2 kr of them) - or, with q2 None (beta == 0), of W+ alone: the contraction then runs over
     kr only.  LAUNCHES counts the two under 'conv_geom_ab_dual' and 'conv_geom_ab' (b6: + '_b6')."""
-    n_img = n if n_img is None else n_img
-    if x is None or tuple(x.shape) != (n_img, hw[0] * hw[1], n_oc):
-        raise ValueError("conv_geom_ab: x must be (n_img, H W, n_oc)")
-    for name, t in (("q", q), ("q2", q2)):
-        if (t is None and name == "q") or (t is not None and tuple(t.shape) != (n_img, ohw[0] * ohw[1], kr)):
-            raise ValueError("conv_geom_ab: {} must be (n_img, OH OW, kr)".format(name))
-    if addend is not None and tuple(addend.shape) != (n, hw[0] * hw[1], n_oc):
-        raise ValueError("conv_geom_ab: addend must have the output's shape")
-    if map2img is not None and validate:
-        map2img = check_map2img(map2img, n, n_img)
-    if inp.numel() != n * ohw[0] * ohw[1] * kr:
-        raise ValueError("conv_geom_ab: the input must hold n x pixels x kr = {} x {} x {} floats".format(n, ohw[0] * ohw[1], kr))
-    if out is None:
-        out = torch.empty(n, hw[0] * hw[1], n_oc, dtype=torch.float32, device=inp.device)
-    elif out.numel() != n * hw[0] * hw[1] * n_oc:
-        raise ValueError("conv_geom_ab: the output must hold n x pixels x n_oc floats")
-    k = kr if q2 is None else 2 * kr
-    base = _lib.ConvGeomExDesc(ptr(_dev(inp)), ptr(_dev(wpacked)), None, ptr(_dev(x)), ptr(_dev(q)), ptr(_dev(addend)), ptr(_dev(map2img)),
-                               ptr(_dev(out)), _lib.GEOM_BWD, n, n_img, hw[0], hw[1], ohw[0], ohw[1], *geom, k, n_oc)
+    base, out = _conv_geom_desc("conv_geom_ab", _lib.GEOM_BWD, inp, wpacked, n, hw, ohw, geom, kr if q2 is None else 2 * kr, n_oc, kr, "kr",
+                                (("x", x, "x", True), ("q", q, "q", True), ("q2", q2, "q", False)), None, x, q, addend, map2img, n_img, out,
+                                validate)
     d = _lib.ConvGeomAbDesc(base, ptr(_dev(q2)), scale, scale2, kr)
     name = "conv_geom_ab" + ("" if q2 is None else "_dual") + ("_b6" if b6 else "")
     _count(name, _lib.GEOM_BWD)
@@ -797,23 +793,9 @@ def conv_geom_grad(inp, wpacked, n, hw, ohw, geom, k, n_oc, mask=None, scale=Non
     5.12).  inp (n maps, OH OW, k) -> out (n, H W, n_oc) = convT(scale * (mask[img] > 0 ? (clamp ? max(inp, 0) : inp) : 0), W) + addend
     with wpacked the transposed pack of the RAW weights; mask (n_img, OH OW, k), scale (k,), addend like out, each optional.
     LAUNCHES counts it under 'conv_geom_grad' (b6: 'conv_geom_grad_b6')."""
-    n_img = n if n_img is None else n_img
-    if mask is not None and tuple(mask.shape) != (n_img, ohw[0] * ohw[1], k):
-        raise ValueError("conv_geom_grad: mask must be (n_img, OH OW, k)")
-    if scale is not None and tuple(scale.shape) != (k,):
-        raise ValueError("conv_geom_grad: scale must be (k,)")
-    if addend is not None and tuple(addend.shape) != (n, hw[0] * hw[1], n_oc):
-        raise ValueError("conv_geom_grad: addend must have the output's shape")
-    if map2img is not None and validate:
-        map2img = check_map2img(map2img, n, n_img)
-    if inp.numel() != n * ohw[0] * ohw[1] * k:
-        raise ValueError("conv_geom_grad: the input must hold n x pixels x k = {} x {} x {} floats".format(n, ohw[0] * ohw[1], k))
-    if out is None:
-        out = torch.empty(n, hw[0] * hw[1], n_oc, dtype=torch.float32, device=inp.device)
-    elif out.numel() != n * hw[0] * hw[1] * n_oc:
-        raise ValueError("conv_geom_grad: the output must hold n x pixels x n_oc floats")
-    base = _lib.ConvGeomExDesc(ptr(_dev(inp)), ptr(_dev(wpacked)), None, None, None, ptr(_dev(addend)), ptr(_dev(map2img)), ptr(_dev(out)),
-                               _lib.GEOM_BWD, n, n_img, hw[0], hw[1], ohw[0], ohw[1], *geom, k, n_oc)
+    base, out = _conv_geom_desc("conv_geom_grad", _lib.GEOM_BWD, inp, wpacked, n, hw, ohw, geom, k, n_oc, k, "k",
+                                (("mask", mask, "q", False), ("scale", scale, "k", False)), None, None, None, addend, map2img, n_img, out,
+                                validate)
     d = _lib.ConvGeomGradDesc(base, ptr(_dev(mask)), ptr(_dev(scale)), 1 if clamp else 0)
     _count("conv_geom_grad_b6" if b6 else "conv_geom_grad", _lib.GEOM_BWD)
     lib = _lib.load()
@@ -1158,7 +1140,8 @@ class ResNetEncoder:
         self.cin = plan.convs[0]["cin"]
         self.c2 = 8                                   # the split image [x+ | x- | 0..] (lrpx_nchw_to_nhwc_posneg)
         self.packs = []
-        for cv in plan.convs:
+        relu = {0} | {blk[k] for blk in plan.blocks for k in ("conv1", "conv2")}       # the convs whose BatchNorm a ReLU follows
+        for i, cv in enumerate(plan.convs):
             wt = cv["module"].weight.detach().to(torch.float32)
             bn = cv["bn"]
             sd = torch.sqrt(bn.running_var.detach().float() + bn.eps)
@@ -1175,7 +1158,7 @@ class ResNetEncoder:
                 fwd = pack(torch.cat([torch.cat([wt, wt, pad], 1), zrow], 0), _lib.GEOM_FWD)
                 bwd = pack(zrow, _lib.GEOM_BWD)
                 k_in = self.c2
-            self.packs.append(dict(fwd=fwd, bwd=bwd, w=w, b=b, k_in=k_in, cout=cv["cout"], geom=cv["geom"]))
+            self.packs.append(dict(fwd=fwd, bwd=bwd, w=w, b=b, k_in=k_in, cout=cv["cout"], geom=cv["geom"], relu=i in relu))
         self._ab_packs = []                           # the general rule's packs, built at its first call; replicas share the list
         self._grad_packs = []                         # the gradient chain's raw-W transposed packs, likewise
         torch.cuda.current_stream().synchronize()
@@ -1284,66 +1267,100 @@ class ResNetEncoder:
         return x
 
     # ---- relevance ---------------------------------------------------------------------------------------------------------------------
-    def relevance(self, r_feat_nhwc, map2img=None, out=None, layer_ms=None):
-        """compute_lrp (LRPtools/lrp_wrapper.py:63-87) for n_maps maps: (n_maps, h w, C) relevance at the feature map -> (n_maps, cin, H, W);
-        map m runs on the trace of image map2img[m] (int32 on the device; None: n_maps == B, map m on image m).  No forward work: the
-        pass is one Add split and three or four transposed convs per block, the pool gather, the stem's transposed conv and the fold.
-        layer_ms: as in `forward`."""
+    def _map_args(self, fn, feat, name, map2img, out):
+        """The per-map arguments of the public pass `fn`, checked once, before anything is launched: -> (the tensor `name` at the feature
+        map, contiguous; map2img validated on the host, or None; out, allocated if None; n_maps).  ValueError / LrpxError otherwise."""
         if self.trace is None:
-            raise ValueError("ResNetEncoder.relevance: no trace - call forward() first")
+            raise ValueError("ResNetEncoder.{}: no trace - call forward() first".format(fn))
         B = self.n_img
-        t, dims = self.trace, self.dims
-        r = _dev(r_feat_nhwc)
+        r = _dev(feat)
         c_feat = self.packs[self.plan.blocks[-1]["conv3"]]["cout"]
         if r.dim() != 3 or tuple(r.shape[1:]) != (self.feat_hw[0] * self.feat_hw[1], c_feat) or r.dtype != torch.float32:
-            raise ValueError("ResNetEncoder.relevance: r_feat_nhwc must be float32 (n_maps, {}, {}), got {}".format(
-                self.feat_hw[0] * self.feat_hw[1], c_feat, tuple(r.shape)))
+            raise ValueError("ResNetEncoder.{}: {} must be float32 (n_maps, {}, {}), got {}".format(
+                fn, name, self.feat_hw[0] * self.feat_hw[1], c_feat, tuple(r.shape)))
         n_maps = r.shape[0]
         if n_maps == 0:
-            raise ValueError("ResNetEncoder.relevance: no maps")
+            raise ValueError("ResNetEncoder.{}: no maps".format(fn))
         if map2img is None:
             if n_maps != B:
-                raise ValueError("ResNetEncoder.relevance: without map2img there is one map per image of the trace ({} maps, {} images)"
-                                 .format(n_maps, B))
+                raise ValueError("ResNetEncoder.{}: without map2img there is one map per image of the trace ({} maps, {} images)"
+                                 .format(fn, n_maps, B))
         else:
             map2img = check_map2img(map2img, n_maps, B)
         H, W = self.shape[1], self.shape[2]
         if out is None:
             out = torch.empty(n_maps, self.cin, H, W, dtype=torch.float32, device=self.device)
         elif tuple(out.shape) != (n_maps, self.cin, H, W) or not out.is_contiguous():
-            raise ValueError("ResNetEncoder.relevance: out must be contiguous (n_maps, {}, {}, {})".format(self.cin, H, W))
-        r = r.contiguous()
+            raise ValueError("ResNetEncoder.{}: out must be contiguous (n_maps, {}, {}, {})".format(fn, self.cin, H, W))
+        return r.contiguous(), map2img, out, n_maps
+
+    def _walk(self, r, map2img, out, n_maps, layer_ms, head, convT, pool, stem_c, tail):
+        """One per-map pass down the trace, from `r` (n_maps, h w, C) at the feature map to `out`: per block, last first, the head, then
+        conv3 -> ws a, conv2 -> ws b, the downsample (if any) -> ws a, conv1 with the shortcut's term as addend -> ws r[cur] (ping-pong);
+        then the pool step -> ws a, the stem's conv -> ws b on `stem_c` channels, and the tail into `out`.  What a pass brings:
+          head(bi, r, ws) -> (conv3's input, the shortcut's term) at block bi's output, in ws r1 / r2
+          convT(i, inp, x, addend, o, n_oc): the transposed conv of conv i, o = f(inp, x) + addend on n_oc channels, x the trace's
+            tensor at the conv's input
+          pool: `resnet_maxpool_rel` or `resnet_maxpool_grad`;  tail(rs, out): the stem conv's result into the NCHW result
+        layer_ms: as in `forward`, around every conv."""
+        t, dims, blocks, B = self.trace, self.dims, self.plan.blocks, self.n_img
         ws = self._workspace(n_maps)
 
-        def convT(i, r_out, x, addend, dst):
-            pk = self.packs[i]
-            ev = _events(layer_ms)
-            hw, ohw = dims[i]
-            n_oc = x.shape[2]
+        def conv(i, inp, x, addend, dst, n_oc):
+            hw = dims[i][0]
             o = dst[: n_maps * hw[0] * hw[1] * n_oc].view(n_maps, hw[0] * hw[1], n_oc)
-            conv_geom_ex(r_out, pk["bwd"], _lib.GEOM_BWD, n_maps, hw, ohw, pk["geom"], pk["cout"], n_oc, x=x, q=t["q"][i], addend=addend,
-                         map2img=map2img, n_img=B, out=o, validate=False, b6=self.b6)
-            _events_done(ev, layer_ms, self.plan.convs[i]["name"])
+            if layer_ms is None:
+                convT(i, inp, x, addend, o, n_oc)
+            else:
+                ev = _events(layer_ms)
+                convT(i, inp, x, addend, o, n_oc)
+                _events_done(ev, layer_ms, self.plan.convs[i]["name"])
             return o
         cur = 0
-        for bi in range(len(self.plan.blocks) - 1, -1, -1):
-            blk = self.plan.blocks[bi]
+        for bi in range(len(blocks) - 1, -1, -1):
+            blk = blocks[bi]
             x = t["out"][bi - 1] if bi > 0 else t["pool"]
+            x2, x1 = t["act"][blk["conv2"]], t["act"][blk["conv1"]]
+            r1, r2 = head(bi, r, ws)
+            ra = conv(blk["conv3"], r1, x2, None, ws["a"], x2.shape[2])
+            rb = conv(blk["conv2"], ra, x1, None, ws["b"], x1.shape[2])
+            if blk["downsample"] is not None:
+                r2 = conv(blk["downsample"], r2, x, None, ws["a"], x.shape[2])
+            r = conv(blk["conv1"], rb, x, r2, ws["r"][cur], x.shape[2])
+            cur = 1 - cur
+        a0 = t["act"][0]
+        rp = ws["a"][: n_maps * a0[0].numel()].view(n_maps, *a0.shape[1:])
+        pool(a0, r, map2img, rp, n_maps, B, self.pool_dims[0], self.pool_dims[1], self.packs[0]["cout"], self.plan.pool)
+        tail(conv(0, rp, t["xs"], None, ws["b"], stem_c), out)
+        return out
+
+    def _walk_lrp(self, r, map2img, out, n_maps, layer_ms, convT):
+        """`_walk` with the LRP rules around the convs: the Add split, the pool rule, the stem's split image and its fold"""
+        t, B = self.trace, self.n_img
+
+        def head(bi, r, ws):
             r1 = ws["r1"][: r.numel()].view(r.shape)
             r2 = ws["r2"][: r.numel()].view(r.shape)
             resnet_add_split(r, t["c1"][bi], t["c2"][bi], map2img, r1, r2, n_maps, B)
-            ra = convT(blk["conv3"], r1, t["act"][blk["conv2"]], None, ws["a"])
-            rb = convT(blk["conv2"], ra, t["act"][blk["conv1"]], None, ws["b"])
-            if blk["downsample"] is not None:
-                r2 = convT(blk["downsample"], r2, x, None, ws["a"])
-            r = convT(blk["conv1"], rb, x, r2, ws["r"][cur])
-            cur = 1 - cur
-        pk0 = self.packs[0]
-        rp = ws["a"][: n_maps * t["act"][0][0].numel()].view(n_maps, *t["act"][0].shape[1:])
-        resnet_maxpool_rel(t["act"][0], r, map2img, rp, n_maps, B, self.pool_dims[0], self.pool_dims[1], pk0["cout"], self.plan.pool)
-        rs = convT(0, rp, t["xs"], None, ws["b"])
-        resnet_stem_fold(rs, out, n_maps, self.cin, self.cin, self.c2, H * W)
-        return out
+            return r1, r2
+        pix = self.shape[1] * self.shape[2]
+        return self._walk(r, map2img, out, n_maps, layer_ms, head, convT, resnet_maxpool_rel, self.c2,
+                          lambda rs, o: resnet_stem_fold(rs, o, n_maps, self.cin, self.cin, self.c2, pix))
+
+    def relevance(self, r_feat_nhwc, map2img=None, out=None, layer_ms=None):
+        """compute_lrp (LRPtools/lrp_wrapper.py:63-87) for n_maps maps: (n_maps, h w, C) relevance at the feature map -> (n_maps, cin, H, W);
+        map m runs on the trace of image map2img[m] (int32 on the device; None: n_maps == B, map m on image m).  No forward work: the
+        pass is one Add split and three or four transposed convs per block, the pool gather, the stem's transposed conv and the fold.
+        layer_ms: as in `forward`."""
+        r, map2img, out, n_maps = self._map_args("relevance", r_feat_nhwc, "r_feat_nhwc", map2img, out)
+        t, dims, packs, B, b6 = self.trace, self.dims, self.packs, self.n_img, self.b6
+
+        def convT(i, r_out, x, addend, o, n_oc):
+            pk = packs[i]
+            hw, ohw = dims[i]
+            conv_geom_ex(r_out, pk["bwd"], _lib.GEOM_BWD, n_maps, hw, ohw, pk["geom"], pk["cout"], n_oc, x=x, q=t["q"][i], addend=addend,
+                         map2img=map2img, n_img=B, out=o, validate=False, b6=b6)
+        return self._walk_lrp(r, map2img, out, n_maps, layer_ms, convT)
 
     # ---- the general alpha-beta rule (DESIGN.md 5.10) -------------------------------------------------------------------------------
     def _ab_state(self):
@@ -1401,64 +1418,19 @@ class ResNetEncoder:
         alpha, beta = float(alpha), float(beta)
         if not (alpha == alpha and beta == beta and abs(alpha) != float("inf") and abs(beta) != float("inf")):
             raise ValueError("ResNetEncoder.relevance_alpha_beta: alpha and beta must be finite")
-        if self.trace is None:
-            raise ValueError("ResNetEncoder.relevance_alpha_beta: no trace - call forward() first")
-        B = self.n_img
-        t, dims = self.trace, self.dims
-        r = _dev(r_feat_nhwc)
-        c_feat = self.packs[self.plan.blocks[-1]["conv3"]]["cout"]
-        if r.dim() != 3 or tuple(r.shape[1:]) != (self.feat_hw[0] * self.feat_hw[1], c_feat) or r.dtype != torch.float32:
-            raise ValueError("ResNetEncoder.relevance_alpha_beta: r_feat_nhwc must be float32 (n_maps, {}, {}), got {}".format(
-                self.feat_hw[0] * self.feat_hw[1], c_feat, tuple(r.shape)))
-        n_maps = r.shape[0]
-        if n_maps == 0:
-            raise ValueError("ResNetEncoder.relevance_alpha_beta: no maps")
-        if map2img is None:
-            if n_maps != B:
-                raise ValueError("ResNetEncoder.relevance_alpha_beta: without map2img there is one map per image of the trace ({} maps, "
-                                 "{} images)".format(n_maps, B))
-        else:
-            map2img = check_map2img(map2img, n_maps, B)
-        H, W = self.shape[1], self.shape[2]
-        if out is None:
-            out = torch.empty(n_maps, self.cin, H, W, dtype=torch.float32, device=self.device)
-        elif tuple(out.shape) != (n_maps, self.cin, H, W) or not out.is_contiguous():
-            raise ValueError("ResNetEncoder.relevance_alpha_beta: out must be contiguous (n_maps, {}, {}, {})".format(self.cin, H, W))
-        r = r.contiguous()
+        r, map2img, out, n_maps = self._map_args("relevance_alpha_beta", r_feat_nhwc, "r_feat_nhwc", map2img, out)
         dual = beta != 0.
         qn = self._ab_coef() if dual else None
         ab = self._ab_packs
-        ws = self._workspace(n_maps)
+        t, dims, packs, B, b6 = self.trace, self.dims, self.packs, self.n_img, self.b6
 
-        def convT(i, r_out, x, addend, dst):
-            pk = self.packs[i]
-            ev = _events(layer_ms)
+        def convT(i, r_out, x, addend, o, n_oc):
+            pk = packs[i]
             hw, ohw = dims[i]
-            n_oc = x.shape[2]
-            o = dst[: n_maps * hw[0] * hw[1] * n_oc].view(n_maps, hw[0] * hw[1], n_oc)
             conv_geom_ab(r_out, ab[i]["bwd"] if dual else pk["bwd"], n_maps, hw, ohw, pk["geom"], pk["cout"], n_oc, x, t["q"][i],
                          q2=qn[i] if dual else None, scale=alpha, scale2=-beta if dual else 0., addend=addend, map2img=map2img, n_img=B,
-                         out=o, validate=False, b6=self.b6)
-            _events_done(ev, layer_ms, self.plan.convs[i]["name"])
-            return o
-        cur = 0
-        for bi in range(len(self.plan.blocks) - 1, -1, -1):
-            blk = self.plan.blocks[bi]
-            x = t["out"][bi - 1] if bi > 0 else t["pool"]
-            r1 = ws["r1"][: r.numel()].view(r.shape)
-            r2 = ws["r2"][: r.numel()].view(r.shape)
-            resnet_add_split(r, t["c1"][bi], t["c2"][bi], map2img, r1, r2, n_maps, B)
-            ra = convT(blk["conv3"], r1, t["act"][blk["conv2"]], None, ws["a"])
-            rb = convT(blk["conv2"], ra, t["act"][blk["conv1"]], None, ws["b"])
-            if blk["downsample"] is not None:
-                r2 = convT(blk["downsample"], r2, x, None, ws["a"])
-            r = convT(blk["conv1"], rb, x, r2, ws["r"][cur])
-            cur = 1 - cur
-        rp = ws["a"][: n_maps * t["act"][0][0].numel()].view(n_maps, *t["act"][0].shape[1:])
-        resnet_maxpool_rel(t["act"][0], r, map2img, rp, n_maps, B, self.pool_dims[0], self.pool_dims[1], self.packs[0]["cout"], self.plan.pool)
-        rs = convT(0, rp, t["xs"], None, ws["b"])
-        resnet_stem_fold(rs, out, n_maps, self.cin, self.cin, self.c2, H * W)
-        return out
+                         out=o, validate=False, b6=b6)
+        return self._walk_lrp(r, map2img, out, n_maps, layer_ms, convT)
 
     # ---- the gradient chain -----------------------------------------------------------------------------------------
     def _grad_state(self):
@@ -1488,62 +1460,26 @@ class ResNetEncoder:
         return self._grad_chain("guided_backprop", d_feat_nhwc, map2img, out, relus, layer_ms)
 
     def _grad_chain(self, fn, d_feat_nhwc, map2img, out, relus, layer_ms):
-        if self.trace is None:
-            raise ValueError("ResNetEncoder.{}: no trace - call forward() first".format(fn))
-        B = self.n_img
-        t, dims = self.trace, self.dims
-        g = _dev(d_feat_nhwc)
-        c_feat = self.packs[self.plan.blocks[-1]["conv3"]]["cout"]
-        if g.dim() != 3 or tuple(g.shape[1:]) != (self.feat_hw[0] * self.feat_hw[1], c_feat) or g.dtype != torch.float32:
-            raise ValueError("ResNetEncoder.{}: d_feat_nhwc must be float32 (n_maps, {}, {}), got {}".format(
-                fn, self.feat_hw[0] * self.feat_hw[1], c_feat, tuple(g.shape)))
-        n_maps = g.shape[0]
-        if n_maps == 0:
-            raise ValueError("ResNetEncoder.{}: no maps".format(fn))
-        if map2img is None:
-            if n_maps != B:
-                raise ValueError("ResNetEncoder.{}: without map2img there is one map per image of the trace ({} maps, {} images)"
-                                 .format(fn, n_maps, B))
-        else:
-            map2img = check_map2img(map2img, n_maps, B)
-        H, W = self.shape[1], self.shape[2]
-        if out is None:
-            out = torch.empty(n_maps, self.cin, H, W, dtype=torch.float32, device=self.device)
-        elif tuple(out.shape) != (n_maps, self.cin, H, W) or not out.is_contiguous():
-            raise ValueError("ResNetEncoder.{}: out must be contiguous (n_maps, {}, {}, {})".format(fn, self.cin, H, W))
-        g = g.contiguous()
+        g, map2img, out, n_maps = self._map_args(fn, d_feat_nhwc, "d_feat_nhwc", map2img, out)
         gp = self._grad_state()
-        ws = self._workspace(n_maps)
+        t, dims, packs, B, b6 = self.trace, self.dims, self.packs, self.n_img, self.b6
         clamp_all, clamp_stem = relus == "all", relus is not None
 
-        def convT(i, g_out, n_oc, mask, clamp, addend, dst):
-            pk = self.packs[i]
-            ev = _events(layer_ms)
-            hw, ohw = dims[i]
-            o = dst[: n_maps * hw[0] * hw[1] * n_oc].view(n_maps, hw[0] * hw[1], n_oc)
-            conv_geom_grad(g_out, gp[i], n_maps, hw, ohw, pk["geom"], pk["cout"], n_oc, mask=mask, scale=pk["w"], clamp=clamp,
-                           addend=addend, map2img=map2img, n_img=B, out=o, validate=False, b6=self.b6)
-            _events_done(ev, layer_ms, self.plan.convs[i]["name"])
-            return o
-        cur = 0
-        for bi in range(len(self.plan.blocks) - 1, -1, -1):
-            blk = self.plan.blocks[bi]
-            c_in = (t["out"][bi - 1] if bi > 0 else t["pool"]).shape[2]
-            g0 = ws["r1"][: g.numel()].view(g.shape)                   # the gradient at the Add's sum
+        def head(bi, g, ws):
+            g0 = ws["r1"][: g.numel()].view(g.shape)                   # the gradient at the Add's sum: both branches take it
             resnet_relu_grad(g, t["out"][bi], map2img, g0, n_maps, B, clamp_all)
-            ga = convT(blk["conv3"], g0, self.packs[blk["conv2"]]["cout"], None, False, None, ws["a"])
-            gb = convT(blk["conv2"], ga, self.packs[blk["conv1"]]["cout"], t["act"][blk["conv2"]], clamp_all, None, ws["b"])
-            short = g0
-            if blk["downsample"] is not None:
-                short = convT(blk["downsample"], g0, c_in, None, False, None, ws["a"])
-            g = convT(blk["conv1"], gb, c_in, t["act"][blk["conv1"]], clamp_all, short, ws["r"][cur])
-            cur = 1 - cur
-        c0 = self.packs[0]["cout"]
-        gs = ws["a"][: n_maps * t["act"][0][0].numel()].view(n_maps, *t["act"][0].shape[1:])
-        resnet_maxpool_grad(t["act"][0], g, map2img, gs, n_maps, B, self.pool_dims[0], self.pool_dims[1], c0, self.plan.pool)
-        gi = convT(0, gs, self.cin, t["act"][0], clamp_stem, None, ws["b"])
-        check(_lib.load().lrpx_nhwc_to_nchw(ptr(gi), ptr(out), n_maps, self.cin, H * W, self.cin, stream_ptr()))
-        return out
+            return g0, g0
+
+        def convT(i, g_out, x, addend, o, n_oc):
+            pk = packs[i]
+            hw, ohw = dims[i]
+            relu = pk["relu"]                                          # the ReLU behind conv i: its mask, and guided backprop's clamp
+            conv_geom_grad(g_out, gp[i], n_maps, hw, ohw, pk["geom"], pk["cout"], n_oc, mask=t["act"][i] if relu else None,
+                           scale=pk["w"], clamp=relu and (clamp_stem if i == 0 else clamp_all), addend=addend, map2img=map2img, n_img=B,
+                           out=o, validate=False, b6=b6)
+        pix = self.shape[1] * self.shape[2]
+        return self._walk(g, map2img, out, n_maps, layer_ms, head, convT, resnet_maxpool_grad, self.cin,
+                          lambda gi, o: check(_lib.load().lrpx_nhwc_to_nchw(ptr(gi), ptr(o), n_maps, self.cin, pix, self.cin, stream_ptr())))
 
     def _workspace(self, n_maps):
         """per-map scratch, sized once per (trace shape, n_maps): r1 / r2 of the Add split, two chain buffers, two block-input buffers"""
