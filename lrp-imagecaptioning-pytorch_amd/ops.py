@@ -231,8 +231,9 @@ def conv_geom_pack_bf16x3(w, direction):
 def conv_geom(inp, wpacked, direction, n, hw, ohw, geom, k, n_oc, bias=None, x=None, out=None):
     """The runtime-geometry conv engine (csrc/conv_geom.hip), NHWC fp32.  hw = (H, W) the conv's input map, ohw = (OH, OW) its
     output map, geom = (kh, kw, sh, sw, ph, pw).  GEOM_FWD: inp (n, H W, k) -> out (n, OH OW, n_oc) (+ bias);
-    GEOM_BWD: inp (n, OH OW, k) -> out (n, H W, n_oc) = x * convT(inp)."""
-    pix = hw[0] * hw[1] if direction == _lib.GEOM_BWD else ohw[0] * ohw[1]
+    GEOM_BWD: inp (n, OH OW, k) -> out (n, H W, n_oc) = x * convT(inp).  LAUNCHES counts it under 'conv_geom'."""
+    _count("conv_geom", direction)
+    pix =hw[0] * hw[1] if direction == _lib.GEOM_BWD else ohw[0] * ohw[1]
     if out is None:
         out = torch.empty(n, pix, n_oc, dtype=torch.float32, device=inp.device)
     d = _lib.ConvGeomDesc(ptr(_dev(inp)), ptr(_dev(wpacked)), ptr(_dev(bias)), ptr(_dev(x)), ptr(_dev(out)), direction,
