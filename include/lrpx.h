@@ -96,8 +96,11 @@ int lrpx_pack_weights_f16f8(const float* w, int cout, int cin, int mode, void* p
 size_t lrpx_packed_wino_b6_bytes(int n_oc, int k);
 int lrpx_pack_weights_wino_b6(const float* w, int cout, int cin, int mode, void* packed, void* stream);
 /* which bf16x6 REL_MUL convs with wpacked_wino run on the Winograd kernel: bit 0 = 56 x 56, bit 1 = 28 x 28, bit 2 = 14 x 14 maps.
- * Process-wide; initial value from LRPX_B6_WINO (default 7: all three).  bits < 0 only queries.  Returns the previous value.  0 = the direct
- * kernels, bit for bit what the library computed before the Winograd kernel existed */
+ * Bit 3 (8) = the Winograd kernel stages its patches the way it always did: every thread fetches all four columns of its patch.  Without the
+ * bit a thread fetches its tile's own two columns and takes the outer two from the neighbouring lanes of its wave (column sharing): the same
+ * bits, fewer bytes through the vector-memory path, measured NOT faster and kept for A/B.
+ * Process-wide; initial value from LRPX_B6_WINO (default 15: all three map sizes, own-fetch staging).  bits < 0 only queries.  Returns the previous
+ * value.  0 = the direct kernels, bit for bit what the library computed before the Winograd kernel existed */
 int lrpx_set_b6_wino(int bits);
 /* K-chunk used by lrpx_conv_mfma for a given image width / taps / input channels */
 int lrpx_conv_kc(int hw, int taps, int cin);

@@ -118,8 +118,9 @@ struct Switches {
     int b6_fwd_ksplit56; // LRPX_B6_FWD_KSPLIT56 (default 2): ... of the 56x56 layers
     int b6_wide;         // LRPX_B6_WIDE (bit mask): 8-wave conv-mode-1 relevance kernels for 56/28 (1), 14 (2), pooled-input 56/28 (4)
     int b6_rel_ksplit14; // LRPX_B6_REL_KSPLIT14 (default 2; 1 = unsplit, 4 built): K ranges per tile of the 14x14 RELEVANCE layers of conv mode 1 (partial sums + rel_mul_finish)
-    int b6_wino;         // LRPX_B6_WINO (bit mask, default 7): conv-mode-1 relevance convs that are not under a pool on the Winograd F(2x2,3x3) kernel
-                         // (conv_wino_b6.h) at 56 x 56 (1), 28 x 28 (2), 14 x 14 (4); needs lrpx_conv_desc.wpacked_wino.  lrpx_set_b6_wino overrides it
+    int b6_wino;         // LRPX_B6_WINO (bit mask, default 15): conv-mode-1 relevance convs that are not under a pool on the Winograd F(2x2,3x3) kernel
+                         // (conv_wino_b6.h) at 56 x 56 (1), 28 x 28 (2), 14 x 14 (4); needs lrpx_conv_desc.wpacked_wino.  lrpx_set_b6_wino overrides it.
+                         // 8: every staging thread fetches its whole patch (legacy staging); without it the outer columns come from the neighbouring lanes (same bits, not faster)
     int x6_legacy;       // LRPX_X6_LEGACY: conv mode 1 on round 1's flow (conv_bf16x6.h with EPI_REL + pool kernels) instead of the fused B6 kernels
 };
 const Switches& switches();      // (lrpx_core.hip)

@@ -37,7 +37,29 @@ __device__ __forceinline__ void wino_split8(const f32x4 q0, const f32x4 q1, bf16
     }
 }
 
-template <int HW>
+// x - y, x + y and fma(x, s, y) (s = +-1: y +- x, one rounding, the bits of the add) on the channel pairs of a quad: v_pk_add_f32 / v_pk_fma_f32
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x4 wino_sub(const f32x4 x, const f32x4 y) {
+    const f32x2 lo = __builtin_shufflevector(x, x, 0, 1) - __builtin_shufflevector(y, y, 0, 1);
+    const f32x2 hi = __builtin_shufflevector(x, x, 2, 3) - __builtin_shufflevector(y, y, 2, 3);
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3);
+}
+__device__ __forceinline__ f32x4 wino_add(const f32x4 x, const f32x4 y) {
+    const f32x2 lo = __builtin_shufflevector(x, x, 0, 1) + __builtin_shufflevector(y, y, 0, 1);
+    const f32x2 hi = __builtin_shufflevector(x, x, 2, 3) + __builtin_shufflevector(y, y, 2, 3);
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3);
+}
+__device__ __forceinline__ f32x4 wino_fma(const f32x4 x, const float s, const f32x4 y) {
+    const f32x2 ss = {s, s};
+    const f32x2 lo = __builtin_elementwise_fma(__builtin_shufflevector(x, x, 0, 1), ss, __builtin_shufflevector(y, y, 0, 1));
+    const f32x2 hi = __builtin_elementwise_fma(__builtin_shufflevector(x, x, 2, 3), ss, __builtin_shufflevector(y, y, 2, 3));
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3);
+}
+
+// SHARE: a staging thread fetches only its tile's own two patch columns and takes the two outer ones from the lanes that own them
+// (lane -/+ 4: the same channel quad of the tile to the left / right); false = every thread fetches its four columns (LRPX_B6_WINO bit 8,
+// the default: the shared form moves fewer bytes and is not faster).  Both stage the same bits.
+template <int HW, bool SHARE>
 __global__ __launch_bounds__(512) void conv_wino_b6_kernel(ConvArgs a, int total_tiles, int m_blocks, int n_blocks) {
     constexpr int TW = HW / 2, TPM = TW * TW, P = HW * HW;
     constexpr int BAND = 32;
@@ -61,44 +83,77 @@ __global__ __launch_bounds__(512) void conv_wino_b6_kernel(ConvArgs a, int total
     const int nchunk = a.cin / 16;
 
     // ---- staging: thread = (tile, 4-channel quad, half of the transform rows); three patch rows x four columns each ----
+    // rv[0..2] = patch rows (a, b, c) with V rows  a - c  and  c + sgn b:  half 0 (i = 0, 1): a, b, c = d0, d1, d2, sgn = +1
+    // (d0 - d2, d1 + d2);  half 1 (i = 2, 3): a, b, c = d2, d3, d1, sgn = -1 (d2 - d1, d1 - d3) - one code path, no selects
     const int seg = tid & 3, stile = (tid >> 2) & 63;
-    const int half = wave >> 2;                 // 0: V rows i = 0, 1 (patch rows 0..2)   1: i = 2, 3 (patch rows 1..3)
+    const int half = wave >> 2;
+    const float sgn = half ? -1.f : 1.f;
     unsigned smask = 0;
+    bool take_l = false, take_r = false;     // SHARE: patch column 0 / 3 comes from lane - 4 / lane + 4
     long sbase;
+    int srow[3];                             // patch row of slot a, b, c (wave-uniform)
     {
         const int T = row0 + stile;
         const int n = T / TPM, t = T - n * TPM;
         const int ty = t / TW, tx = t - ty * TW;
-        const int y0 = 2 * ty - 1 + half, x0 = 2 * tx - 1;
+        const int y0 = 2 * ty - 1, x0 = 2 * tx - 1;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) srow[r] = half ? (r == 2 ? 1 : r + 2) : r;
         if (T < total_tiles) {
 #pragma unroll
             for (int r = 0; r < 3; ++r)
 #pragma unroll
                 for (int c = 0; c < 4; ++c)
-                    if (y0 + r >= 0 && y0 + r < HW && x0 + c >= 0 && x0 + c < HW) smask |= 1u << (r * 4 + c);
+                    if (y0 + srow[r] >= 0 && y0 + srow[r] < HW && x0 + c >= 0 && x0 + c < HW) smask |= 1u << (r * 4 + c);
+            if (SHARE) {
+                // lanes -/+ 4 hold tiles T -/+ 1 (same half, so the same patch rows) if they are in this wave; inside a tile row
+                // they are this map's tiles tx -/+ 1, whose own columns 2 / 1 are this patch's columns 0 / 3.  At the ends of
+                // the wave and of the tile row the thread keeps its own fetch (or the zero padding) under smask.
+                take_l = (stile & 15) != 0 && tx != 0;
+                take_r = (stile & 15) != 15 && tx != TW - 1 && T + 1 < total_tiles;
+                if (take_l) smask &= ~0x111u;
+                if (take_r) smask &= ~0x888u;
+            }
         }
         sbase = (((long)n * HW + y0) * HW + x0) * a.cin + seg * 4;
     }
+    // smask never changes: what a thread does not fetch stays the zero it starts as (SHARE: or is overwritten by the exchange)
     f32x4 rv[3][4];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) rv[r][c] = f32x4{0, 0, 0, 0};
 #define LRPXW_ISSUE(CHUNK)                                                                                          \
     _Pragma("unroll") for (int r = 0; r < 3; ++r) _Pragma("unroll") for (int c = 0; c < 4; ++c) {                    \
-        rv[r][c] = f32x4{0, 0, 0, 0};                                                                               \
         if (smask & (1u << (r * 4 + c)))                                                                            \
-            rv[r][c] = *reinterpret_cast<const f32x4*>(a.in + sbase + (long)(r * HW + c) * a.cin + (CHUNK) * 16);    \
+            rv[r][c] = *reinterpret_cast<const f32x4*>(a.in + sbase + (long)(srow[r] * HW + c) * a.cin + (CHUNK) * 16); \
     }
-    // stage 1 (rows): t_0 = d0 - d2, t_1 = d1 + d2, t_2 = d2 - d1, t_3 = d1 - d3; stage 2 (columns) alike
+    // ds_bpermute moves a dword between lanes without a VALU slot (DPP row shifts stop at 16 lanes = 4 tiles); one select per dword.
+    // (the element goes through a scalar: __builtin_bit_cast straight on rv[r][c][e] reads element 0 of the vector)
+    const int lane_l = ((lane - 4) & 63) * 4, lane_r = ((lane + 4) & 63) * 4;
+#define LRPXW_SHARE()                                                                                               \
+    if (SHARE) {                                                                                                    \
+        _Pragma("unroll") for (int r = 0; r < 3; ++r) _Pragma("unroll") for (int e = 0; e < 4; ++e) {                \
+            const float ml = rv[r][2][e], mr = rv[r][1][e];                                                         \
+            const float fl = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(lane_l, __builtin_bit_cast(int, ml))); \
+            const float fr = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(lane_r, __builtin_bit_cast(int, mr))); \
+            rv[r][0][e] = take_l ? fl : rv[r][0][e];                                                                \
+            rv[r][3][e] = take_r ? fr : rv[r][3][e];                                                                \
+        }                                                                                                           \
+    }
+    // stage 1 (rows): t_0 = d0 - d2, t_1 = d1 + d2, t_2 = d2 - d1, t_3 = d1 - d3; stage 2 (columns) alike.  Channel pairs: packed fp32
 #define LRPXW_COMMIT(BUFIDX)                                                                                        \
     {                                                                                                               \
+        LRPXW_SHARE()                                                                                               \
         char* vb = ldsw + (BUFIDX) * WINO_BUF + (half * 8) * WINO_XI + seg * WINO_KQ + stile * 16;                  \
         _Pragma("unroll") for (int ii = 0; ii < 2; ++ii) {                                                          \
             f32x4 t[4];                                                                                             \
             _Pragma("unroll") for (int c = 0; c < 4; ++c)                                                           \
-                t[c] = half == 0 ? (ii == 0 ? rv[0][c] - rv[2][c] : rv[1][c] + rv[2][c])                            \
-                                 : (ii == 0 ? rv[1][c] - rv[0][c] : rv[0][c] - rv[2][c]);                           \
-            *reinterpret_cast<f32x4*>(vb + (ii * 4 + 0) * WINO_XI) = t[0] - t[2];                                   \
-            *reinterpret_cast<f32x4*>(vb + (ii * 4 + 1) * WINO_XI) = t[1] + t[2];                                   \
-            *reinterpret_cast<f32x4*>(vb + (ii * 4 + 2) * WINO_XI) = t[2] - t[1];                                   \
-            *reinterpret_cast<f32x4*>(vb + (ii * 4 + 3) * WINO_XI) = t[1] - t[3];                                   \
+                t[c] = ii == 0 ? wino_sub(rv[0][c], rv[2][c]) : wino_fma(rv[1][c], sgn, rv[2][c]);                  \
+            *reinterpret_cast<f32x4*>(vb + (ii * 4 + 0) * WINO_XI) = wino_sub(t[0], t[2]);                          \
+            *reinterpret_cast<f32x4*>(vb + (ii * 4 + 1) * WINO_XI) = wino_add(t[1], t[2]);                          \
+            *reinterpret_cast<f32x4*>(vb + (ii * 4 + 2) * WINO_XI) = wino_sub(t[2], t[1]);                          \
+            *reinterpret_cast<f32x4*>(vb + (ii * 4 + 3) * WINO_XI) = wino_sub(t[1], t[3]);                          \
         }                                                                                                           \
     }
 
@@ -173,6 +228,7 @@ __global__ __launch_bounds__(512) void conv_wino_b6_kernel(ConvArgs a, int total
         __syncthreads();
     }
 #undef LRPXW_ISSUE
+#undef LRPXW_SHARE
 #undef LRPXW_COMMIT
 
     // ---- output transform Y = A^T M A (A^T = [1 1 1 0; 0 1 -1 -1]) through LDS, then out = x * Y ----
@@ -229,7 +285,7 @@ __global__ __launch_bounds__(512) void conv_wino_b6_kernel(ConvArgs a, int total
         }
 }
 
-template <int HW>
+template <int HW, bool SHARE>
 int launch_conv_wino_b6(const ConvArgs& a, hipStream_t stream) {
     constexpr int TPM = (HW / 2) * (HW / 2);
     const long total_tiles = (long)a.n_maps * TPM;
@@ -240,7 +296,7 @@ int launch_conv_wino_b6(const ConvArgs& a, hipStream_t stream) {
         set_error("conv_wino_b6: grid %ld out of range or n_oc %d not a multiple of 64", grid, a.n_oc);
         return LRPX_EINVAL;
     }
-    auto kern = conv_wino_b6_kernel<HW>;
+    auto kern = conv_wino_b6_kernel<HW, SHARE>;
     static LdsOnce attr_once;
     LRPX_TRY(reserve_lds_once(attr_once, kern, WINO_LDS, "conv_wino_b6"));
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), WINO_LDS, stream, a, (int)total_tiles, (int)m_blocks, n_blocks);

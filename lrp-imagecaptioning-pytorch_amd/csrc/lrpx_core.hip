@@ -77,7 +77,7 @@ const Switches& switches() {
         w.x6_legacy = set("LRPX_X6_LEGACY");
         w.b6_wide = num("LRPX_B6_WIDE", 0);
         w.b6_rel_ksplit14 = num("LRPX_B6_REL_KSPLIT14", 2);
-        w.b6_wino = num("LRPX_B6_WINO", 7) & 7;
+        w.b6_wino = num("LRPX_B6_WINO", 15) & 15;
         w.b6_fwd_ksplit28 = num("LRPX_B6_FWD_KSPLIT28", 4);
         w.b6_fwd_ksplit56 = num("LRPX_B6_FWD_KSPLIT56", 2);
         return w;
@@ -1135,7 +1135,7 @@ int lrpx_pack_weights_wino_b6(const float* w, int cout, int cin, int mode, void*
 
 int lrpx_set_b6_wino(int bits) {
     const int prev = b6_wino_bits();
-    if (bits >= 0) g_b6_wino.store(bits & 7, std::memory_order_relaxed);
+    if (bits >= 0) g_b6_wino.store(bits & 15, std::memory_order_relaxed);
     return prev;
 }
 

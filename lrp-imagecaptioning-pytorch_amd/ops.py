@@ -65,7 +65,8 @@ def pack_weights_wino_b6(w, cout, cin, mode):
 
 
 def set_b6_wino(bits):
-    """lrpx_set_b6_wino: bit mask of the map sizes (56: 1, 28: 2, 14: 4) whose conv-mode-1 relevance convs run as Winograd; returns the previous mask"""
+    """lrpx_set_b6_wino: bit mask of the map sizes (56: 1, 28: 2, 14: 4) whose conv-mode-1 relevance convs run as Winograd
+    (+ 8: the kernel's legacy patch staging, without column sharing between lanes - the same bits; default 15); returns the previous mask"""
     return _lib.load().lrpx_set_b6_wino(int(bits))
 
 
