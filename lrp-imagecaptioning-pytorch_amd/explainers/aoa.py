@@ -10,11 +10,13 @@ import torch
 from .. import _lib, ops
 from .._lib import (AoaGradState, AoaRelState, AoaStepArgs, AoaTrace, EPI_PLAIN, EPI_REL, PACK_DENSE, PACK_DENSE_T, STAB_EPS, check, ptr, ptr_at,
                     stream_ptr)
-from .gridtd import IMAGENET_MEAN, IMAGENET_STD, VGG_PREFIX, _t, load_image
+from .dropin import ExplainerBase
+from .engine_base import EngineBase
+from .gridtd import VGG_PREFIX, _t
 from .ragged import ragged
 
 
-class AOAEngine:
+class AOAEngine(EngineBase):
     """`state`: the reference `AOAModel` state_dict (models/aoamodel.py:116-142).  Without encoder weights
     (bottom-up model, :1795-1797) only `features=` inputs are accepted."""
 
@@ -30,6 +32,7 @@ class AOAEngine:
         if names:
             self.vgg = ops.Vgg16([_t(state[k], dev) for k in names],
                                  [_t(state[k.replace(".weight", ".bias")], dev) for k in names])
+        self.cnn, self.resnet = self.vgg, False          # (the encoder as explainers/engine_base.py reads it: VGG16 or none)
         self.sd = sd
         self.NH = num_head
         self.V, self.E = sd["embedding.weight"].shape
@@ -193,91 +196,22 @@ class AOAEngine:
                                     ptr(sd["decoder_aoa_linear.bias"]), ptr(lin), H, B, H, H, 0, st))
         check(lib.lrpx_aoa_fwd_post(c, t, ptr(qg), 2 * H, ptr(lin), st))
 
-    def sample_lrp(self, enc, max_length, start_id, end_id, skip_ids):
-        """AOAModel.sample_lrp, greedy (models/aoamodel.py:679-745): LRP-inference decoding.  `get_lrp_weight_step`
-        (:597-626) is handed the log-softmax of the scores (:721-723), unlike the gridTD model.  Returns (seq int64
-        (B,max_length), seq_logprobs (B,max_length)); tokens after <end> are 0, nothing is written once every sequence
-        has finished (:742-744)."""
-        lib = _lib.load()
-        B, T, H = enc["B"], max_length, self.H
-        dev = self.device
-        skip = torch.zeros(self.V, dtype=torch.uint8, device=dev)
-        skip[torch.as_tensor(sorted(int(i) for i in skip_ids), dtype=torch.int64, device=dev)] = 1
-        toks = torch.zeros(B, T + 1, dtype=torch.int64, device=dev)
-        toks[:, 0] = start_id
-        lps = torch.zeros(B, T, dtype=torch.float32, device=dev)
-        tr = self._alloc_trace(B, T, enc["P"])
-        hcw = torch.empty(B, H, device=dev)
-        nxt = torch.empty(B, dtype=torch.int64, device=dev)
-        lp = torch.empty(B, dtype=torch.float32, device=dev)
-        unfinished = torch.ones(B, dtype=torch.bool, device=dev)
-        for t in range(T):
-            self._step(tr, enc, t, toks, self.bcat_model)
-            st = stream_ptr()
-            pred = self.logits(tr["hc"][:, t].contiguous())
-            check(lib.lrpx_lrp_reweight_rows(ptr(pred), self.V, self.V, ptr_at(tr["h"], (t + 1) * H), (T + 1) * H,
-                                             ptr_at(tr["c_aoa"], t * H), T * H, ptr(self.sd["fc.weight"]), ptr(skip),
-                                             ptr(hcw), B, H, 1, st))
-            wpred = self.logits(hcw)
-            check(lib.lrpx_argmax_logprob_rows(ptr(wpred), self.V, B, self.V, ptr(nxt), ptr(lp), st))
-            alive = unfinished.any()
-            unfinished = unfinished & (nxt != end_id)
-            toks[:, t + 1] = torch.where(alive, nxt * unfinished, torch.zeros_like(nxt))
-            lps[:, t] = torch.where(alive, lp, torch.zeros_like(lp))
-        return toks[:, 1:].contiguous(), lps
+    # the decode loops of explainers/engine_base.py (beam_search, sample_lrp, forwardlrp_context) on this model's step
+    _BEAM_STATE = ("h", "c")
 
-    def beam_search(self, enc, beam_size, max_cap_length, start_id, end_id):
-        """`AOAModel.beam_search` (models/aoamodel.py, the algorithm of models/gridTDmodel.py:400-478 on the AoA step) for
-        ONE image: returns the chosen token sequence incl. <start>."""
-        from .beam import run_beam_search
-        assert enc["B"] == 1, "beam search captions one image"
-        nb = int(beam_size)
-        encb = {k: (v.expand(nb, *v.shape[1:]).contiguous() if torch.is_tensor(v) else v) for k, v in enc.items()}
-        encb["B"] = nb
-        T = int(max_cap_length)
-        tr = self._alloc_trace(nb, T, enc["P"])
-        toks = torch.zeros(nb, T + 1, dtype=torch.int64, device=self.device)
+    def _decode_trace(self, enc, B, T, lrp=False):
+        return self._alloc_trace(B, T, enc["P"])
 
-        def step(t, prev):
-            toks[:, t] = prev
-            self._step(tr, encb, t, toks, self.bcat_model)
+    def _decode_step(self, tr, enc, t, toks):
+        self._step(tr, enc, t, toks, self.bcat_model)
 
-        def reorder(t, src):
-            sel = torch.tensor(src, dtype=torch.int64, device=self.device)
-            for k in ("h", "c"):
-                tr[k][:len(src), t + 1] = tr[k][sel, t + 1]
-
-        return run_beam_search(step, lambda t: self.logits(tr["hc"][:, t].contiguous()), reorder, self.V, nb, T,
-                               start_id, end_id, self.device)
-
-    def forwardlrp_context(self, enc, captions, caption_lengths, skip_ids):
-        """The forward half of `AOAModel.forwardlrp_context` (models/aoamodel.py:628-677): teacher-forced decoding with the
-        model's own forward; every step's scores are recomputed from the fc input re-weighted by the relevance of the
-        step's arg-max word (`get_lrp_weight_step`, :597-626 - handed the RAW scores here, unlike `sample_lrp`).  Dropout is
-        the identity (evaluation mode).  Returns (predictions (B,L,V), weighted_predictions (B,L,V), L)."""
-        lib = _lib.load()
-        B, H = enc["B"], self.H
-        L = int(max(caption_lengths)) - 1
-        dev = self.device
-        captions = captions.to(dev, torch.int64).contiguous()
-        assert captions.shape[0] == B and captions.shape[1] >= L
-        skip = torch.zeros(self.V, dtype=torch.uint8, device=dev)
-        skip[torch.as_tensor(sorted(int(i) for i in skip_ids), dtype=torch.int64, device=dev)] = 1
-        toks = captions[:, :L + 1].contiguous() if captions.shape[1] > L else torch.cat(
-            [captions, captions.new_zeros(B, 1)], 1).contiguous()
-        tr = self._alloc_trace(B, L, enc["P"])
-        hcw = torch.empty(B, H, device=dev)
-        preds = torch.empty(B, L, self.V, device=dev)
-        wpreds = torch.empty(B, L, self.V, device=dev)
-        for t in range(L):
-            self._step(tr, enc, t, toks, self.bcat_model)
-            pred = self.logits(tr["hc"][:, t].contiguous())
-            check(lib.lrpx_lrp_reweight_rows(ptr(pred), self.V, self.V, ptr_at(tr["h"], (t + 1) * H), (L + 1) * H,
-                                             ptr_at(tr["c_aoa"], t * H), L * H, ptr(self.sd["fc.weight"]), ptr(skip),
-                                             ptr(hcw), B, H, 0, stream_ptr()))
-            preds[:, t] = pred
-            wpreds[:, t] = self.logits(hcw)
-        return preds, wpreds, L
+    def _reweight(self, tr, t, pred, skip, hcw, log_softmax):
+        """`get_lrp_weight_step` (models/aoamodel.py:597-626): `sample_lrp` hands it the log-softmax of the scores (:721-723),
+        `forwardlrp_context` the raw scores"""
+        B, T, H = tr["B"], tr["T"], self.H
+        check(_lib.load().lrpx_lrp_reweight_rows(ptr(pred), self.V, self.V, ptr_at(tr["h"], (t + 1) * H), (T + 1) * H,
+                                                 ptr_at(tr["c_aoa"], t * H), T * H, ptr(self.sd["fc.weight"]), ptr(skip),
+                                                 ptr(hcw), B, H, 1 if log_softmax else 0, stream_ptr()))
 
     def _plain_rows(self, x, name, bias, amax=None):
         """x (R, K) @ W^T + bias -> (R, N) for one of the trace's plain linears over all (image, word) rows: split products on the
@@ -423,57 +357,19 @@ class AOAEngine:
         tr = self.trace(enc, captions, predictions=False, grad=True)
         rg = ragged(lens, B, T, self.device)
         d_feat, r_words, row2img = self.gradient(enc, tr, head_idx, rg)
-        n = d_feat.shape[0]                      # B*T, or the valid rows of captions of unequal length
-        if n == 0:
-            maps = d_feat.new_zeros((0, enc["P"]) if kind == "gradcam" else (0, 3, 224, 224))
-        elif kind == "gradcam":
-            maps = torch.empty(n, enc["P"], device=self.device, dtype=torch.float32)
-            check(_lib.load().lrpx_gradcam(ptr(enc["feats"]), ptr(d_feat), ptr(row2img), ptr(maps), n, enc["P"], self.C,
-                                           stream_ptr()))
-        elif kind in ("guided", "guided_gradcam"):
+        P = enc["P"]
+
+        def maps_of(d_feat, row2img):
+            if kind == "gradcam":
+                return self.grad_cam(enc, d_feat, row2img)
+            if kind not in ("guided", "guided_gradcam"):
+                return self.vgg.gradient(d_feat, row2img)
             maps = self.vgg.guided_backprop(d_feat, row2img)
             if kind == "guided_gradcam":         # ExplainAOAGuidedGradCam (:1714-1751): x the expanded Grad-CAM map
-                cam = torch.empty(n, enc["P"], device=self.device, dtype=torch.float32)
-                check(_lib.load().lrpx_gradcam(ptr(enc["feats"]), ptr(d_feat), ptr(row2img), ptr(cam), n, enc["P"],
-                                               self.C, stream_ptr()))
-                maps = ops.guided_gradcam(maps, cam, int(round(enc["P"] ** 0.5)))
-        else:
-            maps = self.vgg.gradient(d_feat, row2img)
-        if rg is not None and not rg.full:       # back to the padded layout, zeros behind an image's last word
-            maps = ops.scatter_maps(maps, rg)
-            if return_features:
-                d_feat = ops.scatter_maps(d_feat, rg)
-        maps = maps.view(B, T, enc["P"]) if kind == "gradcam" else maps.view(B, T, 3, 224, 224)
-        out = (maps, r_words.view(B, T, T))
-        if return_features:
-            out = out + (d_feat.view(B, T, enc["P"], self.C), tr, enc)
-        return out
-
-    def logits(self, hc_rows, fast=False, amax=None):
-        """fc scores for R rows -> (R,V).  fast=True (the (T,V) block a trace keeps, not the decisions of a decoding loop): split
-        products on the fp16 matrix cores (csrc/dense_f16x3.hip, fp32-grade: <= 2e-7 of a row's maximum)"""
-        R = hc_rows.shape[0]
-        out = torch.empty(R, self.V, device=self.device)
-        if fast and R >= 128 and self.p_fc_fwd_h is not None and self._f16():
-            hc_rows = hc_rows.contiguous()
-            ops.conv_mfma(hc_rows, self.p_fc_fwd_h, R, 0, self.H, -(-self.V // 32) * 32, 1, EPI_PLAIN, pix_per_map=1, oc_split=self.V,
-                          bias=self.sd["fc.bias"], out0=out, f16x3=1, in_amax=amax if amax is not None else ops.amax_maps(hc_rows, R))
-            return out
-        ops.conv_mfma(hc_rows, self.p_fc_fwd, R, 0, self.H, -(-self.V // 32) * 32, 1, EPI_PLAIN, pix_per_map=1,
-                      oc_split=self.V, bias=self.sd["fc.bias"], out0=out)
-        return out
-
-    def _row_index(self, B, T):
-        key = (B, T)
-        if key not in self._idx_cache:
-            b = torch.arange(B, device=self.device).view(B, 1)
-            t = torch.arange(T, device=self.device).view(1, T)
-            s = torch.arange(T, device=self.device).view(T, 1, 1)
-            idx = (b * T + (t - s).clamp(min=0)).to(torch.int32).reshape(T, B * T).contiguous()
-            row2img = (b + 0 * t).to(torch.int32).reshape(B * T).contiguous()
-            rowid = torch.arange(B * T, device=self.device, dtype=torch.int32)
-            self._idx_cache[key] = (idx, row2img, rowid)
-        return self._idx_cache[key]
+                maps = ops.guided_gradcam(maps, self.grad_cam(enc, d_feat, row2img), int(round(P ** 0.5)))
+            return maps
+        return self._finish(rg, B, T, d_feat, r_words, row2img, maps_of, (P,) if kind == "gradcam" else (3, 224, 224),
+                            features=(tr, enc) if return_features else None)
 
     def relevance(self, enc, tr, head_idx, lens=None, compact=True):
         """explain_caption_wordt (:1064-1156) for every (image, word) row -> r_feat (B*T,P,C), r_words (B*T,T), row -> image.
@@ -533,25 +429,22 @@ class AOAEngine:
         else:
             a_val = e(n, P, H)
             check(lib.lrpx_aoa_rel_value_rows(ctr, crs, ptr(r_ctx), ptr(enc["value"]), int(head_idx), ptr(a_val), ptr(rowlist), n, st))
+        amax2 = None
         if f16_rules:
             amax2 = ops.zeros(n, dtype=torch.int32, device=self.device)           # max|a_proj| per row: recorded by the first GEMM
             ops.conv_mfma(a_val, self.p_v_rel_head[int(head_idx)] if head_only else self.p_v_rel_h, n, 0, dk if head_only else H, H, 1,
                           EPI_REL, pix_per_map=P, oc_split=H, x=enc["Vp"], u=U,
                           zdiv=enc["proj_pre"], stab=STAB_EPS, map2img=row2img, out1=a_proj, f16x3=1,
                           in_amax=ops.amax_maps(a_val, n), out1_amax=amax2)
-            ops.conv_mfma(a_proj, self.p_proj_rel_h, n, 0, H, -(-Cc // 32) * 32, 1, EPI_REL, pix_per_map=P, oc_split=Cc,
-                          x=enc["feats"], map2img=row2img, out0=r_feat, f16x3=1, in_amax=amax2)       # :1145-1148
         elif b6_rules:
             ops.conv_mfma(a_val, self.p_v_rel_head6[int(head_idx)] if head_only else self.p_v_rel_6, n, 0, dk if head_only else H, H, 1,
                           EPI_REL, pix_per_map=P, oc_split=H, x=enc["Vp"], u=U, zdiv=enc["proj_pre"], stab=STAB_EPS, map2img=row2img,
                           out1=a_proj, bf16x6=1)
-            ops.conv_mfma(a_proj, self.p_proj_rel_6, n, 0, H, -(-Cc // 32) * 32, 1, EPI_REL, pix_per_map=P, oc_split=Cc,
-                          x=enc["feats"], map2img=row2img, out0=r_feat, bf16x6=1)                     # :1145-1148
         else:
             ops.conv_mfma(a_val, self.p_v_rel, n, 0, H, H, 1, EPI_REL, pix_per_map=P, oc_split=H, x=enc["Vp"], u=U,
                           zdiv=enc["proj_pre"], stab=STAB_EPS, map2img=row2img, out1=a_proj)
-            ops.conv_mfma(a_proj, self.p_proj_rel, n, 0, H, Cc, 1, EPI_REL, pix_per_map=P, oc_split=Cc, x=enc["feats"],
-                          map2img=row2img, out0=r_feat)                                   # :1145-1148
+        # :1145-1148, in the arithmetic of the v_proj rule
+        self._proj_rule(a_proj, n, P, enc["feats"], row2img, r_feat, kind="f16" if f16_rules else "b6" if b6_rules else "f32", in_amax=amax2)
         return r_feat, rs["r_words"], row2img
 
     def explain_batch(self, captions, head_idx, images=None, features=None, lens=None, accumulate=False,
@@ -568,258 +461,68 @@ class AOAEngine:
             r_feat, r_words, _ = self.relevance(enc, tr, head_idx, rg, compact=False)
             return r_feat.view(B, T, enc["P"], self.C), r_words.view(B, T, T)
         r_feat, r_words, row2img = self.relevance(enc, tr, head_idx, rg)
-        if rg is not None and not rg.full:
-            # unequal caption lengths (models/aoamodel.py:1171-1176 explains `caption_length` words): the VGG16 chain runs on the
-            # sum(lens) valid maps; back to the padded layout afterwards (running sums per image over ITS words)
-            maps = self.vgg.relevance(r_feat, row2img) if rg.n else r_feat.new_zeros(0, 3, 224, 224)
-            maps = ops.scatter_maps(maps, rg, accumulate=accumulate)
-            if return_features:
-                r_feat = ops.scatter_maps(r_feat, rg)
-        else:
-            maps = self.vgg.relevance(r_feat, row2img)
-            if accumulate:
-                maps = ops.cumsum_maps(maps, B, T)
-        out = (maps.view(B, T, 3, 224, 224), r_words.view(B, T, T))
-        if return_features:
-            out = out + (r_feat.view(B, T, enc["P"], self.C), tr, enc)
-        return out
+        # unequal caption lengths (models/aoamodel.py:1171-1176 explains `caption_length` words): the VGG16 chain runs on the sum(lens)
+        # valid maps; `_finish` takes the result back to the padded layout
+        return self._finish(rg, B, T, r_feat, r_words, row2img, self.vgg.relevance, (3, 224, 224), accumulate=accumulate,
+                            features=(tr, enc) if return_features else None)
 
+    def _static(self, graph, key, captions, head_idx, images, features, accumulate, predictions):
+        name, src = ("features", features) if features is not None else ("images", images)
+        return self._static_step(graph, key, src.to(self.device, torch.float32), captions.to(self.device, torch.int64),
+                                 lambda s, c: self.explain_batch(c, head_idx, accumulate=accumulate, predictions=predictions, **{name: s}))
 
     def explain_batch_graph(self, captions, head_idx, images=None, features=None, accumulate=False, predictions=False):
-        """`explain_batch` replayed from a captured HIP graph (one per input shape / head), as GridTDEngine.explain_batch_graph:
-        one hipGraphLaunch instead of the ~330 launches of a bottom-up step.  Worth it for a SINGLE batch in flight (the host
-        issues ~4 us per launch); with batches in flight on several streams eager launches are faster (config 5, B = 32:
-        442 000 maps/s eager against 343 000 - 391 000 replayed, gpurun_out/r3g) - a replayed graph does not overlap with its
-        neighbours the way independent kernels do.  Inputs are copied into the graph's static buffers; the returned tensors
-        are the graph's static outputs (overwritten by the next call with the same shapes)."""
+        """`explain_batch` replayed from a captured HIP graph, one per input shape and head (explainers/engine_base.py: `_static_step`)."""
         src = features if features is not None else images
-        src = src.to(self.device, torch.float32)
-        captions = captions.to(self.device, torch.int64)
         key = (features is not None, tuple(src.shape), tuple(captions.shape), int(head_idx), bool(accumulate), bool(predictions), self._f16())
-        if not hasattr(self, "_graphs"):
-            self._graphs = {}
-        g = self._graphs.get(key)
-        if g is None:
-            st_src, st_cap = src.clone(), captions.clone()
-            kw = dict(features=st_src) if features is not None else dict(images=st_src)
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):                       # warm-up outside capture (kernel attributes, index caches)
-                self.explain_batch(st_cap, head_idx, accumulate=accumulate, predictions=predictions, **kw)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                out = self.explain_batch(st_cap, head_idx, accumulate=accumulate, predictions=predictions, **kw)
-            g = self._graphs[key] = (graph, st_src, st_cap, out)
-        graph, st_src, st_cap, out = g
-        st_src.copy_(src)
-        st_cap.copy_(captions)
-        graph.replay()
-        return out
+        return self._static(True, key, captions, head_idx, images, features, accumulate, predictions)
 
     def explain_batch_replay(self, captions, head_idx, images=None, features=None, accumulate=False, predictions=False):
-        """`explain_batch` as a RECORDED step (lrp_amd._lib.Recording): the first call with a given input shape runs the step eagerly
-        on static copies of the inputs and keeps its library calls - functions, arguments, and every buffer they point at; later calls
-        copy the inputs into those static buffers and issue the same calls again: the same kernels in the same order on the same
-        stream, as ordinary launches (they overlap with other streams' kernels like any launch; a HIP graph replay did not), without the
-        interpreter's ~9 us per launch.  Bit-identical to `explain_batch` by construction.  Like a graph's, the returned tensors are
-        the recording's static outputs: overwritten by the next call of the same shape on this engine (take `replica()`s for batches
-        in flight).  Captions of equal length only (`lens` makes the launch sequence data-dependent)."""
+        """`explain_batch` as a RECORDED step, one per input shape, head and stream (explainers/engine_base.py: `_static_step`)."""
         src = features if features is not None else images
-        src = src.to(self.device, torch.float32)
-        captions = captions.to(self.device, torch.int64)
         key = (tuple(src.shape), tuple(captions.shape), bool(accumulate), bool(predictions), _lib.stream_ptr().value,
                self.vgg.conv_mode if self.vgg is not None else None, int(head_idx), features is not None, self._f16())
-        if not hasattr(self, "_recordings"):
-            self._recordings = {}
-        rec = self._recordings.get(key)
-        if rec is None:
-            st_src, st_cap = src.clone(), captions.clone()
-            # warm-up outside the recording: one-time work (kernel attributes, index caches, workspace allocations) must not be replayed
-            self.explain_batch(st_cap, head_idx, accumulate=accumulate, predictions=predictions, **({"features": st_src} if features is not None else {"images": st_src}))
-            rec = _lib.Recording()
-            with rec:
-                rec.result = self.explain_batch(st_cap, head_idx, accumulate=accumulate, predictions=predictions, **({"features": st_src} if features is not None else {"images": st_src}))
-            rec.inputs = (st_src, st_cap)
-            self._recordings[key] = rec
-            return rec.result
-        st_src, st_cap = rec.inputs
-        st_src.copy_(src)
-        st_cap.copy_(captions)
-        return rec.replay()
-
-    def _f16(self):
-        """the decoder GEMMs on the fp16 split products?  (ops.decoder_f16: with conv modes 2 / 3 only - the engine's own `vgg.conv_mode` or the
-        process default; `force_f16` overrides per engine)"""
-        if self.force_f16 is not None:
-            return bool(self.force_f16)
-        return ops.decoder_f16(self.vgg.conv_mode if self.vgg is not None else None)
-
-    def replica(self):
-        """A second execution context over the SAME weights: own VGG16 trace / workspace buffers, so that several
-        batches can be in flight on separate HIP streams (as GridTDEngine.replica)."""
-        import copy
-        r = copy.copy(self)
-        if self.vgg is not None:
-            r.vgg = self.vgg.replica()
-        r._idx_cache = {}
-        for k in ("_graphs", "_replicas", "_streams", "_recordings"):
-            r.__dict__.pop(k, None)
-        return r
+        return self._static(False, key, captions, head_idx, images, features, accumulate, predictions)
 
     def explain_stream(self, batches, head_idx, depth=3, accumulate=False):
-        """`explain_batch` over an iterable of independent (images, captions) batches with `depth` batches in flight,
-        each on its own HIP stream and buffer set (the decoder's latency-bound kernels of one batch overlap the CNN
-        relevance chain of another).  Yields (maps, r_words) in input order, complete when yielded; bit-identical to
-        serial `explain_batch` calls."""
-        depth = max(1, int(depth))
-        if not hasattr(self, "_replicas"):
-            self._replicas, self._streams = [self], [torch.cuda.Stream(device=self.device)]
-        while len(self._replicas) < depth:
-            self._replicas.append(self.replica())
-            self._streams.append(torch.cuda.Stream(device=self.device))
-        pending = []
-        for i, batch in enumerate(batches):
-            images, captions = batch[0], batch[1]
-            lens = batch[2] if len(batch) > 2 else None                 # (images, captions[, lens])
-            k = i % depth
-            st = self._streams[k]
-            st.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(st):
-                out = self._replicas[k].explain_batch(captions, head_idx, images=images, lens=lens, accumulate=accumulate)
-                ev = torch.cuda.Event()
-                ev.record(st)
-            for t in out:
-                t.record_stream(torch.cuda.current_stream(self.device))
-            pending.append((out, ev, images, captions))      # inputs stay alive until the side stream has read them
-            if len(pending) >= depth:
-                o, e, _, _ = pending.pop(0)
-                e.synchronize()
-                yield o
-        for o, e, _, _ in pending:
-            e.synchronize()
-            yield o
+        """`explain_batch` over an iterable of (images, captions[, lens]) batches, `depth` in flight (explainers/engine_base.py)."""
+        return self._explain_stream(batches, depth, lambda eng, images, captions, lens: eng.explain_batch(
+            captions, head_idx, images=images, lens=lens, accumulate=accumulate))
 
 
-class ExplainAOAAttention(object):
+class ExplainAOAAttention(ExplainerBase):
     """Drop-in for the reference's `ExplainAOAAttention` (models/aoamodel.py:748-1194), called as evaluation.py:637,702,767 call
     it: `explain_caption(img_filepath, head_idx)`, `explain_caption_wordt(t, head_idx)`, `explain_cnn(R)`,
     `explain_caption_words(img_filepath)`, `teacherforce_forward(img, beam_caption_encode)`, `get_hidden_parameters(img_filepath)`,
     `preprocess_img(img_filepath)`; attributes `.model .word_map .img .img_filepath .beam_caption .beam_caption_encode .predictions
-    .alphas .args`.  Wherever the reference takes a file path a (1,3,H,W) tensor is accepted too.  See
-    explainers/gridtd.py:ExplainGridTDAttention for the conventions (without `caption_encode=` the image is captioned by the
-    reference's own procedure, beam search with beam 3 over 20 steps, :992; nothing written to disk)."""
-    EPS = 0.01
-    EX_TYPE = 'lrp'
-    TF_MODEL_BIAS = False      # the LRP explainer's LanguageLSTM forward adds bias_ih twice (:873); the gradient family's is correct (:1298)
+    .alphas .args`.  Conventions: explainers/dropin.py; the caption the reference explains is its beam search with beam 3 over 20
+    steps (:992)."""
 
     def __init__(self, args, word_map, model=None):
-        self.args = args
-        self.word_map = word_map
-        self.vocab_size = len(word_map)
         self.num_head = getattr(args, "num_head", 8)
+        super().__init__(args, word_map, model)
+
+    def _engine_key(self):
         from . import engine_cache
-        key = engine_cache.fingerprint("aoa", args.weight if model is None else model, (self.num_head,))
+        return engine_cache.fingerprint("aoa", self.args.weight if self.model is None else self.model, (self.num_head,))
 
-        def build():
-            if model is None:
-                state = torch.load(args.weight, map_location="cpu")['state_dict']
-            elif hasattr(model, "state_dict"):
-                state = model.state_dict()
-            else:
-                state = model
-            return AOAEngine(state, self.num_head)
-        self.model = model
-        # one device engine per weight set (explainers/engine_cache.py); weights shared, trace / workspace buffers this explainer's own
-        self.engine = engine_cache.get(key, build, hold=engine_cache.source_tensors(model)).replica()
-        self.rev_word_map = {v: k for k, v in word_map.items()}
-        self.mean = list(IMAGENET_MEAN)
-        self.std = list(IMAGENET_STD)
-
-    def preprocess_img(self, img_filepath):
-        """Resize -> ToTensor -> Normalize (models/aoamodel.py:864-868), host side."""
-        return load_image(img_filepath, getattr(self.args, "height", 224), getattr(self.args, "width", 224), self.mean, self.std,
-                          self.engine.device)
+    def _build_engine(self, state):
+        return AOAEngine(state, self.num_head)
 
     def get_hidden_parameters(self, img, caption_encode=None):
         """Forward trace (:990-1062).  `img`: file path (the reference's argument) or a (1,3,224,224) tensor."""
-        eng = self.engine
-        if isinstance(img, str):
-            self.img_filepath = img
-            self.img = self.preprocess_img(img)
-        else:
-            self.img = img.to(eng.device, torch.float32)
-        # (a caption that is handed over is uploaded before the encoder is enqueued: the copy of a pageable list waits for the stream)
-        cap_dev = None if caption_encode is None else torch.tensor([[int(c) for c in caption_encode]], dtype=torch.int64, device=eng.device)
-        self._enc = eng.encode(self.img)
-        if caption_encode is None:       # the reference captions the image itself: beam 3, 20 steps (:992-995)
-            from .beam import caption_from_sequence
-            seq = eng.beam_search(self._enc, 3, 20, self.word_map['<start>'], self.word_map['<end>'])
-            caption_encode = caption_from_sequence(seq, self.word_map)
-        self.beam_caption_encode = [int(c) for c in caption_encode]
-        self.caption_length = len(self.beam_caption_encode) - 1
-        special = {self.word_map[k] for k in ('<start>', '<end>', '<unk>', '<pad>') if k in self.word_map}
-        self.beam_caption = [' '.join(self.rev_word_map.get(c, str(c)) for c in self.beam_caption_encode[1:]
-                                      if c not in special)]
-        self._rel = {}
-        if self.caption_length == 0:
-            return
-        cap = cap_dev if cap_dev is not None else torch.tensor([self.beam_caption_encode], dtype=torch.int64, device=eng.device)
-        self._cap_dev = cap
-        self._tr = eng.trace(self._enc, cap, predictions=True)
-        self.image_features = ops.nhwc_to_nchw(self._enc["feats"].contiguous(), eng.C, 14, 14)
-        self.num_pixels = self._enc["P"]
-        self.predictions = self._tr["pred"][0]
-        self.alphas = self._tr["alpha"][0]
-        self._rel = {}
+        self._hidden_parameters(img, caption_encode, 3, 20)
 
-    def _relevance(self, head_idx):
-        if head_idx not in self._rel:
-            self._rel[head_idx] = self.engine.relevance(self._enc, self._tr, head_idx)
-        return self._rel[head_idx]
+    def _explain_rows(self, head_idx):
+        return self.engine.relevance(self._enc, self._tr, head_idx)
 
     def explain_caption_wordt(self, t, head_idx):
-        assert t < self.caption_length
-        r_feat, r_words, _ = self._relevance(head_idx)
-        return ops.nhwc_to_nchw(r_feat[t:t + 1].contiguous(), self.engine.C, 14, 14), r_words[t, :t + 1].clone()
-
-    def explain_cnn(self, r_img_feature):
-        t_nhwc = ops.nchw_to_nhwc(r_img_feature.to(torch.float32))
-        r = self.engine.vgg.relevance(t_nhwc, torch.zeros(r_img_feature.shape[0], dtype=torch.int32,
-                                                          device=self.engine.device))
-        if getattr(self, "_img_grad", None) is None:
-            self._img_grad = r
-        else:
-            check(_lib.load().lrpx_accumulate(ptr(self._img_grad), ptr(r), r.numel(), stream_ptr()))
-        ops.check_relevance(self._img_grad, finite=True, nonzero=True)
-        return self._img_grad.clone()
-
-    def teacherforce_forward(self, img, beam_caption_encode):
-        """(:952-988; gradient family :1377-1413) -> predictions (len(beam_caption_encode), V) under teacher forcing: step t reads
-        token t (evaluation.py:702,767 hand the caption WITH <start>), with this explainer's own LanguageLSTM forward."""
-        eng = self.engine
-        if isinstance(img, str):
-            img = self.preprocess_img(img)
-        enc = eng.encode(img.to(eng.device, torch.float32))
-        cap = torch.tensor([[int(c) for c in beam_caption_encode] + [0]], dtype=torch.int64, device=eng.device)
-        n = cap.shape[1] - 1
-        tr = eng.trace(enc, cap, model_bias=self.TF_MODEL_BIAS, predictions=False)
-        return eng.logits(tr["hc"].view(n, eng.H))       # the fp32 kernel of the decoding loops, at any caption length
+        return self._explain_wordt(t, head_idx)
 
     def explain_caption(self, img_filepath, head_idx, t_list=None, caption_encode=None):
-        """(:1165-1181); the returned maps are the reference's running sums (lrp_wrapper.py:64-82)."""
-        img = img_filepath
-        self.img_filepath = img_filepath
-        self.get_hidden_parameters(img, caption_encode)
-        if self.caption_length == 0:
-            return [], []
-        self._img_grad = None
-        r_feat, r_words, row2img = self._relevance(head_idx)
-        maps = ops.cumsum_maps(self.engine.vgg.relevance(r_feat, row2img), 1, self.caption_length)
-        ops.check_relevance(maps, finite=True, nonzero=True)
-        return ([maps[t:t + 1] for t in range(self.caption_length)],
-                [r_words[t, :t + 1] for t in range(self.caption_length)])
+        """(:1165-1181; gradient family :1517-1534) -> ([T] x maps, [T] x (t+1,)).  The LRP maps are the reference's running sums
+        (lrp_wrapper.py:64-82); the gradient family's image gradient is a fresh tensor per word."""
+        return self._explain_caption(img_filepath, caption_encode, head_idx)
 
     def explain_caption_words(self, img_filepath, caption_encode=None):
         """(:1183-1194) linguistic relevance only, head 0."""
@@ -837,37 +540,21 @@ class ExplainAOAGradient(ExplainAOAAttention):
     encoder (`explain_cnn`, :1501-1515).  Same surface: `explain_caption(img, head_idx) -> (maps, word scores)`."""
     EX_TYPE = 'gradient'
     TF_MODEL_BIAS = True
+    _RUNNING_SUMS = False
 
     def get_hidden_parameters(self, img, caption_encode=None):
         super().get_hidden_parameters(img, caption_encode)
-        if self.caption_length == 0:
-            return
-        self._tr = self.engine.trace(self._enc, self._cap_dev, predictions=True, grad=True)      # :1309-1376 (correct LSTM bias)
-        self.predictions = self._tr["pred"][0]
-        self.alphas = self._tr["alpha"][0]
+        if self.caption_length:
+            self._trace(grad=True)             # :1309-1376 (correct LSTM bias)
 
-    def _relevance(self, head_idx):
-        if head_idx not in self._rel:
-            self._rel[head_idx] = self.engine.gradient(self._enc, self._tr, head_idx)
-        return self._rel[head_idx]
+    def _explain_rows(self, head_idx):
+        return self.engine.gradient(self._enc, self._tr, head_idx)
 
     def _cnn(self, d_feat_nhwc, row2img):
         return self.engine.vgg.gradient(d_feat_nhwc, row2img)
 
-    def explain_cnn(self, d_img_feature):
-        t_nhwc = ops.nchw_to_nhwc(d_img_feature.to(torch.float32))
-        return self._cnn(t_nhwc, torch.zeros(d_img_feature.shape[0], dtype=torch.int32, device=self.engine.device))
-
-    def explain_caption(self, img_filepath, head_idx, t_list=None, caption_encode=None):
-        """(:1517-1534) no running sums here: the image gradient is a fresh tensor per word."""
-        self.img_filepath = img_filepath
-        self.get_hidden_parameters(img_filepath, caption_encode)
-        if self.caption_length == 0:
-            return [], []
-        d_feat, r_words, row2img = self._relevance(head_idx)
-        maps = self._cnn(d_feat, row2img)
-        return ([maps[t:t + 1] for t in range(self.caption_length)],
-                [r_words[t, :t + 1] for t in range(self.caption_length)])
+    def explain_cnn(self, d_img_feature):          # (the reference's argument name in this family)
+        return super().explain_cnn(d_img_feature)
 
 
 class ExplainAOAGuidedGradient(ExplainAOAGradient):
@@ -886,12 +573,8 @@ class ExplainAOAGuidedGradCam(ExplainAOAGuidedGradient):
     EX_TYPE = 'GuidedGradCam'
 
     def _cnn(self, d_feat_nhwc, row2img):
-        rows, P = d_feat_nhwc.shape[0], d_feat_nhwc.shape[1]
         guided = self.engine.vgg.guided_backprop(d_feat_nhwc, row2img)
-        cam = torch.empty(rows, P, device=self.engine.device, dtype=torch.float32)
-        check(_lib.load().lrpx_gradcam(ptr(self._enc["feats"]), ptr(d_feat_nhwc.contiguous()), ptr(row2img), ptr(cam), rows,
-                                       P, self.engine.C, stream_ptr()))
-        return ops.guided_gradcam(guided, cam, int(round(P ** 0.5)))
+        return ops.guided_gradcam(guided, self.engine.grad_cam(self._enc, d_feat_nhwc, row2img), int(round(d_feat_nhwc.shape[1] ** 0.5)))
 
 
 class ExplainAOAGradCam(ExplainAOAGradient):
@@ -899,8 +582,4 @@ class ExplainAOAGradCam(ExplainAOAGradient):
     EX_TYPE = 'GradCam'
 
     def _cnn(self, d_feat_nhwc, row2img):
-        rows, P = d_feat_nhwc.shape[0], d_feat_nhwc.shape[1]
-        cam = torch.empty(rows, P, device=self.engine.device, dtype=torch.float32)
-        check(_lib.load().lrpx_gradcam(ptr(self._enc["feats"]), ptr(d_feat_nhwc.contiguous()), ptr(row2img), ptr(cam), rows,
-                                       P, self.engine.C, stream_ptr()))
-        return cam
+        return self.engine.grad_cam(self._enc, d_feat_nhwc, row2img)

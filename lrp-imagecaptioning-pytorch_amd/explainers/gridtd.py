@@ -12,6 +12,8 @@ import torch
 from .. import _lib, ops
 from .._lib import (EPI_PLAIN, EPI_REL, GridGradState, GridRelState, GridStepArgs, GridTrace, PACK_DENSE, PACK_DENSE_T, check, ptr,
                     ptr_at, stream_ptr)
+from .dropin import ExplainerBase
+from .engine_base import EngineBase
 from .ragged import ragged
 
 VGG_PREFIX = "img_encoder.encoder."
@@ -23,27 +25,13 @@ def _t(v, dev):
     return v.detach().to(device=dev, dtype=torch.float32).contiguous()
 
 
-IMAGENET_MEAN, IMAGENET_STD = [0.485, 0.456, 0.406], [0.229, 0.224, 0.225]
-
-
-def load_image(img_filepath, height, width, mean, std, device):
-    """`preprocess_img` of every reference explainer (models/gridTDmodel.py:767-771, models/aoamodel.py:864-868): PIL open ->
-    RGB -> `transforms.Resize((height, width))` (PIL bilinear) -> `ToTensor` (/255, CHW) -> `Normalize(mean, std)` -> (1,3,H,W)
-    on the device.  Host side, as in the reference (image decoding is outside the path)."""
-    from PIL import Image
-    im = Image.open(img_filepath).convert('RGB').resize((width, height), Image.BILINEAR)
-    x = torch.from_numpy(np.asarray(im, dtype=np.float32) / 255.0).permute(2, 0, 1)
-    x = (x - torch.tensor(mean).view(3, 1, 1)) / torch.tensor(std).view(3, 1, 1)
-    return x.unsqueeze(0).contiguous().to(device)
-
-
 def resnet_encoder_keys(state):
     """does the state dict hold a bottleneck ResNet under `img_encoder.encoder.` (key names of models/resnet.py) rather than VGG16's
     numbered `features` layers?"""
     return VGG_PREFIX + "conv1.weight" in state
 
 
-class GridTDEngine:
+class GridTDEngine(EngineBase):
     """Device-resident gridTD model + trace/relevance pipelines.  `state` is the reference model's
     `state_dict` (torch tensors or numpy arrays, names of models/gridTDmodel.py:111-130).
 
@@ -278,18 +266,7 @@ class GridTDEngine:
         return tr
 
     def logits(self, hc_rows, fast=False):
-        """fc(context_hat + h2) (gridTDmodel.py:990) for R rows -> (R,V).  fast=True (the (T,V) block a trace keeps, not the
-        decisions of a decoding loop): split products on the fp16 matrix cores (csrc/dense_f16x3.hip, fp32-grade)"""
-        R = hc_rows.shape[0]
-        out = torch.empty(R, self.V, device=self.device)
-        if fast and R >= 128 and self.p_fc_fwd_h is not None and self._f16():
-            hc_rows = hc_rows.contiguous()
-            ops.conv_mfma(hc_rows, self.p_fc_fwd_h, R, 0, self.H, -(-self.V // 32) * 32, 1, EPI_PLAIN, pix_per_map=1, oc_split=self.V,
-                          bias=self.sd["fc.bias"], out0=out, f16x3=1, in_amax=ops.amax_maps(hc_rows, R))
-            return out
-        ops.conv_mfma(hc_rows, self.p_fc_fwd, R, 0, self.H, -(-self.V // 32) * 32, 1, EPI_PLAIN, pix_per_map=1,
-                      oc_split=self.V, bias=self.sd["fc.bias"], out0=out)
-        return out
+        return EngineBase.logits(self, hc_rows, fast)
 
     def greedy(self, enc, max_cap_length, start_id, end_id, model_bias=True):
         """GridTDModel.greedy_search (gridTDmodel.py:480-520): argmax per step; after the first <end> the
@@ -310,127 +287,34 @@ class GridTDEngine:
             toks[:, t + 1] = nxt * unfinished
         return toks
 
-    def beam_search(self, enc, beam_size, max_cap_length, start_id, end_id):
-        """`GridTDModel.beam_search` (models/gridTDmodel.py:400-478) for ONE image (enc of a single image, as the
-        reference asserts :411): returns the chosen token sequence incl. <start> (`seq`, :469-472)."""
-        from .beam import run_beam_search
-        assert enc["B"] == 1, "beam search captions one image (models/gridTDmodel.py:411)"
-        nb = int(beam_size)
-        encb = {k: (v.expand(nb, *v.shape[1:]).contiguous() if torch.is_tensor(v) else v) for k, v in enc.items()}
-        encb["B"] = nb
-        T = int(max_cap_length)
-        tr = self._alloc_trace(nb, T)
-        toks = torch.zeros(nb, T + 1, dtype=torch.int64, device=self.device)
+    # the decode loops of explainers/engine_base.py (beam_search, sample_lrp, forwardlrp_context) on this model's step
+    _BEAM_STATE = ("h1", "c1", "h2", "c2")
 
-        def step(t, prev):
-            toks[:, t] = prev
-            self._step(tr, encb, t, toks, True)
-
-        def reorder(t, src):
-            sel = torch.tensor(src, dtype=torch.int64, device=self.device)
-            for k in ("h1", "c1", "h2", "c2"):
-                tr[k][:len(src), t + 1] = tr[k][sel, t + 1]
-
-        return run_beam_search(step, lambda t: self.logits(tr["hc"][:, t].contiguous()), reorder, self.V, nb, T,
-                               start_id, end_id, self.device)
-
-    def sample_lrp(self, enc, max_length, start_id, end_id, skip_ids):
-        """GridTDModel.sample_lrp, greedy (gridTDmodel.py:631-702): LRP-inference decoding.  Every step's logits are
-        recomputed from the fc input re-weighted by the predicted word's relevance (`get_lrp_weight_step` :548-577)
-        before the next word is taken.  `skip_ids`: ids exempt from the re-weighting (the reference's STOP_WORDS and
-        special tokens).  Returns (seq int64 (B,max_length), seq_logprobs float32 (B,max_length)); like the reference,
-        tokens after <end> are 0 and nothing is written once every sequence has finished (:699-700)."""
-        lib = _lib.load()
-        B, T, H, E = enc["B"], max_length, self.H, self.E
-        W1 = 2 * E + 2 * H
-        dev = self.device
-        skip = torch.zeros(self.V, dtype=torch.uint8, device=dev)
-        skip[torch.as_tensor(sorted(int(i) for i in skip_ids), dtype=torch.int64, device=dev)] = 1
-        toks = torch.zeros(B, T + 1, dtype=torch.int64, device=dev)
-        toks[:, 0] = start_id
-        lps = torch.zeros(B, T, dtype=torch.float32, device=dev)
+    def _decode_trace(self, enc, B, T, lrp=False):
         tr = self._alloc_trace(B, T)
-        c = C.byref(tr["_c"])
-        xg = torch.empty(B, W1, device=dev)
-        zg = torch.empty(B, H, device=dev)
-        hcw = torch.empty(B, H, device=dev)
-        nxt = torch.empty(B, dtype=torch.int64, device=dev)
-        lp = torch.empty(B, dtype=torch.float32, device=dev)
-        w_gate, b_gate = self.Wcat1[4 * H:], self.bcat1[4 * H:]          # [x_gate | h_gate] rows of the fused weight
-        unfinished = torch.ones(B, dtype=torch.bool, device=dev)
+        if lrp:      # `sample_lrp` / `forwardlrp_context` run the model's own forward: the sentinel gate on the NEW h1 (gridTDmodel.py:617)
+            lib, H, W1 = _lib.load(), self.H, 2 * self.E + 2 * self.H
+            c = C.byref(tr["_c"])
+            xg, zg = torch.empty(B, W1, device=self.device), torch.empty(B, H, device=self.device)
+            w_gate, b_gate = self.Wcat1[4 * H:], self.bcat1[4 * H:]          # [x_gate | h_gate] rows of the fused weight
 
-        def sentinel_new_h(t):
-            st = stream_ptr()
-            check(lib.lrpx_gridtd_fwd_gate_input(c, t, ptr(xg), st))
-            check(lib.lrpx_linear_small(ptr(xg), W1, ptr(w_gate), ptr(b_gate), ptr(zg), H, B, W1, H, 0, st))
-            check(lib.lrpx_gridtd_fwd_sentinel(c, t, ptr(zg), H, st))
+            def sentinel_new_h(t):
+                st = stream_ptr()
+                check(lib.lrpx_gridtd_fwd_gate_input(c, t, ptr(xg), st))
+                check(lib.lrpx_linear_small(ptr(xg), W1, ptr(w_gate), ptr(b_gate), ptr(zg), H, B, W1, H, 0, st))
+                check(lib.lrpx_gridtd_fwd_sentinel(c, t, ptr(zg), H, st))
+            tr["_after_lstm1"] = sentinel_new_h
+        return tr
 
-        for t in range(T):
-            self._step(tr, enc, t, toks, True, after_lstm1=sentinel_new_h)
-            st = stream_ptr()
-            pred = self.logits(tr["hc"][:, t].contiguous())
-            check(lib.lrpx_gridtd_lrp_reweight(c, t, ptr(pred), self.V, self.V, ptr(self.sd["fc.weight"]), ptr(skip),
-                                               ptr(hcw), st))
-            wpred = self.logits(hcw)
-            check(lib.lrpx_argmax_logprob_rows(ptr(wpred), self.V, B, self.V, ptr(nxt), ptr(lp), st))
-            alive = unfinished.any()                                        # the reference's `break` (:699-700)
-            unfinished = unfinished & (nxt != end_id)
-            toks[:, t + 1] = torch.where(alive, nxt * unfinished, torch.zeros_like(nxt))
-            lps[:, t] = torch.where(alive, lp, torch.zeros_like(lp))
-        return toks[:, 1:].contiguous(), lps
+    def _decode_step(self, tr, enc, t, toks):
+        self._step(tr, enc, t, toks, True, after_lstm1=tr.get("_after_lstm1"))
 
-    def forwardlrp_context(self, enc, captions, caption_lengths, skip_ids):
-        """The forward half of `GridTDModel.forwardlrp_context` (models/gridTDmodel.py:579-630; LRP-inference fine-tuning,
-        SURVEY §8(f) row 2): teacher-forced decoding with the model's own forward (sentinel gate on the NEW h1, :617) where
-        every step's scores are recomputed from the fc input re-weighted by the relevance of the step's arg-max word
-        (`get_lrp_weight_step`, :548-577).  captions (B, >= L) int64 incl. <start> in column 0; L = max(caption_lengths) - 1.
-        Returns (predictions (B,L,V), weighted_predictions (B,L,V), L).  The loss and its gradients (train.py:211-263)
-        are training and stay outside the path."""
-        lib = _lib.load()
-        B, H, E = enc["B"], self.H, self.E
-        L = int(max(caption_lengths)) - 1
-        W1 = 2 * E + 2 * H
-        dev = self.device
-        captions = captions.to(dev, torch.int64).contiguous()
-        assert captions.shape[0] == B and captions.shape[1] >= L
-        skip = torch.zeros(self.V, dtype=torch.uint8, device=dev)
-        skip[torch.as_tensor(sorted(int(i) for i in skip_ids), dtype=torch.int64, device=dev)] = 1
-        toks = captions[:, :L + 1].contiguous() if captions.shape[1] > L else torch.cat(
-            [captions, captions.new_zeros(B, 1)], 1).contiguous()          # column t is the input of step t
-        tr = self._alloc_trace(B, L)
-        c = C.byref(tr["_c"])
-        xg, zg, hcw = torch.empty(B, W1, device=dev), torch.empty(B, H, device=dev), torch.empty(B, H, device=dev)
-        w_gate, b_gate = self.Wcat1[4 * H:], self.bcat1[4 * H:]
-        preds = torch.empty(B, L, self.V, device=dev)
-        wpreds = torch.empty(B, L, self.V, device=dev)
-
-        def sentinel_new_h(t):
-            st = stream_ptr()
-            check(lib.lrpx_gridtd_fwd_gate_input(c, t, ptr(xg), st))
-            check(lib.lrpx_linear_small(ptr(xg), W1, ptr(w_gate), ptr(b_gate), ptr(zg), H, B, W1, H, 0, st))
-            check(lib.lrpx_gridtd_fwd_sentinel(c, t, ptr(zg), H, st))
-
-        for t in range(L):
-            self._step(tr, enc, t, toks, True, after_lstm1=sentinel_new_h)
-            pred = self.logits(tr["hc"][:, t].contiguous())
-            check(lib.lrpx_gridtd_lrp_reweight(c, t, ptr(pred), self.V, self.V, ptr(self.sd["fc.weight"]), ptr(skip),
-                                               ptr(hcw), stream_ptr()))
-            preds[:, t] = pred
-            wpreds[:, t] = self.logits(hcw)
-        return preds, wpreds, L
+    def _reweight(self, tr, t, pred, skip, hcw, log_softmax):
+        """`get_lrp_weight_step` (models/gridTDmodel.py:548-577): always on the raw scores"""
+        check(_lib.load().lrpx_gridtd_lrp_reweight(C.byref(tr["_c"]), t, ptr(pred), self.V, self.V, ptr(self.sd["fc.weight"]), ptr(skip),
+                                                   ptr(hcw), stream_ptr()))
 
     # ------------------------------------------------------------------------------------------
-    def _row_index(self, B, T):
-        key = (B, T)
-        if key not in self._idx_cache:
-            b = torch.arange(B, device=self.device).view(B, 1)
-            t = torch.arange(T, device=self.device).view(1, T)
-            s = torch.arange(T, device=self.device).view(T, 1, 1)
-            idx = (b * T + (t - s).clamp(min=0)).to(torch.int32).reshape(T, B * T).contiguous()
-            row2img = (b + 0 * t).to(torch.int32).reshape(B * T).contiguous()
-            self._idx_cache[key] = (idx, row2img)
-        return self._idx_cache[key]
-
     def relevance(self, enc, tr, lens=None, want_r_feat=True):
         """explain_caption_wordt (gridTDmodel.py:1014-1135) for every (image, word) row at once.
         Returns r_feat (B*T, P, C) relevance of the encoder output (NHWC), r_words (B*T, T) and the row -> image table.
@@ -452,7 +336,7 @@ class GridTDEngine:
         for k, v in rs.items():
             setattr(c, k, ptr(v))
         ctr, crs = C.byref(tr["_c"]), C.byref(c)
-        idx, row2img = self._row_index(B, T)
+        idx, row2img, _ = self._row_index(B, T)
         check(lib.lrpx_gridtd_rel_init(ctr, crs, ptr(self.sd["fc.weight"]), ptr(tr["logit"]), ptr(tr["captions"]),
                                        T + 1, st))
         W1 = 2 * E + 2 * H
@@ -481,79 +365,27 @@ class GridTDEngine:
         a_proj = e(n, P, H)
         check(lib.lrpx_gridtd_rel_pix_rows(ctr, crs, ptr(enc["Vp"]), ptr(enc["proj_pre"]), ptr(a_proj), ptr(rowlist), n, st))
         r_feat = e(n, P, Cc)
-        if self.p_proj_rel_h is not None and self._f16():
-            ops.conv_mfma(a_proj, self.p_proj_rel_h, n, 0, H, -(-Cc // 32) * 32, 1, EPI_REL, pix_per_map=P, oc_split=Cc,
-                          x=enc["feats"], u=U, map2img=row2img, out0=r_feat, f16x3=1, in_amax=ops.amax_maps(a_proj, n))
-        elif self.p_proj_rel_6 is not None and self.dense_bf16x6:
-            ops.conv_mfma(a_proj, self.p_proj_rel_6, n, 0, H, -(-Cc // 32) * 32, 1, EPI_REL, pix_per_map=P, oc_split=Cc,
-                          x=enc["feats"], u=U, map2img=row2img, out0=r_feat, bf16x6=1)
-        else:
-            ops.conv_mfma(a_proj, self.p_proj_rel, n, 0, H, Cc, 1, EPI_REL, pix_per_map=P, oc_split=Cc,
-                          x=enc["feats"], u=U, map2img=row2img, out0=r_feat)
+        self._proj_rule(a_proj, n, P, enc["feats"], row2img, r_feat, u=U)
         return r_feat, rs["r_words"], row2img
 
-    def explain_batch_graph(self, images, captions, accumulate=False, predictions=False):
-        """`explain_batch` replayed from a captured HIP graph (one graph per (B,T) shape): the ~450 kernel launches
-        of a step (decoder trace and lock-step relevance are launch-bound) are issued by one hipGraphLaunch instead
-        of the Python loop.  Inputs are copied into the graph's static buffers; the returned tensors are the graph's
-        static outputs (overwritten by the next call with the same shape)."""
-        self._refuse_resnet("explain_batch_graph", "the ResNet engine's trace has not been captured in a HIP graph (the recording is missing)")
+    def _static(self, graph, images, captions, accumulate, predictions, *key):
         images = images.to(self.device, torch.float32)
         captions = captions.to(self.device, torch.int64)
-        key = (tuple(images.shape), tuple(captions.shape), bool(accumulate), bool(predictions), self._f16())
-        g = self._graphs.get(key) if hasattr(self, "_graphs") else None
-        if g is None:
-            if not hasattr(self, "_graphs"):
-                self._graphs = {}
-            st_img, st_cap = images.clone(), captions.clone()
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):                       # warm-up outside capture (kernel attributes, caches)
-                self.explain_batch(st_img, st_cap, accumulate=accumulate, predictions=predictions)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                out = self.explain_batch(st_img, st_cap, accumulate=accumulate, predictions=predictions)
-            g = self._graphs[key] = (graph, st_img, st_cap, out)
-        graph, st_img, st_cap, out = g
-        st_img.copy_(images)
-        st_cap.copy_(captions)
-        graph.replay()
-        return out
+        key = (tuple(images.shape), tuple(captions.shape), bool(accumulate), bool(predictions)) + key + (self._f16(),)
+        return self._static_step(graph, key, images, captions,
+                                 lambda i, c: self.explain_batch(i, c, accumulate=accumulate, predictions=predictions))
+
+    def explain_batch_graph(self, images, captions, accumulate=False, predictions=False):
+        """`explain_batch` replayed from a captured HIP graph, one per (B,T) shape (explainers/engine_base.py: `_static_step`)."""
+        self._refuse_resnet("explain_batch_graph", "the ResNet engine's trace has not been captured in a HIP graph (the recording is missing)")
+        return self._static(True, images, captions, accumulate, predictions)
 
     def explain_batch_replay(self, images, captions, accumulate=False, predictions=False):
-        """`explain_batch` as a RECORDED step (lrp_amd._lib.Recording): the first call with a given input shape runs the step eagerly
-        on static copies of the inputs and keeps its library calls - functions, arguments, and every buffer they point at; later calls
-        copy the inputs into those static buffers and issue the same calls again: the same kernels in the same order on the same
-        stream, as ordinary launches (they overlap with other streams' kernels like any launch; a HIP graph replay did not), without the
-        interpreter's ~9 us per launch.  Bit-identical to `explain_batch` by construction.  Like a graph's, the returned tensors are
-        the recording's static outputs: overwritten by the next call of the same shape on this engine (take `replica()`s for batches
-        in flight).  Captions of equal length only (`lens` makes the launch sequence data-dependent)."""
+        """`explain_batch` as a RECORDED step, one per input shape and stream (explainers/engine_base.py: `_static_step`)."""
         self._refuse_resnet("explain_batch_replay", "the recording of the ResNet engine's step (_lib.Recording has only been built and "
                             "checked around the VGG16 chain's calls) is missing")
-        src = images
-        src = src.to(self.device, torch.float32)
-        captions = captions.to(self.device, torch.int64)
-        key = (tuple(src.shape), tuple(captions.shape), bool(accumulate), bool(predictions), _lib.stream_ptr().value,
-               self.vgg.conv_mode if self.vgg is not None else None, self._f16())
-        if not hasattr(self, "_recordings"):
-            self._recordings = {}
-        rec = self._recordings.get(key)
-        if rec is None:
-            st_src, st_cap = src.clone(), captions.clone()
-            # warm-up outside the recording: one-time work (kernel attributes, index caches, workspace allocations) must not be replayed
-            self.explain_batch(st_src, st_cap, accumulate=accumulate, predictions=predictions)
-            rec = _lib.Recording()
-            with rec:
-                rec.result = self.explain_batch(st_src, st_cap, accumulate=accumulate, predictions=predictions)
-            rec.inputs = (st_src, st_cap)
-            self._recordings[key] = rec
-            return rec.result
-        st_src, st_cap = rec.inputs
-        st_src.copy_(src)
-        st_cap.copy_(captions)
-        return rec.replay()
+        return self._static(False, images, captions, accumulate, predictions, _lib.stream_ptr().value,
+                            self.vgg.conv_mode if self.vgg is not None else None)
 
     def guided_gradient(self, enc, tr, lens=None, mask_features=True):
         """ExplainiGridTDGuidedGradient.explain_caption_wordt (gridTDmodel.py:1588-1675) for every (image, word)
@@ -574,7 +406,7 @@ class GridTDEngine:
         for k, v in gs.items():
             setattr(c, k, ptr(v))
         ctr, cgs = C.byref(tr["_c"]), C.byref(c)
-        _, row2img = self._row_index(B, T)
+        _, row2img, _ = self._row_index(B, T)
         check(lib.lrpx_gridtd_grad_init(ctr, cgs, ptr(self.sd["fc.weight"]), ptr(tr["captions"]), T + 1, st))
         for s in range(T):
             check(lib.lrpx_gridtd_grad_step(ctr, cgs, s, 0, st))
@@ -604,15 +436,7 @@ class GridTDEngine:
         else:   # ExplainGridTDGradient.explain_caption_wordt (:1424-1505): same BPTT, no `features <= 0` gate
             mask = torch.ones(B, P, Cc, device=self.device, dtype=torch.float32)
         d_feat = e(rows, P, Cc)
-        if self.p_proj_rel_h is not None and self._f16():      # the split-fp16 GEMM of the relevance path (fp32-grade, 4x the fp32 MFMA's rate)
-            ops.conv_mfma(a_proj, self.p_proj_rel_h, rows, 0, H, -(-Cc // 32) * 32, 1, EPI_REL, pix_per_map=P, oc_split=Cc, x=mask,
-                          u=U, map2img=row2img, out0=d_feat, f16x3=1, in_amax=ops.amax_maps(a_proj, rows))
-        elif self.p_proj_rel_6 is not None and self.dense_bf16x6:
-            ops.conv_mfma(a_proj, self.p_proj_rel_6, rows, 0, H, -(-Cc // 32) * 32, 1, EPI_REL, pix_per_map=P, oc_split=Cc, x=mask,
-                          u=U, map2img=row2img, out0=d_feat, bf16x6=1)
-        else:
-            ops.conv_mfma(a_proj, self.p_proj_rel, rows, 0, H, Cc, 1, EPI_REL, pix_per_map=P, oc_split=Cc, x=mask, u=U,
-                          map2img=row2img, out0=d_feat)                                          # :1668, :1674
+        self._proj_rule(a_proj, rows, P, mask, row2img, d_feat, u=U)                                  # :1668, :1674
         return d_feat, gs["r_words"], row2img
 
     def explain_batch_guided(self, images, captions, lens=None, return_features=False, gradcam=False):
@@ -628,20 +452,13 @@ class GridTDEngine:
         tr = self.trace(enc, captions, predictions=False, grad=True)
         rg = ragged(lens, B, T, self.device)
         d_feat, r_words, row2img = self.guided_gradient(enc, tr, rg)
-        if d_feat.shape[0] == 0:                  # every caption empty
-            maps = d_feat.new_zeros(0, 3, 224, 224)
-        else:
+
+        def maps_of(d_feat, row2img):
             maps = self.vgg.guided_backprop(d_feat, row2img)
             if gradcam:
                 maps = ops.guided_gradcam(maps, self.grad_cam(enc, d_feat, row2img), int(round(self.P ** 0.5)))
-        if rg is not None and not rg.full:        # back to the padded (image, word) layout, zeros behind the last word
-            maps = ops.scatter_maps(maps, rg)
-            if return_features:
-                d_feat = ops.scatter_maps(d_feat, rg)
-        out = (maps.view(B, T, 3, 224, 224), r_words.view(B, T, T))
-        if return_features:
-            out = out + (d_feat.view(B, T, self.P, self.C), tr, enc)
-        return out
+            return maps
+        return self._finish(rg, B, T, d_feat, r_words, row2img, maps_of, (3, 224, 224), features=(tr, enc) if return_features else None)
 
     def explain_batch_gradient(self, images, captions, lens=None, cam=False, return_features=False):
         """Batched `ExplainGridTDGradient.explain_caption` (models/gridTDmodel.py:1214-1539): plain
@@ -655,29 +472,8 @@ class GridTDEngine:
         tr = self.trace(enc, captions, predictions=False, grad=True)
         rg = ragged(lens, B, T, self.device)
         d_feat, r_words, row2img = self.guided_gradient(enc, tr, rg, mask_features=False)
-        if d_feat.shape[0] == 0:
-            maps = d_feat.new_zeros((0, self.P) if cam else (0, 3, 224, 224))
-        elif cam:
-            maps = self.grad_cam(enc, d_feat, row2img)
-        else:
-            maps = self.vgg.gradient(d_feat, row2img)
-        if rg is not None and not rg.full:
-            maps = ops.scatter_maps(maps, rg)
-            if return_features:
-                d_feat = ops.scatter_maps(d_feat, rg)
-        maps = maps.view(B, T, self.P) if cam else maps.view(B, T, 3, 224, 224)
-        out = (maps, r_words.view(B, T, T))
-        if return_features:
-            out = out + (d_feat.view(B, T, self.P, self.C), tr, enc)
-        return out
-
-    def grad_cam(self, enc, d_feat, row2img):
-        """`grad_cam` (models/gridTDmodel.py:1760-1771) for every (image, word) row: (rows,P,C) gradients -> (rows,P)."""
-        rows = d_feat.shape[0]
-        cam = torch.empty(rows, self.P, device=self.device, dtype=torch.float32)
-        check(_lib.load().lrpx_gradcam(ptr(enc["feats"]), ptr(d_feat.contiguous()), ptr(row2img), ptr(cam), rows, self.P,
-                                       self.C, stream_ptr()))
-        return cam
+        return self._finish(rg, B, T, d_feat, r_words, row2img, (lambda d, m: self.grad_cam(enc, d, m)) if cam else self.vgg.gradient,
+                            (self.P,) if cam else (3, 224, 224), features=(tr, enc) if return_features else None)
 
     def explain_batch(self, images, captions, lens=None, accumulate=False, return_features=False, predictions=False):
         """Batched `explain_caption` (gridTDmodel.py:1141-1156): images (B,3,H,W) - 224 x 224 for VGG16, what gives P feature pixels for
@@ -693,236 +489,72 @@ class GridTDEngine:
         tr = self.trace(enc, captions, predictions=predictions)
         rg = ragged(lens, B, T, self.device)
         r_feat, r_words, row2img = self.relevance(enc, tr, rg)
-        if rg is not None and not rg.full:
-            # unequal caption lengths (models/gridTDmodel.py:1147-1153 explains `caption_length` words): the chain runs on
-            # the sum(lens) valid maps; the result goes back to the padded layout (running sums per image over ITS words)
-            maps = self.cnn.relevance(r_feat, row2img) if rg.n else r_feat.new_zeros(0, *images.shape[1:])
-            maps = ops.scatter_maps(maps, rg, accumulate=accumulate)
-            if return_features:
-                r_feat = ops.scatter_maps(r_feat, rg)
-        else:
-            maps = self.cnn.relevance(r_feat, row2img)
-            if accumulate:
-                maps = ops.cumsum_maps(maps, B, T)
-        out = (maps.view(B, T, *images.shape[1:]), r_words.view(B, T, T))
-        if predictions:
-            out = out + (tr["pred"],)
-        if return_features:
-            out = out + (r_feat.view(B, T, self.P, self.C), tr, enc)
-        return out
-
-    def _f16(self):
-        """the decoder GEMMs on the fp16 split products?  (ops.decoder_f16: with conv modes 2 / 3 only - the engine's own `vgg.conv_mode` or the
-        process default; `force_f16` overrides per engine).  With a ResNet encoder the mode is the engine's `encoder_conv_mode` (0 / 1):
-        never, whatever `lrpx_set_conv_mode` says."""
-        if self.force_f16 is not None:
-            return bool(self.force_f16)
-        if self.resnet:
-            return ops.decoder_f16(self.encoder_conv_mode)
-        return ops.decoder_f16(self.vgg.conv_mode if self.vgg is not None else None)
-
-    def replica(self):
-        """A second execution context over the SAME weights (device tensors and packed blobs are shared): own VGG16
-        trace / workspace buffers, so two batches can be in flight on two HIP streams."""
-        import copy
-        r = copy.copy(self)
-        r.cnn = self.cnn.replica()
-        r.vgg = None if self.resnet else r.cnn
-        r._idx_cache = {}
-        for k in ("_graphs", "_replicas", "_streams", "_recordings"):     # a replica never shares another engine's streams / buffer sets
-            r.__dict__.pop(k, None)
-        return r
+        # unequal caption lengths (models/gridTDmodel.py:1147-1153 explains `caption_length` words): the chain runs on the
+        # sum(lens) valid maps; `_finish` takes the result back to the padded layout
+        return self._finish(rg, B, T, r_feat, r_words, row2img, self.cnn.relevance, tuple(images.shape[1:]), accumulate=accumulate,
+                            extra=(tr["pred"],) if predictions else (), features=(tr, enc) if return_features else None)
 
     def explain_stream(self, batches, depth=3, accumulate=False):
-        """Explain an iterable of independent (images, captions) batches with `depth` batches in flight, each on its own
-        HIP stream and buffer set.  Batches are independent (no exchange step), and roughly a seventh of
-        a batch's time is the decoder's lock-step chain of small latency-bound kernels: it overlaps the MFMA-bound CNN
-        relevance chain of the neighbouring batch.  Yields (maps, r_words) in input order; each result is complete
-        (its stream has been synchronised) when it is yielded.  Results are bit-identical to `explain_batch`."""
-        depth = max(1, int(depth))
-        if not hasattr(self, "_replicas"):
-            self._replicas, self._streams = [self], [torch.cuda.Stream(device=self.device)]
-        while len(self._replicas) < depth:
-            self._replicas.append(self.replica())
-            self._streams.append(torch.cuda.Stream(device=self.device))
-        pending = []
-        for i, batch in enumerate(batches):
-            images, captions = batch[0], batch[1]
-            lens = batch[2] if len(batch) > 2 else None                 # (images, captions[, lens])
-            k = i % depth
-            st = self._streams[k]
-            st.wait_stream(torch.cuda.current_stream(self.device))     # inputs produced on the caller's stream
-            with torch.cuda.stream(st):
-                out = self._replicas[k].explain_batch(images, captions, lens=lens, accumulate=accumulate)
-                ev = torch.cuda.Event()
-                ev.record(st)
-            for t in out:
-                t.record_stream(torch.cuda.current_stream(self.device))
-            # the side stream reads the caller's tensors (`.to()` copies nothing when they already are device fp32 / int64):
-            # keep them alive until the batch's event has completed, or the caching allocator could hand their memory to
-            # the caller's next batch while this one is still queued
-            pending.append((out, ev, images, captions))
-            if len(pending) >= depth:
-                o, e, _, _ = pending.pop(0)
-                e.synchronize()
-                yield o
-        for o, e, _, _ in pending:
-            e.synchronize()
-            yield o
+        """`explain_batch` over an iterable of (images, captions[, lens]) batches, `depth` in flight (explainers/engine_base.py)."""
+        return self._explain_stream(batches, depth, lambda eng, images, captions, lens: eng.explain_batch(images, captions, lens=lens,
+                                                                                                         accumulate=accumulate))
 
 
 # ------------------------------------------------------------------------------------------------
 # drop-in explainer (models/gridTDmodel.py:705-1211)
 # ------------------------------------------------------------------------------------------------
-class ExplainGridTDAttention(object):
+class ExplainGridTDAttention(ExplainerBase):
     """Same constructor, attributes and methods as the reference's `ExplainGridTDAttention`
     (models/gridTDmodel.py:705-1156): `explain_caption(img_filepath) -> (relevance_imgs, relevance_preceeding_words)`,
     `explain_caption_wordt(t)`, `explain_cnn(R)`, `teacherforce_forward(img, ids)`; attributes `.model .word_map .img
-    .beam_caption .beam_caption_encode .predictions .alphas .betas .args`.
-
-    `model` may be the reference's `GridTDModel` (any nn.Module with that `state_dict`), a `state_dict`, or None
-    (then `args.weight` is loaded like :717-718).  Without `caption_encode=` the image is captioned as the reference does
-    it (`beam_search(beam_size=2, max_cap_length=50)`, :935-937; `GridTDEngine.beam_search`), so the same caption is
-    explained.  Nothing is written to disk (visualisation is out of scope).
+    .beam_caption .beam_caption_encode .predictions .alphas .betas .args`.  Conventions: explainers/dropin.py; the caption the
+    reference explains is `beam_search(beam_size=2, max_cap_length=50)` (:935-937).
 
     ResNet encoders (`args.encoder` 'resnet101' / 'renset50', models/gridTDmodel.py:26-31): a `GridTDModel` hands over its
     `model.img_encoder.encoder` (used as it is when it lives on the GPU, rebuilt from the state dict otherwise); a state dict or
     `args.weight` with models/resnet.py key names is built by `ops.bottleneck_resnet_from_state`.  `args.height` / `args.width` size
     the images (448 x 448 for the reference's 196 attention pixels); `args.encoder_conv_mode` (optional, default 1) is the
     engine's.  The gradient-family subclasses refuse such a model (NotImplementedError)."""
-    EPS = 0.01
-    EX_TYPE = 'lrp'
     NEEDS_ENCODER_GRADIENT = False      # the gradient family: VGG16 only
 
-    def __init__(self, args, word_map, model=None):
-        self.args = args
-        self.word_map = word_map
-        self.vocab_size = len(word_map)
-        # one device engine per weight set (explainers/engine_cache.py): evaluation.py:806-838 builds an explainer per image
+    def _engine_key(self):
         from . import engine_cache
-        mode = getattr(args, "encoder_conv_mode", 1)
-        key = engine_cache.fingerprint("gridtd", args.weight if model is None else model, extra=() if mode == 1 else (("encoder_conv_mode", mode),))
-        cls = type(self).__name__
+        mode = getattr(self.args, "encoder_conv_mode", 1)
+        return engine_cache.fingerprint("gridtd", self.args.weight if self.model is None else self.model,
+                                        extra=() if mode == 1 else (("encoder_conv_mode", mode),))
 
-        def refuse():
-            raise NotImplementedError("{}: not built for a ResNet encoder - {}".format(cls, GridTDEngine.GRADIENT_MISSING))
+    def _refuse_resnet(self):
+        raise NotImplementedError("{}: not built for a ResNet encoder - {}".format(type(self).__name__, GridTDEngine.GRADIENT_MISSING))
 
-        def build():
-            encoder = None
-            if model is None:
-                state = torch.load(args.weight, map_location="cpu")['state_dict']
-            elif hasattr(model, "state_dict"):
-                state = model.state_dict()
-                enc = getattr(getattr(model, "img_encoder", None), "encoder", None)
-                if resnet_encoder_keys(state) and isinstance(enc, torch.nn.Module) and all(
-                        t.device.type == "cuda" for t in list(enc.parameters()) + list(enc.buffers())):
-                    encoder = enc                  # the model's own module (else: rebuilt from the same tensors by the engine)
-            else:
-                state = model
-            if self.NEEDS_ENCODER_GRADIENT and resnet_encoder_keys(state):
-                refuse()                           # before anything is uploaded
-            return GridTDEngine(state, encoder=encoder, encoder_conv_mode=mode)
-        self.model = model
-        # the weights are shared, the trace / workspace buffers are this explainer's own: two live explainers never see each other's image
-        # (the state dict of a model holds its encoder's tensors too: key and `hold` cover the module as they cover the state)
-        engine = engine_cache.get(key, build, hold=engine_cache.source_tensors(model))
+    def _build_engine(self, state):
+        encoder = None
+        if hasattr(self.model, "state_dict"):
+            enc = getattr(getattr(self.model, "img_encoder", None), "encoder", None)
+            if resnet_encoder_keys(state) and isinstance(enc, torch.nn.Module) and all(
+                    t.device.type == "cuda" for t in list(enc.parameters()) + list(enc.buffers())):
+                encoder = enc                  # the model's own module (else: rebuilt from the same tensors by the engine)
+        if self.NEEDS_ENCODER_GRADIENT and resnet_encoder_keys(state):
+            self._refuse_resnet()              # before anything is uploaded
+        return GridTDEngine(state, encoder=encoder, encoder_conv_mode=getattr(self.args, "encoder_conv_mode", 1))
+
+    def _accept_engine(self, engine):
         if self.NEEDS_ENCODER_GRADIENT and engine.resnet:
-            refuse()
-        self.engine = engine.replica()
-        self.mean = list(IMAGENET_MEAN)
-        self.std = list(IMAGENET_STD)
-        self.rev_word_map = {v: k for k, v in word_map.items()}
-
-    def preprocess_img(self, img_filepath):
-        """Resize -> ToTensor -> Normalize (models/gridTDmodel.py:767-771), host side."""
-        return load_image(img_filepath, getattr(self.args, "height", 224), getattr(self.args, "width", 224), self.mean, self.std,
-                          self.engine.device)
+            self._refuse_resnet()
 
     def get_hidden_parameters(self, img, caption_encode=None, max_cap_length=50):
         """Forward trace (:933-1012).  `img`: file path or a (1,3,H,W) tensor of the encoder's image size (224 x 224 for VGG16)."""
-        self.img = self.preprocess_img(img) if isinstance(img, str) else img.to(self.engine.device, torch.float32)
-        eng = self.engine
-        # a caption that is handed over goes to the device BEFORE the encoder is enqueued: the copy of a pageable host list waits for the
-        # stream, and behind the VGG16 forward it stalled the host for 1 ms per call (the device then idled until the decoder was issued)
-        cap_dev = None if caption_encode is None else torch.tensor([[int(c) for c in caption_encode]], dtype=torch.int64, device=eng.device)
-        self._enc = eng.encode(self.img)
-        if caption_encode is None:
-            from .beam import caption_from_sequence
-            seq = eng.beam_search(self._enc, 2, max_cap_length, self.word_map['<start>'], self.word_map['<end>'])   # :935
-            caption_encode = caption_from_sequence(seq, self.word_map)
-        self.beam_caption_encode = [int(c) for c in caption_encode]
-        special = {self.word_map[k] for k in ('<start>', '<end>', '<unk>', '<pad>') if k in self.word_map}
-        self.beam_caption = [' '.join(self.rev_word_map.get(c, str(c)) for c in self.beam_caption_encode[1:]
-                                      if c not in special)]
-        self.caption_length = len(self.beam_caption_encode) - 1
-        self.num_pixels = eng.P
-        self._rel = None
-        if self.caption_length == 0:
-            return
-        cap = cap_dev if cap_dev is not None else torch.tensor([self.beam_caption_encode], dtype=torch.int64, device=eng.device)
-        self._cap_dev = cap
-        self._tr = eng.trace(self._enc, cap, predictions=True)
-        self.image_features = ops.nhwc_to_nchw(self._enc["feats"].contiguous(), eng.C, *eng.cnn.feat_hw)
-        self.num_pixels = eng.P
-        self.predictions = self._tr["pred"][0]
-        self.alphas = self._tr["alpha"][0]
-        self.betas = self._tr["beta"][0]
-        self._rel = None
+        self._hidden_parameters(img, caption_encode, 2, max_cap_length)
 
-    def _relevance(self):
-        if self._rel is None:
-            self._rel = self.engine.relevance(self._enc, self._tr)
-        return self._rel
+    def _explain_rows(self, head_idx):
+        return self.engine.relevance(self._enc, self._tr)
 
     def explain_caption_wordt(self, t):
         """(:1014-1135) -> (r_img_feature (1,C,h,w), r_words (t+1,))"""
-        assert t < self.caption_length
-        r_feat, r_words, _ = self._relevance()
-        r = ops.nhwc_to_nchw(r_feat[t:t + 1].contiguous(), self.engine.C, *self.engine.cnn.feat_hw)
-        return r, r_words[t, :t + 1].clone()
-
-    def explain_cnn(self, r_img_feature):
-        """(:1137-1139) — `compute_lrp` on `self.img`; like the reference the result accumulates over calls on
-        the same image (`sample.grad`, lrp_wrapper.py:64-82)."""
-        t_nhwc = ops.nchw_to_nhwc(r_img_feature.to(torch.float32))
-        r = self.engine.cnn.relevance(t_nhwc, torch.zeros(r_img_feature.shape[0], dtype=torch.int32,
-                                                          device=self.engine.device))
-        if getattr(self, "_img_grad", None) is None:
-            self._img_grad = r
-        else:
-            check(_lib.load().lrpx_accumulate(ptr(self._img_grad), ptr(r), r.numel(), stream_ptr()))
-        ops.check_relevance(self._img_grad, finite=True, nonzero=True)
-        return self._img_grad.clone()
+        return self._explain_wordt(t)
 
     def explain_caption(self, img_filepath, t_list=None, caption_encode=None):
-        """(:1141-1156) -> ([T] x (1,3,H,W), [T] x (t+1,)); maps are the reference's running sums."""
-        self.img_filepath = img_filepath
-        self.get_hidden_parameters(img_filepath, caption_encode)
-        if self.caption_length == 0:          # the beam search produced <end> first: nothing to explain (empty lists, :1147-1156)
-            return [], []
-        self._img_grad = None
-        r_feat, r_words, row2img = self._relevance()
-        maps = self.engine.cnn.relevance(r_feat, row2img)
-        maps = ops.cumsum_maps(maps, 1, self.caption_length)
-        ops.check_relevance(maps, finite=True, nonzero=True)
-        relevance_imgs = [maps[t:t + 1] for t in range(self.caption_length)]
-        relevance_preceeding_words = [r_words[t, :t + 1] for t in range(self.caption_length)]
-        assert len(relevance_imgs) == self.caption_length
-        return relevance_imgs, relevance_preceeding_words
-
-    TF_MODEL_BIAS = False      # the LRP explainer's LanguageLSTM forward adds bias_ih twice (:789); the gradient family's is correct (:1265)
-
-    def teacherforce_forward(self, img, beam_caption_encode):
-        """(:892-931; gradient family :1282-1321) -> predictions (len(beam_caption_encode), V) under teacher forcing: step t reads
-        token t - evaluation.py:266,437 hands the caption WITH <start> - with this explainer's own forward."""
-        eng = self.engine
-        if isinstance(img, str):
-            img = self.preprocess_img(img)
-        enc = eng.encode(img.to(eng.device, torch.float32))
-        cap = torch.tensor([[int(c) for c in beam_caption_encode] + [0]], dtype=torch.int64, device=eng.device)
-        n = cap.shape[1] - 1
-        tr = eng.trace(enc, cap, model_bias=self.TF_MODEL_BIAS, predictions=False)
-        return eng.logits(tr["hc"].view(n, eng.H))       # the fp32 kernel of the decoding loops, at any caption length
+        """(:1141-1156) -> ([T] x (1,3,H,W), [T] x (t+1,)); the LRP maps are the reference's running sums."""
+        return self._explain_caption(img_filepath, caption_encode)
 
 
 class ExplainiGridTDGuidedGradient(ExplainGridTDAttention):
@@ -931,34 +563,21 @@ class ExplainiGridTDGuidedGradient(ExplainGridTDAttention):
     EX_TYPE = 'GuidedBackpropagate'
     TF_MODEL_BIAS = True
     NEEDS_ENCODER_GRADIENT = True
+    _RUNNING_SUMS = False
 
     def get_hidden_parameters(self, img, caption_encode=None, max_cap_length=50):
         super().get_hidden_parameters(img, caption_encode, max_cap_length)
-        if self.caption_length == 0:
-            return
-        self._tr = self.engine.trace(self._enc, self._cap_dev, predictions=True, grad=True)     # :1323-1422 (correct LSTM bias)
-        self.predictions = self._tr["pred"][0]
-        self.alphas, self.betas = self._tr["alpha"][0], self._tr["beta"][0]
+        if self.caption_length:
+            self._trace(grad=True)             # :1323-1422 (correct LSTM bias)
 
-    def _relevance(self):
-        if self._rel is None:
-            self._rel = self.engine.guided_gradient(self._enc, self._tr)
-        return self._rel
+    def _explain_rows(self, head_idx):
+        return self.engine.guided_gradient(self._enc, self._tr)
 
-    def explain_cnn(self, d_img_feature):
-        t_nhwc = ops.nchw_to_nhwc(d_img_feature.to(torch.float32))
-        return self.engine.vgg.guided_backprop(t_nhwc, torch.zeros(d_img_feature.shape[0], dtype=torch.int32,
-                                                                   device=self.engine.device))
+    def _cnn(self, d_feat, row2img):
+        return self.engine.vgg.guided_backprop(d_feat, row2img)
 
-    def explain_caption(self, img_filepath, t_list=None, caption_encode=None):
-        self.img_filepath = img_filepath
-        self.get_hidden_parameters(img_filepath, caption_encode)
-        if self.caption_length == 0:          # the beam search produced <end> first: nothing to explain (empty lists, :1147-1156)
-            return [], []
-        d_feat, r_words, row2img = self._relevance()
-        maps = self.engine.vgg.guided_backprop(d_feat, row2img)
-        return ([maps[t:t + 1] for t in range(self.caption_length)],
-                [r_words[t, :t + 1] for t in range(self.caption_length)])
+    def explain_cnn(self, d_img_feature):          # (the reference's argument name in this family)
+        return super().explain_cnn(d_img_feature)
 
 
 class ExplainGridTDGuidedGradCam(ExplainiGridTDGuidedGradient):
@@ -969,29 +588,17 @@ class ExplainGridTDGuidedGradCam(ExplainiGridTDGuidedGradient):
 
     def grad_cam(self, img_feature, grads):
         """(1,C,h,w) features and gradients -> (h, w) heat map (:1799-1810)"""
-        f = ops.nchw_to_nhwc(img_feature.to(torch.float32))
-        g = ops.nchw_to_nhwc(grads.to(torch.float32))
-        P, Cc = f.shape[1], f.shape[2]
-        cam = torch.empty(1, P, device=self.engine.device, dtype=torch.float32)
-        check(_lib.load().lrpx_gradcam(ptr(f), ptr(g), ptr(None), ptr(cam), 1, P, Cc, stream_ptr()))
-        return cam.view(img_feature.shape[-2], img_feature.shape[-1])
+        return _grad_cam_one(img_feature, grads).view(img_feature.shape[-2], img_feature.shape[-1])
 
     def explain_cnn(self, d_img_feature):
-        guided = super().explain_cnn(d_img_feature)
+        guided = self.engine.vgg.guided_backprop(*self._one_map(d_img_feature))
         cam = self.grad_cam(self.image_features, d_img_feature).reshape(1, -1)
         return ops.guided_gradcam(guided, cam, self.image_features.shape[-1])
 
-    def explain_caption(self, img_filepath, t_list=None, caption_encode=None):
-        self.img_filepath = img_filepath
-        self.get_hidden_parameters(img_filepath, caption_encode)
-        if self.caption_length == 0:          # the beam search produced <end> first: nothing to explain (empty lists, :1147-1156)
-            return [], []
-        d_feat, r_words, row2img = self._relevance()
+    def _cnn(self, d_feat, row2img):
         eng = self.engine
-        maps = ops.guided_gradcam(eng.vgg.guided_backprop(d_feat, row2img), eng.grad_cam(self._enc, d_feat, row2img),
+        return ops.guided_gradcam(eng.vgg.guided_backprop(d_feat, row2img), eng.grad_cam(self._enc, d_feat, row2img),
                                   int(round(eng.P ** 0.5)))
-        return ([maps[t:t + 1] for t in range(self.caption_length)],
-                [r_words[t, :t + 1] for t in range(self.caption_length)])
 
 
 class ExplainGridTDGradient(ExplainiGridTDGuidedGradient):
@@ -1001,27 +608,10 @@ class ExplainGridTDGradient(ExplainiGridTDGuidedGradient):
     inheritance runs the other way, the surface is the same.)"""
     EX_TYPE = 'gradient'
 
-    def _relevance(self):
-        if self._rel is None:
-            self._rel = self.engine.guided_gradient(self._enc, self._tr, mask_features=False)
-        return self._rel
+    def _explain_rows(self, head_idx):
+        return self.engine.guided_gradient(self._enc, self._tr, mask_features=False)
 
-    def explain_cnn(self, d_img_feature):
-        t_nhwc = ops.nchw_to_nhwc(d_img_feature.to(torch.float32))
-        return self.engine.vgg.gradient(t_nhwc, torch.zeros(d_img_feature.shape[0], dtype=torch.int32,
-                                                            device=self.engine.device))
-
-    def explain_caption(self, img_filepath, t_list=None, caption_encode=None):
-        self.img_filepath = img_filepath
-        self.get_hidden_parameters(img_filepath, caption_encode)
-        if self.caption_length == 0:          # the beam search produced <end> first: nothing to explain (empty lists, :1147-1156)
-            return [], []
-        d_feat, r_words, row2img = self._relevance()
-        maps = self._maps(d_feat, row2img)
-        return ([maps[t:t + 1] for t in range(self.caption_length)],
-                [r_words[t, :t + 1] for t in range(self.caption_length)])
-
-    def _maps(self, d_feat, row2img):
+    def _cnn(self, d_feat, row2img):
         return self.engine.vgg.gradient(d_feat, row2img)
 
 
@@ -1032,15 +622,19 @@ class ExplainGridTDGradCam(ExplainGridTDGradient):
 
     def grad_cam(self, img_feature, grads):
         """(1,C,h,w) features and gradients -> (h*w,) heat map, as the reference's method of the same name."""
-        f = ops.nchw_to_nhwc(img_feature.to(torch.float32))
-        g = ops.nchw_to_nhwc(grads.to(torch.float32))
-        P, Cc = f.shape[1], f.shape[2]
-        cam = torch.empty(1, P, device=self.engine.device, dtype=torch.float32)
-        check(_lib.load().lrpx_gradcam(ptr(f), ptr(g), ptr(None), ptr(cam), 1, P, Cc, stream_ptr()))
-        return cam.view(-1)
+        return _grad_cam_one(img_feature, grads).view(-1)
 
     def explain_cnn(self, d_img_feature):
         return self.grad_cam(self.image_features, d_img_feature).unsqueeze(0)
 
-    def _maps(self, d_feat, row2img):
+    def _cnn(self, d_feat, row2img):
         return self.engine.grad_cam(self._enc, d_feat, row2img)
+
+
+def _grad_cam_one(img_feature, grads):
+    """(1,C,h,w) features and gradients at them -> the (1, h*w) Grad-CAM heat map (:1760-1771, :1799-1810)"""
+    f = ops.nchw_to_nhwc(img_feature.to(torch.float32))
+    g = ops.nchw_to_nhwc(grads.to(torch.float32))
+    cam = torch.empty(1, f.shape[1], device=f.device, dtype=torch.float32)
+    check(_lib.load().lrpx_gradcam(ptr(f), ptr(g), ptr(None), ptr(cam), 1, f.shape[1], f.shape[2], stream_ptr()))
+    return cam
