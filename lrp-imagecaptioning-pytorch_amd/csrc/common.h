@@ -69,6 +69,10 @@ int divide_stab_blocked(const float* r, const float* z, const int32_t* map2img, 
 // max|x| over a flat tensor, atomically max-ed into *out as float bits (lrpx_core.hip)
 int amax_flat(const float* x, long n, unsigned* out, hipStream_t stream);
 
+// zero `bytes` bytes at dst on the stream (lrpx_core.hip): every clear of the library goes through here - hipMemsetAsync, a kernel while
+// the stream is being captured into a HIP graph
+int clear_async(void* dst, size_t bytes, hipStream_t stream);
+
 // hipFuncAttributeMaxDynamicSharedMemorySize of one kernel instantiation.  HIP function attributes are PER DEVICE, and one
 // host process may drive several GPUs from several threads (include/lrpx.h THREADING), so the attribute is set exactly once
 // per (instantiation, device ordinal) even when several host threads make their first launch of it at the same time

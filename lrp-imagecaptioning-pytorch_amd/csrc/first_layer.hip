@@ -300,10 +300,7 @@ int first_layer_relevance(const float* S, const float* w6, const float* X8, cons
 }
 
 int first_layer_pack_mfma(const float* w, float* packed, int plain, hipStream_t s) {
-    if (hipMemsetAsync(packed, 0, F16X3_HEADER_FLOATS * sizeof(float), s) != hipSuccess) {
-        set_error("first_layer_pack_mfma: memset failed");
-        return LRPX_ELAUNCH;
-    }
+    LRPX_TRY(clear_async(packed, F16X3_HEADER_FLOATS * sizeof(float), s));
     LRPX_TRY(amax_flat(w, 64 * 3 * 9, reinterpret_cast<unsigned*>(packed) + 1, s));
     hipLaunchKernelGGL(pack_first_layer_mfma_kernel, dim3((2 * 9 * 64 * 8 + 255) / 256), dim3(256), 0, s, w, packed, plain);
     return check_launch("pack_first_layer_mfma");

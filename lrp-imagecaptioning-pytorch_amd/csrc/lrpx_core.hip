@@ -281,6 +281,44 @@ int amax_flat(const float* x, long n, unsigned* out, hipStream_t s) {
     return check_launch("amax_flat");
 }
 
+// dst[0 .. head + 16 n16 + tail) = 0: bytes up to the first 16-byte boundary, 16-byte stores, the bytes behind the last whole one
+__global__ void clear_kernel(unsigned char* __restrict__ dst, unsigned head, size_t n16, unsigned tail) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint4* body = reinterpret_cast<uint4*>(dst + head);
+    for (size_t k = i; k < n16; k += (size_t)gridDim.x * blockDim.x) body[k] = uint4{0u, 0u, 0u, 0u};
+    if (i < head) dst[i] = 0;
+    if (i < tail) dst[head + n16 * 16 + i] = 0;
+}
+
+// Every clear of the library.  On a stream that is not being captured: hipMemsetAsync, as ever (the eager and the recorded step keep
+// their launches).  While the stream is captured into a HIP graph (explain_batch_graph): the kernel above, one launch.  A
+// hipMemsetAsync captured as a memset node cleared on the first launch of the graph only (HIP 7.0): later launches filled the range
+// with a stray 16-byte pattern, and the elements that nothing but the clear writes (h[:, 0], c[:, 0] and the amax rows of a decoder
+// trace) made every later replay differ from the eager step (tests/test_gpu_graph_primitives.py).  A kernel node clears.
+int clear_async(void* dst, size_t bytes, hipStream_t s) {
+    if (!bytes) return LRPX_OK;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap) != hipSuccess) {
+        set_error("clear: cannot query the stream's capture status");
+        return LRPX_ELAUNCH;
+    }
+    if (cap == hipStreamCaptureStatusNone) {
+        if (hipMemsetAsync(dst, 0, bytes, s) != hipSuccess) {
+            set_error("clear: hipMemsetAsync failed");
+            return LRPX_ELAUNCH;
+        }
+        return LRPX_OK;
+    }
+    const size_t to16 = (16 - (reinterpret_cast<uintptr_t>(dst) & 15)) & 15;
+    const unsigned head = (unsigned)(bytes < to16 ? bytes : to16);
+    const size_t n16 = (bytes - head) / 16;
+    const unsigned tail = (unsigned)(bytes - head - n16 * 16);
+    const size_t blocks = ceil_div((long)n16, 256);
+    hipLaunchKernelGGL(clear_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks > 4096 ? 4096 : blocks)), dim3(256), 0, s,
+                       static_cast<unsigned char*>(dst), head, n16, tail);
+    return check_launch("clear");
+}
+
 // lane-local |max| of 4 values -> per-map amax.  Waves whose 64 lanes sit in one map (every layer of the path) reduce
 // in registers and issue one atomic; mixed waves fall back to one atomic per lane.
 __device__ __forceinline__ void amax_commit(unsigned* __restrict__ amax, long n, float m) {
@@ -1315,10 +1353,7 @@ int lrpx_unpool_winner(const float* s_lo, const uint8_t* am, const int32_t* map2
 int lrpx_amax_maps(const float* s, int n_maps, long per, uint32_t* amax, void* stream) {
     LRPX_CHECK_PTRS("lrpx_amax_maps", {s, "s"}, {amax, "amax"});
     LRPX_REQUIRE(s && amax && n_maps > 0 && per > 0 && per % 4 == 0, "amax_maps: bad arguments (per %% 4)");
-    if (hipMemsetAsync(amax, 0, (size_t)n_maps * sizeof(uint32_t), (hipStream_t)stream) != hipSuccess) {
-        set_error("amax_maps: memset failed");
-        return LRPX_ELAUNCH;
-    }
+    LRPX_TRY(clear_async(amax, (size_t)n_maps * sizeof(uint32_t), (hipStream_t)stream));
     const long per4 = per / 4, total = (long)n_maps * per4;
     // ITER float4 per thread where 256 * ITER divides a map (one atomic per block of 256 * ITER float4, ITER loads in flight per thread)
     const long q = per4 % 256 == 0 ? per4 / 256 : 0;
@@ -1352,10 +1387,7 @@ int lrpx_pack_weights_f16f8(const float* w, int cout, int cin, int mode, void* p
     int n_oc_pad, k_pad;
     pack_dims(cout, cin, mode, 16, &n_oc_pad, &k_pad);
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(packed, 0, F16X3_HEADER_FLOATS * sizeof(float), st) != hipSuccess) {
-        set_error("pack_weights_f16f8: memset failed");
-        return LRPX_ELAUNCH;
-    }
+    LRPX_TRY(clear_async(packed, F16X3_HEADER_FLOATS * sizeof(float), st));
     hipLaunchKernelGGL(amax_flat_kernel, dim3(256), dim3(256), 0, st, w, (long)cout * cin * 9, (unsigned*)packed + 1);
     const long total = (long)(n_oc_pad / 32) * (k_pad / 16) * 3 * 64;
     hipLaunchKernelGGL(pack_weights_f16f8_kernel, dim3(grid_for(total)), dim3(256), 0, st, w, (float*)packed, cout, cin,
@@ -1371,10 +1403,7 @@ int lrpx_pack_weights_f16x2(const float* w, int cout, int cin, int taps, int mod
     int n_oc_pad, k_pad;
     pack_dims(cout, cin, mode, 16, &n_oc_pad, &k_pad);
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(packed, 0, F16X3_HEADER_FLOATS * sizeof(float), st) != hipSuccess) {
-        set_error("pack_weights_f16x2: memset failed");
-        return LRPX_ELAUNCH;
-    }
+    LRPX_TRY(clear_async(packed, F16X3_HEADER_FLOATS * sizeof(float), st));
     // layer scale from max|w| (an upper bound for every mode's transformed weights)
     const long nw = (long)cout * cin * taps;
     hipLaunchKernelGGL(amax_flat_kernel, dim3(256), dim3(256), 0, st, w, nw, (unsigned*)packed + 1);
@@ -1425,11 +1454,7 @@ int lrpx_scatter_maps(const float* in, float* out, int n_img, int t_per_img, con
 int lrpx_zero(void* dst, size_t bytes, void* stream) {
     LRPX_REQUIRE(dst || bytes == 0, "zero: null pointer");
     LRPX_CHECK_PTRS_OPT("lrpx_zero", {dst, "dst"});
-    if (bytes && hipMemsetAsync(dst, 0, bytes, (hipStream_t)stream) != hipSuccess) {
-        set_error("zero: hipMemsetAsync failed");
-        return LRPX_ELAUNCH;
-    }
-    return LRPX_OK;
+    return clear_async(dst, bytes, (hipStream_t)stream);
 }
 
 int lrpx_gather_rows(const void* src, const int32_t* rows, void* dst, int n_rows, int width, void* stream) {

@@ -327,10 +327,7 @@ int lrpx_maxpool_rule(const float* x, const float* r_out, float* r_in, long plan
 int lrpx_max_abs_diff(const float* a, const float* b, long n, float* out_dev, void* stream) {
     LRPX_REQUIRE(a && b && out_dev && n > 0, "max_abs_diff: bad arguments");
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(out_dev, 0, sizeof(float), st) != hipSuccess) {
-        set_error("max_abs_diff: cannot zero the result");
-        return LRPX_ELAUNCH;
-    }
+    LRPX_TRY(clear_async(out_dev, sizeof(float), st));
     const unsigned blocks = (unsigned)min((long)2048, ceil_div(n, 256));
     hipLaunchKernelGGL(max_abs_diff_kernel, dim3(blocks), dim3(256), 0, st, a, b, n, reinterpret_cast<unsigned*>(out_dev));
     return check_launch("max_abs_diff");

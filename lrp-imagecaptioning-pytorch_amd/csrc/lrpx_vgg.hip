@@ -67,10 +67,7 @@ int conv_dispatch(const lrpx_conv_desc* d, hipStream_t s, int f16_ksplit) {
         ((d->epi == EPI_REL) || (d->epi == EPI_PLAIN && !d->relu))) {
         a.ksplit = d->cin / kc >= 16 ? 4 : 2;
         const int ncol = d->oc_split;
-        if (hipMemsetAsync(d->out0, 0, (size_t)d->n_maps * a.pix_per_map * ncol * sizeof(float), s) != hipSuccess) {
-            set_error("conv_mfma: cannot zero the split-K output");
-            return LRPX_ELAUNCH;
-        }
+        LRPX_TRY(clear_async(d->out0, (size_t)d->n_maps * a.pix_per_map * ncol * sizeof(float), s));
     }
     LRPX_REQUIRE(a.pix_per_map > 0, "conv_mfma: pix_per_map must be positive");
     LRPX_REQUIRE((long)a.n_maps * a.pix_per_map < 0x7fffffffL, "conv_mfma: too many pixels for 32-bit indexing");
@@ -779,10 +776,7 @@ int lrpx_vgg16_forward_ex(const void* packed, const float* img_nchw, int n_img, 
     const VggTrace t = vgg_trace_layout(n_img);
     const float* pk = (const float*)packed;
     float* tr = (float*)trace;
-    if (fwd_f16 && mode >= 2 && hipMemsetAsync(tr + t.famax, 0, (size_t)18 * n_img * sizeof(unsigned), (hipStream_t)stream) != hipSuccess) {
-        set_error("vgg16_forward: cannot zero the amax words");
-        return LRPX_ELAUNCH;
-    }
+    if (fwd_f16 && mode >= 2) LRPX_TRY(clear_async(tr + t.famax, (size_t)18 * n_img * sizeof(unsigned), (hipStream_t)stream));
     // the signed image is kept split into x+ / x- (channels 0-2 / 3-5 of 8): Z of the first conv needs both
     LRPX_TRY(lrpx_nchw_to_nhwc_posneg(img_nchw, tr + t.act[0], n_img, 3, 224 * 224, 8, stream));
     bool pools_fused = false, pools_plain = false;
@@ -951,10 +945,7 @@ int lrpx_vgg16_relevance_ex(const void* packed, const void* trace, int n_img, co
     const bool b6 = mode == 1 && !switches().x6_legacy;
     const bool fused = h3 || b6;
     unsigned* amax = h3 ? reinterpret_cast<unsigned*>(R + (size_t)112 * 112 * 64 * n_maps) : nullptr;
-    if (h3 && hipMemsetAsync(amax, 0, (size_t)kNL * n_maps * sizeof(unsigned), (hipStream_t)stream) != hipSuccess) {
-        set_error("vgg16_relevance: cannot zero the amax words");
-        return LRPX_ELAUNCH;
-    }
+    if (h3) LRPX_TRY(clear_async(amax, (size_t)kNL * n_maps * sizeof(unsigned), (hipStream_t)stream));
     // mode 3: every S tensor of the chain and the multiplicands are BLOCKED (blocked.h), the kernels accumulate channels x pixels
     const bool blk = mode == 3;
     // S_16 = R_feat / safe(Z+_16)
@@ -1115,10 +1106,7 @@ static int vgg16_backprop(const void* packed, const void* trace, int n_img, cons
     const bool b6 = mode == 1 && !switches().x6_legacy && !switches().guided_poolbwd;
     unsigned* gam = reinterpret_cast<unsigned*>(R + (size_t)112 * 112 * 64 * n_maps);
     if (h3) {
-        if (hipMemsetAsync(gam, 0, (size_t)kNL * n_maps * sizeof(unsigned), st) != hipSuccess) {
-            set_error("vgg16_guided_backprop: cannot zero the amax words");
-            return LRPX_ELAUNCH;
-        }
+        LRPX_TRY(clear_async(gam, (size_t)kNL * n_maps * sizeof(unsigned), st));
         LRPX_TRY(lrpx_amax_maps(G[cur], n_maps, (long)196 * 512, gam + (size_t)16 * n_maps, st));
     }
     for (int l = kNL - 1; l >= 0; --l) {

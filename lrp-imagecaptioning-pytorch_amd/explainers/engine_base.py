@@ -198,8 +198,9 @@ class EngineBase(object):
 
         HIP graph: the launches of a step (~450 with the VGG16 chain, ~330 bottom-up) issued by one hipGraphLaunch.  Worth it for a
         SINGLE batch in flight (the host issues ~4 us per launch); with batches in flight on several streams eager launches are faster
-        (bottom-up, B = 32: 442 000 maps/s eager against 343 000 - 391 000 replayed) - a replayed graph does not overlap with its
-        neighbours the way independent kernels do.
+        (profiles/graph_replay_fix.txt) - a replayed graph does not overlap with its neighbours the way independent kernels do.
+        Every replay is bit-identical to the eager step too (tests/test_gpu_graph_replay.py): the library clears with a kernel while
+        its stream is being captured (csrc/lrpx_core.hip: clear_async; a captured hipMemsetAsync did not clear a trace's arena on replay).
 
         Either way the returned tensors are the static outputs: overwritten by the next call with the same key on this engine (take
         `replica()`s for batches in flight)."""

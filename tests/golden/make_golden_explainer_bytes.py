@@ -15,22 +15,23 @@ Groups (one engine each, the smallest shapes that take every branch of the share
   aoa_bu          bottom-up AoA, 36 x 2048 regions, V 503, B 4, T 5 (tests/test_gpu_replay.py's shapes): heads 2 and 5, lens None and
                   [5, 1, 3, 0]; explain_batch, explain_batch_replay (recording call + a replay on new inputs, call names kept);
                   sample_lrp, forwardlrp_context, beam_search of image 0
-  aoa_bu_graph    the same engine and inputs: explain_batch_graph of heads 2 and 5, the capturing call (capture + first replay) only
+  aoa_bu_graph    the same engine and inputs: explain_batch_graph of heads 2 and 5, the capturing call (capture + first replay) and a
+                  later replay on new inputs
   gridtd_resnet_mode0 / _mode1
                   the net and decoder of tests/test_gpu_gridtd_resnet.py (B 2, T 3, P 12, C 192, 45 x 51): explain_batch with lens None
                   and [3, 1], accumulate both ways, predictions and features returned; explain_stream at depth 2 over three batches;
                   greedy, sample_lrp, forwardlrp_context, beam_search
   gridtd_vgg      VGG16, V 307, B 2, T 2, lens None and [2, 1]: explain_batch (accumulate both ways), explain_batch_replay,
                   explain_batch_guided (gradcam both ways), explain_batch_gradient (cam both ways)
-  gridtd_vgg_graph  the same engine and inputs: explain_batch_graph, the capturing call only
+  gridtd_vgg_graph  the same engine and inputs: explain_batch_graph, the capturing call and a later replay on new inputs
   aoa_vgg         VGG16, head 3, same sizes: explain_batch, explain_batch_gradient of the four kinds
   dropin_gridtd / dropin_aoa
                   the five classes of each model on those VGG16 states: explain_caption of a tensor image without a caption (the beam
                   path) and with a three-word caption, explain_caption_wordt(1), explain_cnn twice (the accumulation),
                   teacherforce_forward, the attributes of the trace; AoA also explain_caption_words
 
-GRAPH_NOTE says why the graph groups stop at the capturing call.  None of these entry points takes an output buffer, so there is
-nothing to pre-fill.  Each group stores one digest of its inputs, so that a changed draw is told apart from a changed explainer."""
+GRAPH_NOTE says where the digests of the graph groups' later replays come from.  None of these entry points takes an output buffer, so
+there is nothing to pre-fill.  Each group stores one digest of its inputs, so that a changed draw is told apart from a changed explainer."""
 import argparse
 import hashlib
 import json
@@ -49,9 +50,12 @@ from make_golden_resnet import bottleneck_net  # noqa: E402
 
 JSON = os.path.join(HERE, "explainer_bytes.json")
 SKIP = [1, 2, 3, 5, 8, 13]
-GRAPH_NOTE = ("explain_batch_graph: only the capturing call (capture + first replay) is digested.  On the recorded commit every later replay of a "
-              "captured graph, on new inputs or on the captured ones, differs from the eager step (bottom-up AoA, B 4, T 5: r_words off by up to "
-              "2.0) and from one process to the next, in all three graph cases; the case moved to the nearest stable one, the first replay.")
+GRAPH_NOTE = ("explain_batch_graph: the capturing call (capture + first replay, *_call0) was digested from the graph itself.  On the recorded "
+              "commit every later replay of a captured graph differed from the eager step (bottom-up AoA, B 4, T 5: r_words off by up to 2.0) and "
+              "from one process to the next, so the digests of the later replays (*_call1, new inputs) are those of the EAGER step on the same "
+              "inputs: what a replay has to give (tests/test_gpu_graph_replay.py).  The generator takes them from `explain_batch`, the test from "
+              "the replayed graph.")
+RECORDING = False          # True while the generator records (run_all): the later replays of the graph groups come from the eager step
 
 
 def sha(*items):
@@ -111,6 +115,8 @@ def aoa_bu(graph=False):
     if graph:
         for head in (2, 5):
             _put(res, "graph_h%d_call0" % head, eng.explain_batch_graph(caps[0], head, features=feats[0], predictions=True))
+            later = eng.explain_batch if RECORDING else eng.explain_batch_graph
+            _put(res, "graph_h%d_call1" % head, later(caps[1], head, features=feats[1], predictions=True))
         return digest, res, []
     wm = weights.make_word_map(V)
     enc = eng.encode(features=feats[0])
@@ -190,9 +196,11 @@ def gridtd_vgg_graph():
     imgs, caps = _vgg_inputs()
     digest = sha(*imgs, *caps, *[v for _, v in sorted(sd.items())])
     eng = GridTDEngine(sd)
+    imgs, caps = [torch.from_numpy(f).cuda() for f in imgs], [torch.from_numpy(c).cuda() for c in caps]
     res = {}
-    _put(res, "graph_call0", eng.explain_batch_graph(torch.from_numpy(imgs[0]).cuda(), torch.from_numpy(caps[0]).cuda(), accumulate=True,
-                                                     predictions=True))
+    _put(res, "graph_call0", eng.explain_batch_graph(imgs[0], caps[0], accumulate=True, predictions=True))
+    later = eng.explain_batch if RECORDING else eng.explain_batch_graph
+    _put(res, "graph_call1", later(imgs[1], caps[1], accumulate=True, predictions=True))
     return digest, res, []
 
 
@@ -276,6 +284,8 @@ def run_all():
     import lrp_amd  # noqa: F401
     if not torch.cuda.is_available():
         raise SystemExit("make_golden_explainer_bytes: needs a GPU")
+    global RECORDING
+    RECORDING = True
     cases = {}
     for name, fn in GROUPS.items():
         digest, res, calls = fn()
