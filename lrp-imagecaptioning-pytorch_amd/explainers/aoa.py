@@ -1,7 +1,8 @@
 """Batched AoA (attention-on-attention, 8-head) LRP engine + the drop-in `ExplainAOAAttention` explainer.
 
 Reference: models/aoamodel.py:748-1254.  Also serves the bottom-up variant (36 x 2048 region features, no CNN
-stage; SURVEY §8(a) row A-BU): pass `features=` instead of images.  Host logic only sequences HIP kernels."""
+stage; SURVEY §8(a) row A-BU): pass `features=` instead of images.  The encoder is VGG16 or a bottleneck ResNet.
+Host logic only sequences HIP kernels."""
 import ctypes as C
 
 import numpy as np
@@ -11,28 +12,29 @@ from .. import _lib, ops
 from .._lib import (AoaGradState, AoaRelState, AoaStepArgs, AoaTrace, EPI_PLAIN, EPI_REL, PACK_DENSE, PACK_DENSE_T, STAB_EPS, check, ptr, ptr_at,
                     stream_ptr)
 from .dropin import ExplainerBase
-from .engine_base import EngineBase
-from .gridtd import VGG_PREFIX, _t
+from .engine_base import EngineBase, resnet_encoder_keys
 from .ragged import ragged
 
 
 class AOAEngine(EngineBase):
     """`state`: the reference `AOAModel` state_dict (models/aoamodel.py:116-142).  Without encoder weights
-    (bottom-up model, :1795-1797) only `features=` inputs are accepted."""
+    (bottom-up model, :1795-1797) only `features=` inputs are accepted.
+
+    The encoder (models/aoamodel.py:31-51) is chosen as `GridTDEngine`'s is (`EngineBase._init_encoder`): VGG16 from its keys, or
+    `ops.ResNetEncoder` from models/resnet.py key names (`ops.bottleneck_resnet_from_state`), in encoder conv mode 1 (the exact bf16
+    split).  `AOAResNetEngine` below is the same engine with the encoder handed over as a module and the mode as a parameter.
+    The attention runs over any number of pixels, so a ResNet encoder takes any image size it accepts (the reference's default
+    224 x 224 gives P = 49 at C = 2048); only the channel count must be `img_projector`'s (`encode` checks).  DESIGN.md 5.13."""
+
+    _GUIDED_GRADCAM_MISSING = ("Guided Grad-CAM expands the heat map by a fixed 16 (models/aoamodel.py:1743), which is not the image at a "
+                              "ResNet's stride of 32: the reference's own class fails there")
+    _GRADCAM_MAX_PIXELS = 256          # lrpx_gradcam's limit on the pixels of a heat map
 
     def __init__(self, state, num_head=8, device="cuda"):
-        _lib.load()
-        if not torch.cuda.is_available():
-            raise _lib.LrpxError("the LRP hot path needs an MI355X; there is no CPU fallback")
-        dev = torch.device(device)
-        self.device = dev
-        sd = {k: _t(v, dev) for k, v in state.items() if not k.startswith(VGG_PREFIX)}
-        names = [k for k in state if k.startswith(VGG_PREFIX) and k.endswith(".weight")]
-        self.vgg = None
-        if names:
-            self.vgg = ops.Vgg16([_t(state[k], dev) for k in names],
-                                 [_t(state[k.replace(".weight", ".bias")], dev) for k in names])
-        self.cnn, self.resnet = self.vgg, False          # (the encoder as explainers/engine_base.py reads it: VGG16 or none)
+        self._build(state, num_head, device, None, 1)
+
+    def _build(self, state, num_head, device, encoder, encoder_conv_mode):
+        sd = self._init_encoder(state, device, encoder, encoder_conv_mode, need_encoder=False)          # (explainers/engine_base.py)
         self.sd = sd
         self.NH = num_head
         self.V, self.E = sd["embedding.weight"].shape
@@ -126,13 +128,15 @@ class AOAEngine(EngineBase):
     # ------------------------------------------------------------------------------------------
     def encode(self, images=None, features=None):
         """(:999-1009) image-side constants; `features`: (B,P,C) region/pixel features instead of images."""
-        lib = _lib.load()
-        st = stream_ptr()
         H, Cc = self.H, self.C
         if features is None:
-            if self.vgg is None:
+            if self.cnn is None:
                 raise ValueError("this AoA model has no encoder: pass features=(B,P,C)")
-            feats = self.vgg.forward(images.to(self.device, torch.float32).contiguous())
+            self._feature_pixels(images)          # (host arithmetic: a ResNet of another width is refused before any device work)
+        lib = _lib.load()
+        st = stream_ptr()
+        if features is None:
+            feats = self.cnn.forward(images.to(self.device, torch.float32).contiguous())
         else:
             feats = features.to(self.device, torch.float32).contiguous()
         B, P, _ = feats.shape
@@ -151,6 +155,19 @@ class AOAEngine(EngineBase):
         ops.conv_mfma(enc["Vp"], self.p_v_fwd, B, 0, H, H, 1, EPI_PLAIN, pix_per_map=P, oc_split=H,
                       bias=self.sd["decoder_v_proj.bias"], out0=enc["value"])
         return enc
+
+    def _feature_pixels(self, images):
+        """P = h w of the encoder's feature map for these images (host arithmetic).  A ResNet encoder whose feature channels are not
+        `img_projector`'s input width is refused here, before any kernel runs."""
+        if not self.resnet:
+            return self.cnn.feat_hw[0] * self.cnn.feat_hw[1]
+        if images.dim() != 4:
+            raise ValueError("{}: images must be (B, 3, H, W), got {}".format(type(self).__name__, tuple(images.shape)))
+        h, w, c = self.cnn.feature_shape(int(images.shape[2]), int(images.shape[3]))
+        if c != self.C:
+            raise ValueError("{}: the encoder gives {} feature channels; the decoder is built for {} (img_projector)".format(
+                type(self).__name__, c, self.C))
+        return h * w
 
     def _alloc_trace(self, B, T, P, grad=False):
         dev, H, E, NH = self.device, self.H, self.E, self.NH
@@ -350,7 +367,14 @@ class AOAEngine(EngineBase):
     def explain_batch_gradient(self, captions, head_idx, images, kind="gradient", lens=None, return_features=False):
         """Batched `explain_caption` of ExplainAOAGradient (kind="gradient", :1501-1534), ExplainAOAGuidedGradient
         ("guided", :1621-1640), ExplainAOAGradCam ("gradcam", :1669-1689; result (B,T,P) heat maps) and
-        ExplainAOAGuidedGradCam ("guided_gradcam", :1714-1751)."""
+        ExplainAOAGuidedGradCam ("guided_gradcam", :1714-1751; VGG16 only).  With a ResNet encoder the maps are
+        `ResNetEncoder.gradient` / `.guided_backprop(relus="stem")` (the reference hooks the encoder's direct children, :1596-1613: the
+        stem's ReLU alone) at the images' own size."""
+        if kind == "guided_gradcam":
+            self._refuse_resnet("explain_batch_gradient(kind='guided_gradcam')", self._GUIDED_GRADCAM_MISSING)
+        if kind == "gradcam" and self.cnn is not None and self._feature_pixels(images) > self._GRADCAM_MAX_PIXELS:           # before any launch
+            raise ValueError("{}: a feature map of {} pixels; Grad-CAM heat maps are built for at most {} (lrpx_gradcam)".format(
+                type(self).__name__, self._feature_pixels(images), self._GRADCAM_MAX_PIXELS))
         enc = self.encode(images)
         captions = captions.to(self.device, torch.int64).contiguous()
         B, T = captions.shape[0], captions.shape[1] - 1
@@ -363,13 +387,18 @@ class AOAEngine(EngineBase):
             if kind == "gradcam":
                 return self.grad_cam(enc, d_feat, row2img)
             if kind not in ("guided", "guided_gradcam"):
-                return self.vgg.gradient(d_feat, row2img)
-            maps = self.vgg.guided_backprop(d_feat, row2img)
+                return self.cnn.gradient(d_feat, row2img)
+            maps = self._guided_backprop(d_feat, row2img)
             if kind == "guided_gradcam":         # ExplainAOAGuidedGradCam (:1714-1751): x the expanded Grad-CAM map
                 maps = ops.guided_gradcam(maps, self.grad_cam(enc, d_feat, row2img), int(round(P ** 0.5)))
             return maps
-        return self._finish(rg, B, T, d_feat, r_words, row2img, maps_of, (P,) if kind == "gradcam" else (3, 224, 224),
+        return self._finish(rg, B, T, d_feat, r_words, row2img, maps_of, (P,) if kind == "gradcam" else tuple(images.shape[1:]),
                             features=(tr, enc) if return_features else None)
+
+    def _guided_backprop(self, d_feat, row2img):
+        if self.resnet:
+            return self.cnn.guided_backprop(d_feat, row2img, relus="stem")
+        return self.cnn.guided_backprop(d_feat, row2img)
 
     def relevance(self, enc, tr, head_idx, lens=None, compact=True):
         """explain_caption_wordt (:1064-1156) for every (image, word) row -> r_feat (B*T,P,C), r_words (B*T,T), row -> image.
@@ -449,7 +478,7 @@ class AOAEngine(EngineBase):
 
     def explain_batch(self, captions, head_idx, images=None, features=None, lens=None, accumulate=False,
                       return_features=False, predictions=False):
-        """Batched `explain_caption(img, head_idx)` (:1165-1181).  With images: maps (B,T,3,224,224); with
+        """Batched `explain_caption(img, head_idx)` (:1165-1181).  With images: maps (B,T,3,H,W), 224 x 224 for VGG16; with
         `features` (bottom-up): the region-feature relevance (B,T,P,C) is the result (no CNN stage).
         predictions=True keeps the (T,V) scores of the trace as the reference's explainer does (:1026)."""
         enc = self.encode(images, features)
@@ -463,7 +492,7 @@ class AOAEngine(EngineBase):
         r_feat, r_words, row2img = self.relevance(enc, tr, head_idx, rg)
         # unequal caption lengths (models/aoamodel.py:1171-1176 explains `caption_length` words): the VGG16 chain runs on the sum(lens)
         # valid maps; `_finish` takes the result back to the padded layout
-        return self._finish(rg, B, T, r_feat, r_words, row2img, self.vgg.relevance, (3, 224, 224), accumulate=accumulate,
+        return self._finish(rg, B, T, r_feat, r_words, row2img, self.cnn.relevance, tuple(images.shape[1:]), accumulate=accumulate,
                             features=(tr, enc) if return_features else None)
 
     def _static(self, graph, key, captions, head_idx, images, features, accumulate, predictions):
@@ -473,12 +502,16 @@ class AOAEngine(EngineBase):
 
     def explain_batch_graph(self, captions, head_idx, images=None, features=None, accumulate=False, predictions=False):
         """`explain_batch` replayed from a captured HIP graph, one per input shape and head (explainers/engine_base.py: `_static_step`)."""
+        if features is None:
+            self._refuse_resnet("explain_batch_graph", self._NO_GRAPH)
         src = features if features is not None else images
         key = (features is not None, tuple(src.shape), tuple(captions.shape), int(head_idx), bool(accumulate), bool(predictions), self._f16())
         return self._static(True, key, captions, head_idx, images, features, accumulate, predictions)
 
     def explain_batch_replay(self, captions, head_idx, images=None, features=None, accumulate=False, predictions=False):
         """`explain_batch` as a RECORDED step, one per input shape, head and stream (explainers/engine_base.py: `_static_step`)."""
+        if features is None:
+            self._refuse_resnet("explain_batch_replay", self._NO_RECORDING)
         src = features if features is not None else images
         key = (tuple(src.shape), tuple(captions.shape), bool(accumulate), bool(predictions), _lib.stream_ptr().value,
                self.vgg.conv_mode if self.vgg is not None else None, int(head_idx), features is not None, self._f16())
@@ -490,13 +523,33 @@ class AOAEngine(EngineBase):
             captions, head_idx, images=images, lens=lens, accumulate=accumulate))
 
 
+class AOAResNetEngine(AOAEngine):
+    """`AOAEngine` with the encoder's two parameters of `GridTDEngine`: `encoder`, an nn.Module on the GPU that
+    `ops.match_bottleneck_resnet` accepts (the model's own `img_encoder.encoder`; None: built from the state dict as `AOAEngine` does),
+    and `encoder_conv_mode`, the ResNet encoder engine's arithmetic (0: fp32 MFMA, 1: the exact bf16 split).  A mode outside {0, 1}, a
+    module that is not on the GPU and a BasicBlock / dilated / grouped net are refused before any device work.  (`AOAEngine` keeps the
+    constructor it has always had; everything else is inherited.)"""
+
+    def __init__(self, state, num_head=8, device="cuda", encoder=None, encoder_conv_mode=1):
+        self._build(state, num_head, device, encoder, encoder_conv_mode)
+
+
 class ExplainAOAAttention(ExplainerBase):
     """Drop-in for the reference's `ExplainAOAAttention` (models/aoamodel.py:748-1194), called as evaluation.py:637,702,767 call
     it: `explain_caption(img_filepath, head_idx)`, `explain_caption_wordt(t, head_idx)`, `explain_cnn(R)`,
     `explain_caption_words(img_filepath)`, `teacherforce_forward(img, beam_caption_encode)`, `get_hidden_parameters(img_filepath)`,
     `preprocess_img(img_filepath)`; attributes `.model .word_map .img .img_filepath .beam_caption .beam_caption_encode .predictions
     .alphas .args`.  Conventions: explainers/dropin.py; the caption the reference explains is its beam search with beam 3 over 20
-    steps (:992)."""
+    steps (:992).
+
+    ResNet encoders (`args.encoder` 'resnet101' / 'renset50', models/aoamodel.py:34-39): an `AOAModel` hands over its
+    `model.img_encoder.encoder` (used as it is when it lives on the GPU, rebuilt from the state dict otherwise); a state dict or
+    `args.weight` with models/resnet.py key names is built by `ops.bottleneck_resnet_from_state`.  `args.height` / `args.width` size the
+    images (any size the encoder accepts: the attention takes any number of pixels); `args.encoder_conv_mode` (optional, default 1)
+    is the engine's.  The gradient-family subclasses run on such a model too, except `ExplainAOAGuidedGradCam` (NotImplementedError:
+    the reference's own class fails at a stride of 32)."""
+
+    _REFUSES_RESNET = False      # (True: Guided Grad-CAM, VGG16 only)
 
     def __init__(self, args, word_map, model=None):
         self.num_head = getattr(args, "num_head", 8)
@@ -504,13 +557,38 @@ class ExplainAOAAttention(ExplainerBase):
 
     def _engine_key(self):
         from . import engine_cache
-        return engine_cache.fingerprint("aoa", self.args.weight if self.model is None else self.model, (self.num_head,))
+        extra = (self.num_head,)
+        if self.model is None:
+            resnet = getattr(self.args, "encoder", "vgg16") != "vgg16"            # ('resnet101' / 'renset50', models/aoamodel.py:34-39)
+        else:
+            resnet = resnet_encoder_keys(self.model.state_dict() if hasattr(self.model, "state_dict") else self.model)
+        if resnet:                                                                # a ResNet engine is built in ITS conv mode
+            extra += (("resnet", getattr(self.args, "encoder_conv_mode", 1)),)
+        return engine_cache.fingerprint("aoa", self.args.weight if self.model is None else self.model, extra)
+
+    def _refuse_resnet(self):
+        raise NotImplementedError("{}: not built for a ResNet encoder - {}".format(type(self).__name__, AOAEngine._GUIDED_GRADCAM_MISSING))
 
     def _build_engine(self, state):
-        return AOAEngine(state, self.num_head)
+        encoder = None
+        if hasattr(self.model, "state_dict"):
+            enc = getattr(getattr(self.model, "img_encoder", None), "encoder", None)
+            if resnet_encoder_keys(state) and isinstance(enc, torch.nn.Module) and all(
+                    t.device.type == "cuda" for t in list(enc.parameters()) + list(enc.buffers())):
+                encoder = enc                  # the model's own module (else: rebuilt from the same tensors by the engine)
+        if self._REFUSES_RESNET and resnet_encoder_keys(state):
+            self._refuse_resnet()              # before anything is uploaded
+        if not resnet_encoder_keys(state):
+            return AOAEngine(state, self.num_head)
+        return AOAResNetEngine(state, self.num_head, encoder=encoder, encoder_conv_mode=getattr(self.args, "encoder_conv_mode", 1))
+
+    def _accept_engine(self, engine):
+        if self._REFUSES_RESNET and engine.resnet:
+            self._refuse_resnet()
 
     def get_hidden_parameters(self, img, caption_encode=None):
-        """Forward trace (:990-1062).  `img`: file path (the reference's argument) or a (1,3,224,224) tensor."""
+        """Forward trace (:990-1062).  `img`: file path (the reference's argument) or a (1,3,H,W) tensor of the encoder's image size
+        (224 x 224 for VGG16; `args.height` / `args.width` size a file's image)."""
         self._hidden_parameters(img, caption_encode, 3, 20)
 
     def _explain_rows(self, head_idx):
@@ -551,7 +629,7 @@ class ExplainAOAGradient(ExplainAOAAttention):
         return self.engine.gradient(self._enc, self._tr, head_idx)
 
     def _cnn(self, d_feat_nhwc, row2img):
-        return self.engine.vgg.gradient(d_feat_nhwc, row2img)
+        return self.engine.cnn.gradient(d_feat_nhwc, row2img)
 
     def explain_cnn(self, d_img_feature):          # (the reference's argument name in this family)
         return super().explain_cnn(d_img_feature)
@@ -563,7 +641,7 @@ class ExplainAOAGuidedGradient(ExplainAOAGradient):
     EX_TYPE = 'GuidedBackpropagate'
 
     def _cnn(self, d_feat_nhwc, row2img):
-        return self.engine.vgg.guided_backprop(d_feat_nhwc, row2img)
+        return self.engine._guided_backprop(d_feat_nhwc, row2img)
 
 
 class ExplainAOAGuidedGradCam(ExplainAOAGuidedGradient):
@@ -571,6 +649,7 @@ class ExplainAOAGuidedGradCam(ExplainAOAGuidedGradient):
     the Grad-CAM heat map of the same decoder gradient, expanded 16x by `skimage.transform.pyramid_expand` (:1741; here
     one matrix product per axis, ops.pyramid_expand_matrix)."""
     EX_TYPE = 'GuidedGradCam'
+    _REFUSES_RESNET = True
 
     def _cnn(self, d_feat_nhwc, row2img):
         guided = self.engine.vgg.guided_backprop(d_feat_nhwc, row2img)

@@ -1,17 +1,34 @@
-"""What `GridTDEngine` (explainers/gridtd.py) and `AOAEngine` (explainers/aoa.py) share: the fc scores, the index tables, replicas, the
+"""What `GridTDEngine` (explainers/gridtd.py) and `AOAEngine` (explainers/aoa.py) share: the choice of the encoder (`_init_encoder`: VGG16,
+a bottleneck ResNet as a module or from its state-dict keys, or none), the fc scores, the index tables, replicas, the
 decode loops of the reference's models, the static-buffer drivers (HIP graph / recorded step), the stream pipeline, and the tail of
 every batch entry point.  Host logic only: it sequences the library calls of the engine's own `_step` / `relevance` / ... in the order
 the two engines each used to spell out.
 
 An engine provides: `device, sd, V, H, C, p_fc_fwd, p_fc_fwd_h, p_proj_rel, p_proj_rel_h, p_proj_rel_6, dense_bf16x6, force_f16`, the
-encoder as `cnn` (None: region features only), `vgg` (the same object when it is VGG16, else None) and `resnet`, and the hooks
+encoder as `cnn` (None: region features only), `vgg` (the same object when it is VGG16, else None) and `resnet` (all three set by
+`_init_encoder`), and the hooks
 `_decode_trace`, `_decode_step`, `_reweight`, `_BEAM_STATE`."""
 import copy
 
+import numpy as np
 import torch
 
 from .. import _lib, ops
 from .._lib import EPI_PLAIN, EPI_REL, check, ptr, stream_ptr
+
+VGG_PREFIX = "img_encoder.encoder."
+
+
+def _t(v, dev):
+    if isinstance(v, np.ndarray):
+        v = torch.from_numpy(v)
+    return v.detach().to(device=dev, dtype=torch.float32).contiguous()
+
+
+def resnet_encoder_keys(state):
+    """does the state dict hold a bottleneck ResNet under `img_encoder.encoder.` (key names of models/resnet.py) rather than VGG16's
+    numbered `features` layers?"""
+    return VGG_PREFIX + "conv1.weight" in state
 
 
 class _CapturedGraph(object):
@@ -30,6 +47,54 @@ class _CapturedGraph(object):
 
 class EngineBase(object):
     _BEAM_STATE = ()                  # trace tensors (B, T+1, H) a beam search reorders with its beams
+    _ENCODER_CONV_MODES = (0, 1)
+
+    # ---- the encoder ---------------------------------------------------------------------------------------------------------------------
+    def _init_encoder(self, state, device, encoder, encoder_conv_mode, need_encoder=True):
+        """The head of both engines' constructors: the encoder (models/gridTDmodel.py:23-37, models/aoamodel.py:31-51) as `self.cnn` -
+        `ops.Vgg16` built from the VGG16 keys under `img_encoder.encoder.` (`self.vgg` is then the same object), or `ops.ResNetEncoder`:
+        from `encoder=`, an nn.Module on the GPU that `ops.match_bottleneck_resnet` accepts, or from a state dict whose encoder keys are
+        those of models/resnet.py (`ops.bottleneck_resnet_from_state`).  A mode or a net the ResNet engine does not run is refused by
+        host logic, before any device work.  need_encoder=False: a state without encoder keys gives `cnn = None` (region features
+        only).  Sets `device, encoder_conv_mode, cnn, vgg, resnet`; returns the other tensors of `state` on the device."""
+        name = type(self).__name__
+        if isinstance(encoder_conv_mode, bool) or encoder_conv_mode not in self._ENCODER_CONV_MODES:
+            raise ValueError("{}: encoder_conv_mode {!r}: the ResNet encoder engine has modes 0 (fp32 MFMA) and 1 (exact bf16 "
+                             "split)".format(name, encoder_conv_mode))
+        self.encoder_conv_mode = encoder_conv_mode
+        from_state = encoder is None and resnet_encoder_keys(state)
+        if encoder is not None:
+            ops.match_bottleneck_resnet(encoder)          # host logic: a net the engine does not run is refused before any device work
+            tensors = list(encoder.parameters()) + list(encoder.buffers())
+            if not tensors or any(t.device.type != "cuda" for t in tensors):
+                raise ValueError("ResNetEncoder: the model must live on the GPU (no CPU path)")
+        elif from_state:
+            encoder = ops.bottleneck_resnet_from_state(state, VGG_PREFIX)
+        _lib.load()   # fail loudly without the HIP library
+        if not torch.cuda.is_available():
+            raise _lib.LrpxError("the LRP hot path needs an MI355X; there is no CPU fallback")
+        dev = torch.device(device)
+        self.device = dev
+        sd = {k: _t(v, dev) for k, v in state.items() if not k.startswith(VGG_PREFIX)}
+        self.vgg = None
+        if encoder is not None:
+            self.cnn = ops.ResNetEncoder(encoder.to(dev) if from_state else encoder, conv_mode=encoder_conv_mode)
+        else:
+            names = [k for k in state if k.startswith(VGG_PREFIX) and k.endswith(".weight")]
+            if names or need_encoder:
+                self.vgg = ops.Vgg16([_t(state[k], dev) for k in names],
+                                     [_t(state[k.replace(".weight", ".bias")], dev) for k in names])
+            self.cnn = self.vgg
+        self.resnet = encoder is not None
+        return sd
+
+    def _refuse_resnet(self, entry, missing):
+        if self.resnet:
+            raise NotImplementedError("{}.{}: not built for a ResNet encoder - {}".format(type(self).__name__, entry, missing))
+
+    _NO_GRAPH = "the ResNet engine's trace has not been captured in a HIP graph (the recording is missing)"
+    _NO_RECORDING = ("the recording of the ResNet engine's step (_lib.Recording has only been built and checked around the VGG16 chain's "
+                    "calls) is missing")
 
     # ---- hooks -------------------------------------------------------------------------------------------------------------------------
     def _decode_trace(self, enc, B, T, lrp=False):

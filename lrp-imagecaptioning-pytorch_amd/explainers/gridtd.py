@@ -6,29 +6,14 @@ and explained in lock-step by HIP kernels behind the lrpx C ABI (see csrc/lrpx_d
 The host logic below only sequences kernel launches; torch is used for device memory."""
 import ctypes as C
 
-import numpy as np
 import torch
 
 from .. import _lib, ops
 from .._lib import (EPI_PLAIN, EPI_REL, GridGradState, GridRelState, GridStepArgs, GridTrace, PACK_DENSE, PACK_DENSE_T, check, ptr,
                     ptr_at, stream_ptr)
 from .dropin import ExplainerBase
-from .engine_base import EngineBase
+from .engine_base import VGG_PREFIX, EngineBase, _t, resnet_encoder_keys  # noqa: F401  (the names are read from here too)
 from .ragged import ragged
-
-VGG_PREFIX = "img_encoder.encoder."
-
-
-def _t(v, dev):
-    if isinstance(v, np.ndarray):
-        v = torch.from_numpy(v)
-    return v.detach().to(device=dev, dtype=torch.float32).contiguous()
-
-
-def resnet_encoder_keys(state):
-    """does the state dict hold a bottleneck ResNet under `img_encoder.encoder.` (key names of models/resnet.py) rather than VGG16's
-    numbered `features` layers?"""
-    return VGG_PREFIX + "conv1.weight" in state
 
 
 class GridTDEngine(EngineBase):
@@ -43,33 +28,10 @@ class GridTDEngine(EngineBase):
     come from the images and the encoder; the decoder's own sizes C (`img_projector`) and P (`AdaAttention.W_v_proj`: 196 in the
     reference, :127 - a stride-32 ResNet therefore runs at 448 x 448) must match them (`encode` checks).  DESIGN.md 5.11."""
 
-    ENCODER_CONV_MODES = (0, 1)
+    ENCODER_CONV_MODES = EngineBase._ENCODER_CONV_MODES
 
     def __init__(self, state, device="cuda", encoder=None, encoder_conv_mode=1):
-        if isinstance(encoder_conv_mode, bool) or encoder_conv_mode not in self.ENCODER_CONV_MODES:
-            raise ValueError("GridTDEngine: encoder_conv_mode {!r}: the ResNet encoder engine has modes 0 (fp32 MFMA) and 1 (exact bf16 "
-                             "split)".format(encoder_conv_mode))
-        self.encoder_conv_mode = encoder_conv_mode
-        from_state = encoder is None and resnet_encoder_keys(state)
-        if encoder is not None:
-            ops.match_bottleneck_resnet(encoder)          # host logic: a net the engine does not run is refused before any device work
-        elif from_state:
-            encoder = ops.bottleneck_resnet_from_state(state, VGG_PREFIX)
-        _lib.load()   # fail loudly without the HIP library
-        if not torch.cuda.is_available():
-            raise _lib.LrpxError("the LRP hot path needs an MI355X; there is no CPU fallback")
-        dev = torch.device(device)
-        self.device = dev
-        sd = {k: _t(v, dev) for k, v in state.items() if not k.startswith(VGG_PREFIX)}
-        if encoder is not None:
-            self.vgg = None
-            self.cnn = ops.ResNetEncoder(encoder.to(dev) if from_state else encoder, conv_mode=encoder_conv_mode)
-        else:
-            names = [k for k in state if k.startswith(VGG_PREFIX) and k.endswith(".weight")]
-            self.vgg = ops.Vgg16([_t(state[k], dev) for k in names],
-                                 [_t(state[k.replace(".weight", ".bias")], dev) for k in names])
-            self.cnn = self.vgg
-        self.resnet = encoder is not None
+        sd = self._init_encoder(state, device, encoder, encoder_conv_mode)          # (explainers/engine_base.py)
         self.sd = sd
         self.V, self.E = sd["embedding.weight"].shape
         self.H = sd["fc.weight"].shape[1]
@@ -169,10 +131,6 @@ class GridTDEngine(EngineBase):
                              "pixels (AdaAttention.W_v_proj) of {} channels (img_projector)".format(
                                  int(images.shape[2]), int(images.shape[3]), h, w, h * w, c, self.P, self.C))
         return h, w
-
-    def _refuse_resnet(self, entry, missing):
-        if self.resnet:
-            raise NotImplementedError("GridTDEngine.{}: not built for a ResNet encoder - {}".format(entry, missing))
 
     GRADIENT_MISSING = "the gradient chain through the ResNet encoder (guided backprop / plain gradient of ops.ResNetEncoder) is missing"
 
@@ -377,13 +335,12 @@ class GridTDEngine(EngineBase):
 
     def explain_batch_graph(self, images, captions, accumulate=False, predictions=False):
         """`explain_batch` replayed from a captured HIP graph, one per (B,T) shape (explainers/engine_base.py: `_static_step`)."""
-        self._refuse_resnet("explain_batch_graph", "the ResNet engine's trace has not been captured in a HIP graph (the recording is missing)")
+        self._refuse_resnet("explain_batch_graph", self._NO_GRAPH)
         return self._static(True, images, captions, accumulate, predictions)
 
     def explain_batch_replay(self, images, captions, accumulate=False, predictions=False):
         """`explain_batch` as a RECORDED step, one per input shape and stream (explainers/engine_base.py: `_static_step`)."""
-        self._refuse_resnet("explain_batch_replay", "the recording of the ResNet engine's step (_lib.Recording has only been built and "
-                            "checked around the VGG16 chain's calls) is missing")
+        self._refuse_resnet("explain_batch_replay", self._NO_RECORDING)
         return self._static(False, images, captions, accumulate, predictions, _lib.stream_ptr().value,
                             self.vgg.conv_mode if self.vgg is not None else None)
 
