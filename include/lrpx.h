@@ -575,6 +575,13 @@ int lrpx_gridtd_rel_pix(const lrpx_gridtd_trace* tr, const lrpx_gridtd_relstate*
  * chain.  rows = null: all B*T rows (n_rows must be B*T). */
 int lrpx_gridtd_rel_pix_rows(const lrpx_gridtd_trace* tr, const lrpx_gridtd_relstate* rs, const float* Vp,
                              const float* proj_pre, float* a_proj, const int32_t* rows, int n_rows, void* stream);
+/* the same with the mean-of-projected-features term of the bottom-up model (models/gridTDmodel.py:1912-1915: the global feature is
+ * relu(global_img_feature_proj(mean_k Vp[k])), so its relevance returns UNDER the projector rule): r_avg [B*T][H] is the relevance of
+ * that mean (indexed by the full row, also with a row list), avg [B][H] the mean itself;
+ * a_proj[row][k][c] = Vp[b][k][c] * (sum_i alpha[b][i][k] wacc[row][i][c] + r_avg[row][c] / (P z~(avg[b][c]))) / z~(proj_pre[b][k][c]) */
+int lrpx_gridtd_rel_pix_rows_avg(const lrpx_gridtd_trace* tr, const lrpx_gridtd_relstate* rs, const float* Vp,
+                                 const float* proj_pre, const float* r_avg, const float* avg, float* a_proj, const int32_t* rows,
+                                 int n_rows, void* stream);
 int lrpx_rel_words_norm(float* r_words, int rows, int T, void* stream);
 
 /* ---- AoA decoder: trace (get_hidden_parameters, models/aoamodel.py:990-1062) -------------------------- */

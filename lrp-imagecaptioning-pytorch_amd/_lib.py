@@ -154,6 +154,7 @@ SIGNATURES = {
     "lrpx_scatter_maps": (_i, [_f, _f, _i, _i, _f, _f, _l, _i, _f]),
     "lrpx_gather_rows": (_i, [_f, _f, _f, _i, _i, _f]),
     "lrpx_gridtd_rel_pix_rows": (_i, [C.POINTER(GridTrace), C.POINTER(GridRelState), _f, _f, _f, _f, _i, _f]),
+    "lrpx_gridtd_rel_pix_rows_avg": (_i, [C.POINTER(GridTrace), C.POINTER(GridRelState), _f, _f, _f, _f, _f, _f, _i, _f]),
     "lrpx_aoa_rel_value_rows": (_i, [C.POINTER(AoaTrace), C.POINTER(AoaRelState), _f, _f, _i, _f, _f, _i, _f]),
     "lrpx_aoa_rel_value_head": (_i, [C.POINTER(AoaTrace), C.POINTER(AoaRelState), _f, _f, _i, _f, _f, _i, _f]),
     "lrpx_aoa_grad_pix_rows": (_i, [C.POINTER(AoaTrace), _i, _f, _f, _f, _i, _f, _i, _f]),

@@ -773,11 +773,18 @@ __global__ void gridtd_rel_u_kernel(const float* __restrict__ r_avg, const float
 
 // pixel spread :1091-1095 summed over i, and the prologue of the projector rule (:1125-1128):
 // Aproj[row][k][c] = Vp[b][k][c] * sum_{i<=t} alpha[b][i][k] * wacc[row][i][c] / z~(proj_pre[b][k][c])
+// AVG (the bottom-up model, models/gridTDmodel.py:1912-1915: the global feature is taken from the mean of the PROJECTED regions, so
+// its relevance r_avg [B*T][H] comes back under the projector rule): the eye rule of the mean, r_avg / (P z~(avg)), joins the
+// bracket - one value per (row, c), formed once outside the pixel loop:
+// Aproj[row][k][c] = Vp[b][k][c] * (sum_i ... + r_avg[row][c] / (P * z~(avg[b][c]))) / z~(proj_pre[b][k][c])
+template <bool AVG>
 __global__ __launch_bounds__(256) void gridtd_rel_pix_kernel(GridRel g, const float* __restrict__ Vp,
                                                              const float* __restrict__ proj_pre,
                                                              const float* __restrict__ alpha,
                                                              float* __restrict__ Aproj, int kchunk,
-                                                             const int* __restrict__ rowlist) {
+                                                             const int* __restrict__ rowlist,
+                                                             const float* __restrict__ r_avg,
+                                                             const float* __restrict__ avg) {
     // rowlist (variable caption lengths): workgroup x computes row rowlist[x] and writes it as row x of a COMPACT Aproj
     const int row = rowlist ? rowlist[blockIdx.x] : blockIdx.x, b = row / g.T, t = row - b * g.T, H = g.H, P = g.P;
     const long orow = blockIdx.x;
@@ -798,6 +805,10 @@ __global__ __launch_bounds__(256) void gridtd_rel_pix_kernel(GridRel g, const fl
 #pragma unroll
             for (int i = 0; i < TREG; ++i) wr[i] = i < n ? g.wacc[((long)row * g.T + i) * H + c] : 0.f;
         }
+        float ua = 0.f;              // AVG: the mean's share of the bracket (inactive rows read nothing)
+        if constexpr (AVG) {
+            if (act) ua = r_avg[(long)row * H + c] / ((float)P * stab_eps(avg[(long)b * H + c]));
+        }
         for (int k = k0; k < k1; ++k) {
             float a = 0.f;
             if (n <= TREG) {         // (same summation order as the loop below: i = n-1 .. 0; the tail adds exact zeros)
@@ -806,6 +817,7 @@ __global__ __launch_bounds__(256) void gridtd_rel_pix_kernel(GridRel g, const fl
             } else {
                 for (int i = n - 1; i >= 0; --i) a += al[i * kchunk + (k - k0)] * g.wacc[((long)row * g.T + i) * H + c];
             }
+            if constexpr (AVG) a += ua;
             const long pi = ((long)b * P + k) * H + c;
             Aproj[(orow * P + k) * H + c] = act ? Vp[pi] * a / stab_eps(proj_pre[pi]) : 0.f;
         }
@@ -1835,17 +1847,31 @@ int lrpx_rel_avg_u(const float* r_avg, const float* avg, float* u, int rows, int
     return check_launch("rel_avg_u");
 }
 
-int lrpx_gridtd_rel_pix_rows(const lrpx_gridtd_trace* tr, const lrpx_gridtd_relstate* rs, const float* Vp,
-                             const float* proj_pre, float* a_proj, const int32_t* rows, int n_rows, void* stream) {
-    LRPX_CHECK_PTRS_OPT("lrpx_gridtd_rel_pix_rows", {Vp, "Vp"}, {proj_pre, "proj_pre"}, {a_proj, "a_proj"}, {rows, "rows"});
+// both entries of the pixel rule: `mean` - with r_avg / avg, the <true> instantiation of the kernel
+static int launch_gridtd_rel_pix(bool mean, const lrpx_gridtd_trace* tr, const lrpx_gridtd_relstate* rs, const float* Vp, const float* proj_pre,
+                                 const float* r_avg, const float* avg, float* a_proj, const int32_t* rows, int n_rows, void* stream) {
     LRPX_TRY(check_rel(tr, rs));
-    LRPX_REQUIRE(Vp && proj_pre && a_proj, "gridtd_rel_pix: null pointer");
+    LRPX_REQUIRE(Vp && proj_pre && a_proj && (!mean || (r_avg && avg)), "gridtd_rel_pix: null pointer");
     LRPX_REQUIRE(rows ? (n_rows > 0 && n_rows <= tr->B * tr->T) : n_rows == tr->B * tr->T, "gridtd_rel_pix: bad row list");
     const int kchunk = 28;
     const size_t lds = (size_t)tr->T * kchunk * sizeof(float);
-    hipLaunchKernelGGL(gridtd_rel_pix_kernel, dim3(n_rows, (tr->P + kchunk - 1) / kchunk), dim3(256), lds,
-                       (hipStream_t)stream, to_rel(tr, rs), Vp, proj_pre, tr->alpha, a_proj, kchunk, rows);
+    hipLaunchKernelGGL(mean ? gridtd_rel_pix_kernel<true> : gridtd_rel_pix_kernel<false>, dim3(n_rows, (tr->P + kchunk - 1) / kchunk),
+                       dim3(256), lds, (hipStream_t)stream, to_rel(tr, rs), Vp, proj_pre, tr->alpha, a_proj, kchunk, rows, r_avg, avg);
     return check_launch("gridtd_rel_pix");
+}
+
+int lrpx_gridtd_rel_pix_rows(const lrpx_gridtd_trace* tr, const lrpx_gridtd_relstate* rs, const float* Vp,
+                             const float* proj_pre, float* a_proj, const int32_t* rows, int n_rows, void* stream) {
+    LRPX_CHECK_PTRS_OPT("lrpx_gridtd_rel_pix_rows", {Vp, "Vp"}, {proj_pre, "proj_pre"}, {a_proj, "a_proj"}, {rows, "rows"});
+    return launch_gridtd_rel_pix(false, tr, rs, Vp, proj_pre, nullptr, nullptr, a_proj, rows, n_rows, stream);
+}
+
+int lrpx_gridtd_rel_pix_rows_avg(const lrpx_gridtd_trace* tr, const lrpx_gridtd_relstate* rs, const float* Vp,
+                                 const float* proj_pre, const float* r_avg, const float* avg, float* a_proj, const int32_t* rows,
+                                 int n_rows, void* stream) {
+    LRPX_CHECK_PTRS_OPT("lrpx_gridtd_rel_pix_rows_avg", {Vp, "Vp"}, {proj_pre, "proj_pre"}, {r_avg, "r_avg"}, {avg, "avg"},
+                        {a_proj, "a_proj"}, {rows, "rows"});
+    return launch_gridtd_rel_pix(true, tr, rs, Vp, proj_pre, r_avg, avg, a_proj, rows, n_rows, stream);
 }
 
 int lrpx_gridtd_rel_pix(const lrpx_gridtd_trace* tr, const lrpx_gridtd_relstate* rs, const float* Vp,

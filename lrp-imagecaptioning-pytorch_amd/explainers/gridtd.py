@@ -31,13 +31,17 @@ class GridTDEngine(EngineBase):
     ENCODER_CONV_MODES = EngineBase._ENCODER_CONV_MODES
 
     def __init__(self, state, device="cuda", encoder=None, encoder_conv_mode=1):
-        sd = self._init_encoder(state, device, encoder, encoder_conv_mode)          # (explainers/engine_base.py)
+        self._build(state, device, encoder, encoder_conv_mode)
+
+    def _build(self, state, device, encoder, encoder_conv_mode, need_encoder=True):
+        sd = self._init_encoder(state, device, encoder, encoder_conv_mode, need_encoder)          # (explainers/engine_base.py)
         self.sd = sd
         self.V, self.E = sd["embedding.weight"].shape
         self.H = sd["fc.weight"].shape[1]
         self.C = sd["img_projector.weight"].shape[1]
         self.P = sd["AdaAttention.W_v_proj.weight"].shape[0]
         H, E, Cc = self.H, self.E, self.C
+        Kg = sd["global_img_feature_proj.weight"].shape[1]       # C: the mean of the encoder's features; bottom-up (`GridTDBUEngine`): H
         assert H == 512 and E == 512, "kernels are built for hidden=embed=512 (config.py:123-124)"
         # --- forward weights
         a, l = "AdaLSTM.lstm_cell.", "LanguageLSTM."
@@ -68,13 +72,13 @@ class GridTDEngine(EngineBase):
         # --- guided-backprop weights: full gate matrices, contraction over the 4H gate rows (gridTDmodel.py:1637-1659)
         self.p_g2 = ops.pack_weights(self.Wcat2, 4 * H, 3 * H, 1, PACK_DENSE_T, kc)
         self.p_g1 = ops.pack_weights(sd[a + "weight_ih"].contiguous(), 4 * H, 2 * E + H, 1, PACK_DENSE_T, kc)
-        self.p_gp_grad = self.p_gp_rel = ops.pack_weights(sd["global_img_feature_proj.weight"], E, Cc, 1, PACK_DENSE_T, kc)
+        self.p_gp_grad = self.p_gp_rel = ops.pack_weights(sd["global_img_feature_proj.weight"], E, Kg, 1, PACK_DENSE_T, kc)
         # --- relevance weights: g-gate rows of the LSTMs, [W_ih^g | W_hh^g]  (gridTDmodel.py:1019-1024)
         wg1 = torch.cat([sd[a + "weight_ih"][2 * H:3 * H], sd[a + "weight_hh"][2 * H:3 * H]], 1).contiguous()
         wg2 = torch.cat([sd[l + "weight_ih"][2 * H:3 * H], sd[l + "weight_hh"][2 * H:3 * H]], 1).contiguous()
         self.p_wg1 = ops.pack_weights(wg1, H, 2 * E + 2 * H, 1, PACK_DENSE_T, kc)
         self.p_wg2 = ops.pack_weights(wg2, H, 3 * H, 1, PACK_DENSE_T, kc)
-        self.p_gp_rel = ops.pack_weights(sd["global_img_feature_proj.weight"], E, Cc, 1, PACK_DENSE_T, kc)
+        self.p_gp_rel = ops.pack_weights(sd["global_img_feature_proj.weight"], E, Kg, 1, PACK_DENSE_T, kc)
         self.p_proj_rel = ops.pack_weights(self.w_proj2d, H, Cc, 1, PACK_DENSE_T, kc)
         # the projector rule runs over every (word, pixel) row: split products on the fp16 matrix cores (csrc/dense_f16x3.hip)
         self.p_proj_rel_h = ops.pack_weights_f16x2(self.w_proj2d, H, Cc, _lib.PACK_BWD_PLAIN, taps=1) if H % 64 == 0 else None
@@ -87,7 +91,7 @@ class GridTDEngine(EngineBase):
         self.lockstep_f16 = H % 16 == 0 and E % 16 == 0
         self.p_wg1_h = ops.pack_weights_f16x2(wg1, H, 2 * E + 2 * H, _lib.PACK_BWD_PLAIN, taps=1) if self.lockstep_f16 else None
         self.p_wg2_h = ops.pack_weights_f16x2(wg2, H, 3 * H, _lib.PACK_BWD_PLAIN, taps=1) if self.lockstep_f16 else None
-        self.p_gp_rel_h = ops.pack_weights_f16x2(sd["global_img_feature_proj.weight"], E, Cc, _lib.PACK_BWD_PLAIN, taps=1) if self.lockstep_f16 else None
+        self.p_gp_rel_h = ops.pack_weights_f16x2(sd["global_img_feature_proj.weight"], E, Kg, _lib.PACK_BWD_PLAIN, taps=1) if self.lockstep_f16 else None
         torch.cuda.synchronize()
         self._idx_cache = {}
 
@@ -305,7 +309,14 @@ class GridTDEngine(EngineBase):
         d1 = ops.conv_desc(rs["A"], self.p_wg1_h if f16 else self.p_wg1, rows, 0, H, W1, 1, EPI_REL, pix_per_map=1, oc_split=W1,
                            x=tr["xh1"], map2img=idx[0], out0=rs["rx"], f16x3=f16)
         check(lib.lrpx_gridtd_rel_steps(ctr, crs, T, C.byref(d2), C.byref(d1), ptr(idx), idx.shape[1], st))
-        # global feature path (:1116-1124) and projector (:1125-1128)
+        return self._rel_tail(enc, tr, rg, rs, ctr, crs, row2img, f16)
+
+    def _rel_tail(self, enc, tr, rg, rs, ctr, crs, row2img, f16):
+        """global feature path (:1116-1124) and projector (:1125-1128)"""
+        lib, st = _lib.load(), stream_ptr()
+        B, T, H, E, P, Cc = tr["B"], tr["T"], self.H, self.E, self.P, self.C
+        rows = B * T
+        e = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)
         a_glob = e(rows, E)
         check(lib.lrpx_gridtd_rel_glob(ctr, crs, ptr(enc["glob_pre"]), ptr(a_glob), st))
         r_avg = e(rows, Cc)
@@ -455,6 +466,156 @@ class GridTDEngine(EngineBase):
         """`explain_batch` over an iterable of (images, captions[, lens]) batches, `depth` in flight (explainers/engine_base.py)."""
         return self._explain_stream(batches, depth, lambda eng, images, captions, lens: eng.explain_batch(images, captions, lens=lens,
                                                                                                          accumulate=accumulate))
+
+
+class GridTDBUEngine(GridTDEngine):
+    """The bottom-up gridTD model, `GridTDModelBU` (models/gridTDmodel.py:1863-2464): P = 36 region features of C = 2048 channels
+    in place of an encoder.  `state` has the key names and shapes of `GridTDModelBU.state_dict()`: `img_projector.weight` (H, C) - a
+    Linear -, `global_img_feature_proj.weight` (E, H), `AdaAttention.W_v_proj.weight` (P, H), no `img_encoder.` keys.  Anything else is
+    refused (ValueError naming the key) by host logic, before the library is loaded.
+
+    The decoder is `GridTDEngine`'s.  The image side differs (:1912-1915): the global feature is
+    relu(global_img_feature_proj(mean_k relu(img_projector(F))[k])) - the mean of the PROJECTED regions -, so its relevance returns under
+    the projector rule: r_avg = eps(r_glob, avg, glob_pre, W_gp), r_vp[k] = r_proj[k] + eps(r_avg, Vp[k] / P, avg, eye),
+    r_feat[k] = eps(r_vp[k], F[k], proj_pre[k], W_proj) (`_rel_tail`; csrc/lrpx_decoder.hip: lrpx_gridtd_rel_pix_rows_avg).  The
+    region relevance (B, T, P, C) is the result: there is no CNN stage, no running sum, and no gradient explainer (the reference
+    defines none for this model).  DESIGN.md 5.14."""
+
+    NO_GRADIENT = "no gradient explainer is defined for the bottom-up model (models/gridTDmodel.py:1863-2464 has none)"
+
+    def __init__(self, state, device="cuda"):
+        self._check_state(state)
+        self._build(state, device, None, 1, need_encoder=False)
+
+    @staticmethod
+    def _check_state(state):
+        """host logic: the three ways a state is not `GridTDModelBU`'s"""
+        for k in state:
+            if k.startswith("img_encoder."):
+                raise ValueError("GridTDBUEngine: the state holds the encoder key {!r}; the bottom-up model has no encoder "
+                                 "(GridTDEngine explains a model with one)".format(k))
+        wp, wg = state["img_projector.weight"], state["global_img_feature_proj.weight"]
+        if len(wp.shape) != 2:
+            raise ValueError("GridTDBUEngine: 'img_projector.weight' is {}-D {}; the bottom-up model's projector is a Linear, "
+                             "(H, C)".format(len(wp.shape), tuple(wp.shape)))
+        if len(wg.shape) != 2 or wg.shape[1] != wp.shape[0]:
+            raise ValueError("GridTDBUEngine: 'global_img_feature_proj.weight' is {}; the bottom-up model takes the global feature from "
+                             "the mean of the projected regions, (E, H = {})".format(tuple(wg.shape), wp.shape[0]))
+
+    def feature_shape(self, features):
+        """(P, 1, C) of the region features (host arithmetic): the regions as a P x 1 map"""
+        if features.dim() != 3:
+            raise ValueError("GridTDBUEngine: features must be (B, P, C) region features, got {} (this model has no encoder: images are "
+                             "not accepted)".format(tuple(features.shape)))
+        return int(features.shape[1]), 1, int(features.shape[2])
+
+    def _check_sizes(self, features):
+        p, _, c = self.feature_shape(features)
+        if p != self.P or c != self.C:
+            raise ValueError("GridTDBUEngine: {} regions of {} channels; the decoder is built for {} regions (AdaAttention.W_v_proj) of {} "
+                             "channels (img_projector)".format(p, c, self.P, self.C))
+        return p, 1
+
+    def encode(self, features):
+        """The image-side constants of `GridTDModelBU.forward` (:1912-1915) from (B, P, C) region features on any device: `Vp`,
+        `proj_pre`, `avg` (the mean of Vp over the regions, (B, H)), `glob_pre`, `glob`, `att_img`."""
+        self._check_sizes(features)                                        # before any launch
+        lib = _lib.load()
+        st = stream_ptr()
+        H, E, Cc, P = self.H, self.E, self.C, self.P
+        feats = features.to(self.device, torch.float32).contiguous()
+        B = feats.shape[0]
+        e = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)
+        enc = dict(B=B, feats=feats)
+        enc["proj_pre"] = e(B, P, H)
+        ops.conv_mfma(feats, self.p_proj_fwd, B, 0, Cc, H, 1, EPI_PLAIN, pix_per_map=P, oc_split=H,
+                      bias=self.sd["img_projector.bias"], out0=enc["proj_pre"])
+        enc["Vp"] = e(B, P, H)
+        check(lib.lrpx_relu(ptr(enc["proj_pre"]), ptr(enc["Vp"]), enc["Vp"].numel(), st))
+        enc["avg"] = e(B, H)
+        check(lib.lrpx_mean_pixels(ptr(enc["Vp"]), ptr(enc["avg"]), B, P, H, st))
+        enc["glob_pre"] = e(B, E)
+        check(lib.lrpx_linear_small(ptr(enc["avg"]), H, ptr(self.sd["global_img_feature_proj.weight"]),
+                                    ptr(self.sd["global_img_feature_proj.bias"]), ptr(enc["glob_pre"]), E, B, H, E, 0, st))
+        enc["glob"] = e(B, E)
+        check(lib.lrpx_relu(ptr(enc["glob_pre"]), ptr(enc["glob"]), enc["glob"].numel(), st))
+        enc["att_img"] = e(B, P, P)
+        ops.conv_mfma(enc["Vp"], self.p_attv_fwd, B, 0, H, -(-P // 32) * 32, 1, EPI_PLAIN, pix_per_map=P, oc_split=P,
+                      bias=self.sd["AdaAttention.W_v_proj.bias"], out0=enc["att_img"])
+        return enc
+
+    def _rel_tail(self, enc, tr, rg, rs, ctr, crs, row2img, f16):
+        """the tail in the order `GridTDModelBU.forward` dictates: the epsilon rule of `global_img_feature_proj` on x = avg (K = E,
+        n_oc = H) -> r_avg (rows, H); the pixel rule with the mean term (r_avg joins the bracket before the division by z~(proj_pre));
+        the projector rule WITHOUT a `u`."""
+        lib, st = _lib.load(), stream_ptr()
+        B, T, H, E, P, Cc = tr["B"], tr["T"], self.H, self.E, self.P, self.C
+        rows = B * T
+        e = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)
+        a_glob = e(rows, E)
+        check(lib.lrpx_gridtd_rel_glob(ctr, crs, ptr(enc["glob_pre"]), ptr(a_glob), st))
+        r_avg = e(rows, H)
+        ops.conv_mfma(a_glob, self.p_gp_rel_h if f16 else self.p_gp_rel, rows, 0, E, -(-H // 32) * 32 if f16 else H, 1, EPI_REL,
+                      pix_per_map=1, oc_split=H, x=enc["avg"], map2img=row2img, out0=r_avg, f16x3=f16)
+        check(lib.lrpx_rel_words_norm(ptr(rs["r_words"]), rows, T, st))
+        n, rowlist = rows, None
+        if rg is not None and not rg.full:       # unequal lengths: the (word, region) rules on the valid rows only, compact
+            n, rowlist, row2img = rg.n, rg.rows, rg.row2img
+            if n == 0:
+                return e(0, P, Cc), rs["r_words"], row2img
+        a_proj = e(n, P, H)
+        check(lib.lrpx_gridtd_rel_pix_rows_avg(ctr, crs, ptr(enc["Vp"]), ptr(enc["proj_pre"]), ptr(r_avg), ptr(enc["avg"]), ptr(a_proj),
+                                               ptr(rowlist), n, st))
+        r_feat = e(n, P, Cc)
+        self._proj_rule(a_proj, n, P, enc["feats"], row2img, r_feat)
+        return r_feat, rs["r_words"], row2img
+
+    def explain_batch(self, features, captions, lens=None, return_features=False, predictions=False):
+        """Every word of B captions explained on (B, P, C) region features; captions (B, T+1) int64, column 0 = <start>.  Returns
+        r_feat (B, T, P, C) - the relevance of the region features, zero in rows behind an image's last word (`lens`) - and r_words
+        (B, T, T) (row t holds t + 1 valid entries); then the (B, T, V) scores with predictions=True; then the trace and `encode`'s
+        dict with return_features=True."""
+        enc = self.encode(features)
+        captions = captions.to(self.device, torch.int64).contiguous()
+        B, T = captions.shape[0], captions.shape[1] - 1
+        tr = self.trace(enc, captions, predictions=predictions)
+        rg = ragged(lens, B, T, self.device)
+        r_feat, r_words, row2img = self.relevance(enc, tr, rg)
+        out = self._finish(rg, B, T, r_feat, r_words, row2img, lambda feat, m: feat, (self.P, self.C),
+                           extra=(tr["pred"],) if predictions else ())
+        return out + ((tr, enc) if return_features else ())
+
+    def _static(self, graph, features, captions, predictions, *key):
+        features = features.to(self.device, torch.float32)
+        captions = captions.to(self.device, torch.int64)
+        key = (tuple(features.shape), tuple(captions.shape), bool(predictions)) + key + (self._f16(),)
+        return self._static_step(graph, key, features, captions, lambda f, c: self.explain_batch(f, c, predictions=predictions))
+
+    def explain_batch_graph(self, features, captions, predictions=False):
+        """`explain_batch` replayed from a captured HIP graph, one per (B, T) shape (explainers/engine_base.py: `_static_step`)."""
+        self._check_sizes(features)
+        return self._static(True, features, captions, predictions)
+
+    def explain_batch_replay(self, features, captions, predictions=False):
+        """`explain_batch` as a RECORDED step, one per input shape and stream (explainers/engine_base.py: `_static_step`)."""
+        self._check_sizes(features)
+        return self._static(False, features, captions, predictions, _lib.stream_ptr().value)
+
+    def explain_stream(self, batches, depth=3):
+        """`explain_batch` over an iterable of (features, captions[, lens]) batches, `depth` in flight (explainers/engine_base.py)."""
+        return self._explain_stream(batches, depth, lambda eng, features, captions, lens: eng.explain_batch(features, captions, lens=lens))
+
+    def _no_gradient(self, entry):
+        raise NotImplementedError("GridTDBUEngine.{}: {}".format(entry, self.NO_GRADIENT))
+
+    def guided_gradient(self, enc, tr, lens=None, mask_features=True):
+        self._no_gradient("guided_gradient")
+
+    def explain_batch_guided(self, features, captions, lens=None, return_features=False, gradcam=False):
+        self._no_gradient("explain_batch_guided")
+
+    def explain_batch_gradient(self, features, captions, lens=None, cam=False, return_features=False):
+        self._no_gradient("explain_batch_gradient")
 
 
 # ------------------------------------------------------------------------------------------------

@@ -91,11 +91,19 @@ def make_gridtd_resnet_state(seed=0, vocab_size=9586, embed_dim=512, hidden_dim=
     return _gridtd_decoder_state(np.random.RandomState(seed), OrderedDict(), vocab_size, embed_dim, hidden_dim, feat_dim, num_pixels)
 
 
-def _gridtd_decoder_state(rs, sd, vocab_size, embed_dim, hidden_dim, feat_dim, num_pixels):
+def make_gridtd_bu_state(seed=0, vocab_size=9586, embed_dim=512, hidden_dim=512, feat_dim=2048, num_pixels=36):
+    """state_dict (numpy float32) for the reference `GridTDModelBU` (models/gridTDmodel.py:1868-1886; bottom-up region features, no
+    encoder): `img_projector` is a Linear(feat_dim, hidden) - a 2-D weight - and `global_img_feature_proj` a Linear(hidden, embed): the
+    global feature is taken from the mean of the PROJECTED regions (:1912-1915)."""
+    return _gridtd_decoder_state(np.random.RandomState(seed), OrderedDict(), vocab_size, embed_dim, hidden_dim, feat_dim, num_pixels,
+                                 bottom_up=True)
+
+
+def _gridtd_decoder_state(rs, sd, vocab_size, embed_dim, hidden_dim, feat_dim, num_pixels, bottom_up=False):
     b = 1.0 / math.sqrt(feat_dim)
-    sd["img_projector.weight"] = _uniform(rs, (hidden_dim, feat_dim, 1, 1), b)
+    sd["img_projector.weight"] = _uniform(rs, (hidden_dim, feat_dim) if bottom_up else (hidden_dim, feat_dim, 1, 1), b)
     sd["img_projector.bias"] = _uniform(rs, (hidden_dim,), b)
-    _linear(rs, sd, "global_img_feature_proj", embed_dim, feat_dim)
+    _linear(rs, sd, "global_img_feature_proj", embed_dim, hidden_dim if bottom_up else feat_dim)
     _lstm(rs, sd, "LanguageLSTM", 2 * hidden_dim, hidden_dim)
     _lstm(rs, sd, "AdaLSTM.lstm_cell", 2 * embed_dim + hidden_dim, hidden_dim)
     _linear(rs, sd, "AdaLSTM.x_gate", hidden_dim, 2 * embed_dim + hidden_dim)
