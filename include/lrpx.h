@@ -584,6 +584,72 @@ int lrpx_gridtd_rel_pix_rows_avg(const lrpx_gridtd_trace* tr, const lrpx_gridtd_
                                  int n_rows, void* stream);
 int lrpx_rel_words_norm(float* r_words, int rows, int T, void* stream);
 
+/* ---- single-LSTM adaptive-attention decoder (models/adaptiveattention.py): trace (get_hidden_parameters, :626-677) ---------------- */
+typedef struct lrpx_adaatt_trace {
+    int B, T, H, E, P;
+    float* xh;                          /* [B][T][H+2E] = [h[t] | emb(word_t) | glob]: the reference's xht (:688) with the h columns FIRST */
+    float *h, *c;                       /* [B][T+1][H]; row 0 must be zero (init_hidden_state, :123-126) */
+    float *g, *i, *f;                   /* [B][T][H]  g = pre-activation, i / f = activations (:672-674) */
+    float *s, *ctx, *ctx_hat, *hc;      /* [B][T][H]  hc = h[t+1] + ctx_hat[t] (fc input, :663) */
+    float *alpha, *beta;                /* [B][T][P], [B][T] */
+    float *o, *sgate;                   /* optional [B][T][H]: output gate, sentinel gate (the gradient explainers' trace); may be null */
+} lrpx_adaatt_trace;
+/* The teacher-forced trace, decoupled: the recurrence reads h only (the attention feeds nothing back).
+ *   fwd_inputs:        the x columns [emb | glob] of every (image, word) row of xh; the caller then forms
+ *                      zin [B*T][NR] = xh[:, H:] Wx_il^T + b_il for all rows with lrpx_linear_small (K = 2E);
+ *   fwd_recurrence:    T dependent launches of K = H: z = zin[b, t] + Wh_il h[b, t], LSTM cell (:554-565) and sentinel
+ *                      s = sigmoid(z_gate) tanh(c_t) (:603-604) in the epilogue; writes the h columns of xh[b, t + 1].  B > 64 runs in slices;
+ *   fwd_attention_all: AdaptiveAttention (:56-98) on (h[t+1], s[t]) of every row, ctx_hat and hc = h[t+1] + ctx_hat (two launches);
+ *                      att_img [B][P][P] = W_v_proj(Vp) + b; scratch [B*T][3P].
+ * Interleaved gate rows (Wx_il (NR, 2E), Wh_il (NR, H), b_il, zin columns), NR = 16 * ceil(H / 3): row 16 j + 5 u + q = gate q (i, f, g, o of
+ * the LSTM, then the sentinel gate: [W_ih ; x_gate] / [W_hh ; h_gate] / b_ih + b_hh ; b_x + b_h) of hidden unit 3 j + u, u < 3; rows
+ * 16 j + 15 and the rows of units >= H are zero. */
+int lrpx_adaatt_fwd_inputs(const lrpx_adaatt_trace* tr, const float* glob, const float* emb, const long long* tok, int tok_ld,
+                           void* stream);
+int lrpx_adaatt_fwd_recurrence(const lrpx_adaatt_trace* tr, const float* w_hh_il, const float* zin, void* stream);
+int lrpx_adaatt_fwd_attention_all(const lrpx_adaatt_trace* tr, const float* Vp, const float* att_img, const float* Wg, const float* Ws,
+                                  const float* bs, const float* wh, float* scratch, void* stream);
+/* Per-step entries (the decoding loops): fwd_pre writes row xh[b, t] = [h[b, t] | emb[tok[b][t]] | glob[b]]; fwd_step runs the gate
+ * linear over the whole row (w_cat (5H, H+2E) = [W_hh | W_ih ; h_gate | x_gate], gates in blocks of H, b_cat its bias), cell + sentinel,
+ * and the attention of step t.  Values equal the decoupled trace's to rounding (one dot product over [h | x] instead of two). */
+typedef struct lrpx_adaatt_step_args {
+    const float *w_cat, *b_cat;
+    const float *Vp, *att_img;          /* relu(img_projector(features)) [B][P][H]; W_v_proj(Vp) + b [B][P][P] */
+    const float *Wg, *Ws, *bs, *wh;     /* AdaAttention W_g_proj, W_s_proj (+ bias), w_h */
+    float *zz, *att_scratch;            /* scratch [B][5H], [B][3P] */
+} lrpx_adaatt_step_args;
+int lrpx_adaatt_fwd_pre(const lrpx_adaatt_trace* tr, int t, const float* glob, const float* emb, const long long* tok, int tok_ld,
+                        void* stream);
+int lrpx_adaatt_fwd_step(const lrpx_adaatt_trace* tr, int t, const lrpx_adaatt_step_args* a, void* stream);
+
+/* ---- single-LSTM adaptive-attention decoder: relevance (explain_caption_wordt, models/adaptiveattention.py:679-771) ---------------- */
+typedef struct lrpx_adaatt_relstate {
+    const int32_t* lens;                /* [B] words per image (null: T) */
+    float *r_h, *r_c, *r_ctx;           /* [B*T][H]; r_ctx = r_context / z~(ctx_t), the factor of the pixel rule */
+    float* r_glob;                      /* [B*T][E] */
+    float *A, *rx;                      /* gate-rule input [B*T][H] / output [B*T][H+2E] = [h | emb | glob] */
+    float* r_words;                     /* [B*T][T] */
+} lrpx_adaatt_relstate;
+/* :700-724 and the cell split of lock-step 0 (:726-734): fc rule from the target logit onto h[t+1] + ctx_hat[t], split by identity rules,
+ * ctx_hat split into context ((1 - beta) ctx) and sentinel (beta s) - at the explained word only -, r_c[t+1] = r_s + r_h[t+1],
+ * A = r_g / z~(tanh g[t]).  Rows behind an image's last word: zeros in A, r_ctx, r_glob, r_words. */
+int lrpx_adaatt_rel_init(const lrpx_adaatt_trace* tr, const lrpx_adaatt_relstate* rs, const float* fcw, const float* logit,
+                         const long long* tok, int tok_ld, void* stream);
+/* lock-steps 0 <= s < n_steps (:725-742) in one call; per lock-step the gate rule `dense` (an lrpx_conv_mfma descriptor: fp32, taps 1,
+ * EPI_REL, in = A, x = tr->xh, out0 = rx, cin = H, n_oc = oc_split = H + 2E; weights [W_hh^g | W_ih^g] packed DENSE_T; map2img is
+ * replaced by idx + s * idx_ld: row -> source row of the multiplicand) and one point-wise launch: r_h[i] = rx[:H], r_words[i] =
+ * sum rx[H:H+E], r_glob = rx[H+E:] at s == 0 only (:740-741), then the cell split of lock-step s + 1.  Inactive rows: zeros in A, nothing
+ * else touched.  cut_dead_columns != 0: lock-steps s >= 1 contract the first H + E columns only (the glob columns are never read
+ * there); every column that is read is bit-identical to the full-width contraction. */
+int lrpx_adaatt_rel_steps(const lrpx_adaatt_trace* tr, const lrpx_adaatt_relstate* rs, int n_steps, const lrpx_conv_desc* dense,
+                          const int32_t* idx, int idx_ld, int cut_dead_columns, void* stream);
+/* a_glob[row][e] = r_glob[row][e] / z~(glob_nb[b][e]), glob_nb = W_gp avg WITHOUT the bias (:536-537, :743-746) */
+int lrpx_adaatt_rel_glob(const lrpx_adaatt_trace* tr, const lrpx_adaatt_relstate* rs, const float* glob_nb, float* a_glob, void* stream);
+/* a_proj[x][k][c] = Vp[b][k][c] * alpha[b][t][k] * r_ctx[row][c] / z~(proj_nb[b][k][c]) for row = rows[x] (null: x, n_rows = B*T), written
+ * compactly [n_rows][P][H]; proj_nb = the projector's pre-activation WITHOUT the bias (:751-763) */
+int lrpx_adaatt_rel_pix_rows(const lrpx_adaatt_trace* tr, const lrpx_adaatt_relstate* rs, const float* Vp, const float* proj_nb,
+                             float* a_proj, const int32_t* rows, int n_rows, void* stream);
+
 /* ---- AoA decoder: trace (get_hidden_parameters, models/aoamodel.py:990-1062) -------------------------- */
 typedef struct lrpx_aoa_trace {
     int B, T, H, E, P, NH;

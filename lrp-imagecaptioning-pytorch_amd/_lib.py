@@ -58,6 +58,22 @@ class GridStepArgs(C.Structure):
         "w_il1", "b_il1", "w_il2", "b_il2")]
 
 
+class AdaTrace(C.Structure):
+    """lrpx_adaatt_trace"""
+    _fields_ = [("B", _i), ("T", _i), ("H", _i), ("E", _i), ("P", _i)] + [(k, _f) for k in (
+        "xh", "h", "c", "g", "i", "f", "s", "ctx", "ctx_hat", "hc", "alpha", "beta", "o", "sgate")]
+
+
+class AdaStepArgs(C.Structure):
+    """lrpx_adaatt_step_args"""
+    _fields_ = [(k, _f) for k in ("w_cat", "b_cat", "Vp", "att_img", "Wg", "Ws", "bs", "wh", "zz", "att_scratch")]
+
+
+class AdaRelState(C.Structure):
+    """lrpx_adaatt_relstate"""
+    _fields_ = [(k, _f) for k in ("lens", "r_h", "r_c", "r_ctx", "r_glob", "A", "rx", "r_words")]
+
+
 class AoaGradState(C.Structure):
     _fields_ = [(k, _f) for k in ("lens", "d_h", "d_c", "dA", "dB", "gates", "dx", "d_glob", "r_words")]
 
@@ -199,6 +215,15 @@ SIGNATURES = {
     "lrpx_aoa_rel_step": (_i, [C.POINTER(AoaTrace), C.POINTER(AoaRelState), _i, _i, _f]),
     "lrpx_aoa_rel_steps": (_i, [C.POINTER(AoaTrace), C.POINTER(AoaRelState), _i, C.POINTER(ConvDesc), _f, _i, _f]),
     "lrpx_aoa_rel_steps_fused": (_i, [C.POINTER(AoaTrace), C.POINTER(AoaRelState), C.POINTER(ConvDesc), _f, _i, _f, _f, _f, _f]),
+    "lrpx_adaatt_fwd_inputs": (_i, [C.POINTER(AdaTrace), _f, _f, _f, _i, _f]),
+    "lrpx_adaatt_fwd_recurrence": (_i, [C.POINTER(AdaTrace), _f, _f, _f]),
+    "lrpx_adaatt_fwd_attention_all": (_i, [C.POINTER(AdaTrace), _f, _f, _f, _f, _f, _f, _f, _f]),
+    "lrpx_adaatt_fwd_pre": (_i, [C.POINTER(AdaTrace), _i, _f, _f, _f, _i, _f]),
+    "lrpx_adaatt_fwd_step": (_i, [C.POINTER(AdaTrace), _i, C.POINTER(AdaStepArgs), _f]),
+    "lrpx_adaatt_rel_init": (_i, [C.POINTER(AdaTrace), C.POINTER(AdaRelState), _f, _f, _f, _i, _f]),
+    "lrpx_adaatt_rel_steps": (_i, [C.POINTER(AdaTrace), C.POINTER(AdaRelState), _i, C.POINTER(ConvDesc), _f, _i, _i, _f]),
+    "lrpx_adaatt_rel_glob": (_i, [C.POINTER(AdaTrace), C.POINTER(AdaRelState), _f, _f, _f]),
+    "lrpx_adaatt_rel_pix_rows": (_i, [C.POINTER(AdaTrace), C.POINTER(AdaRelState), _f, _f, _f, _f, _i, _f]),
     "lrpx_gridtd_grad_init": (_i, [C.POINTER(GridTrace), C.POINTER(GridGradState), _f, _f, _i, _f]),
     "lrpx_gridtd_grad_step": (_i, [C.POINTER(GridTrace), C.POINTER(GridGradState), _i, _i, _f]),
     "lrpx_spread_pixels": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _f]),

@@ -1,1 +1,2 @@
-"""Per-model explainers (mirror of the `Explain*` classes of models/gridTDmodel.py / models/aoamodel.py)."""
+"""Per-model explainers (mirror of the `Explain*` classes of models/gridTDmodel.py / models/aoamodel.py / models/adaptiveattention.py)."""
+from .adaatt import AdaAttEngine, ExplainAdaptiveAttention  # noqa: F401

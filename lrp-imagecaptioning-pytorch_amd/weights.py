@@ -117,6 +117,35 @@ def _gridtd_decoder_state(rs, sd, vocab_size, embed_dim, hidden_dim, feat_dim, n
     return sd
 
 
+def make_adaatt_state(seed=0, vocab_size=9586, embed_dim=512, hidden_dim=512, feat_dim=512, num_pixels=196, encoder="vgg16",
+                      vgg_bias_std=0.0):
+    """state_dict (numpy float32) for the reference `AdaptiveAttentionCaptioningModel` (models/adaptiveattention.py:103-121; the
+    single-LSTM adaptive-attention model), in the key order of its `state_dict()`.  encoder="vgg16": the VGG16 keys under
+    `img_encoder.encoder.` come first; encoder=None: no `img_encoder.` keys (a ResNet encoder comes as a module or its keys are added by
+    the caller; region-style features need none), and the draws start at the seed.
+    Order of the draws: [VGG16 convs,] img_projector (weight, bias), global_img_feature_proj, AdaLSTM.lstm_cell (`_lstm`: weight_ih,
+    weight_hh, bias_ih, bias_hh; input 2 * embed_dim), AdaLSTM.x_gate, AdaLSTM.h_gate, AdaAttention.W_v_proj, W_s_proj, W_g_proj, w_h,
+    embedding (`_normal`, std 1), fc."""
+    if encoder not in ("vgg16", None):
+        raise ValueError("make_adaatt_state: encoder must be 'vgg16' or None, got {!r}".format(encoder))
+    rs = np.random.RandomState(seed)
+    sd = _vgg_state(rs, "img_encoder.encoder.", vgg_bias_std) if encoder == "vgg16" else OrderedDict()
+    b = 1.0 / math.sqrt(feat_dim)
+    sd["img_projector.weight"] = _uniform(rs, (hidden_dim, feat_dim, 1, 1), b)
+    sd["img_projector.bias"] = _uniform(rs, (hidden_dim,), b)
+    _linear(rs, sd, "global_img_feature_proj", embed_dim, feat_dim)
+    _lstm(rs, sd, "AdaLSTM.lstm_cell", 2 * embed_dim, hidden_dim)
+    _linear(rs, sd, "AdaLSTM.x_gate", hidden_dim, 2 * embed_dim)
+    _linear(rs, sd, "AdaLSTM.h_gate", hidden_dim, hidden_dim)
+    _linear(rs, sd, "AdaAttention.W_v_proj", num_pixels, hidden_dim)
+    _linear(rs, sd, "AdaAttention.W_s_proj", num_pixels, hidden_dim)
+    _linear(rs, sd, "AdaAttention.W_g_proj", num_pixels, hidden_dim, bias=False)
+    _linear(rs, sd, "AdaAttention.w_h", 1, num_pixels, bias=False)
+    sd["embedding.weight"] = _normal(rs, (vocab_size, embed_dim), 1.0)
+    _linear(rs, sd, "fc", vocab_size, hidden_dim)
+    return sd
+
+
 def make_aoa_state(seed=0, vocab_size=11027, embed_dim=512, hidden_dim=512, feat_dim=512,
                    vgg_bias_std=0.0, with_encoder=True):
     """state_dict (numpy float32) for the reference `AOAModel` (models/aoamodel.py:116-142).
