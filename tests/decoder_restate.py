@@ -1,0 +1,432 @@
+"""The four decoder back-passes of csrc/lrpx_decoder.hip restated row by row in plain torch, from the formulae of the reference
+(models/gridTDmodel.py, models/aoamodel.py: line numbers at each step, as in the .hip comments and oracle/lrp_oracle.py), on trace
+tensors of ANY values - and the drawn traces the kernel tests run them on.  A helper module, not a conftest.
+
+    gridtd_rel(d, sd, lens, dtype, order)         explain_caption_wordt, gridTDmodel.py:1014-1135
+    aoa_rel(d, sd, head, lens, dtype, order)      explain_caption_wordt + lrp_mha, aoamodel.py:1064-1156, :812-862
+    gridtd_grad(d, sd, lens, dtype, order)        ExplainiGridTDGuidedGradient.explain_caption_wordt, gridTDmodel.py:1588-1675
+    aoa_grad(d, sd, head, lens, dtype, order)     ExplainAOAGradient.explain_caption_wordt, aoamodel.py:1435-1499
+
+`d`: the trace and encoder tensors, batched as the engines keep them ([B][T][..], [B][T+1][..], g = gate PRE-activation), `sd` the
+model's state dict (CPU tensors), `lens` words per image or None, `dtype` torch.float64 / float32, `order` the summation order of every
+matrix product and of the r_words sums (ORDERS).  Each returns the final value of every tensor the C state struct exposes, row =
+image * T + word, zeros in rows behind an image's last word, and what the pixel rules form from them.  Quirks of the reference that the
+kernels keep are kept: the dead r_h1[i] (gridTDmodel.py:1075 overwrites :1110), `r_c = r_h` as an assignment (aoamodel.py:1116), the
+d_glob assignment (aoamodel.py:1487)."""
+import functools
+
+import torch
+
+ORDERS = ("torch", "rev128", "il128")
+H = E = 512
+EPS = 0.01
+
+
+def stab(z):
+    """z + eps sign(z); exact zeros (of either sign) -> eps   (gridTDmodel.py:757-759)"""
+    zt = z + EPS * torch.sign(z)
+    return torch.where(zt == 0, torch.full_like(zt, EPS), zt)
+
+
+def _chunks(n, order):
+    idx = list(range(0, n, 128))
+    if order == "rev128":
+        return idx[::-1]
+    return idx[0::2] + idx[1::2]          # il128: the even chunks, then the odd ones
+
+
+def mm(a, w, order):
+    """a (.., K) @ w (K, N), the K terms summed in `order`: torch's own, or partial sums of 128 terms added last to first / interleaved"""
+    if order == "torch":
+        return a @ w
+    out = None
+    for k0 in _chunks(a.shape[-1], order):
+        p = a[..., k0:k0 + 128] @ w[k0:k0 + 128]
+        out = p if out is None else out + p
+    return out
+
+
+def tot(x, order):
+    """sum of a vector in `order`"""
+    if order == "torch":
+        return x.sum()
+    out = None
+    for k0 in _chunks(x.shape[-1], order):
+        p = x[k0:k0 + 128].sum()
+        out = p if out is None else out + p
+    return out
+
+
+def _over_steps(terms, order):
+    """sum of a list of per-time-step terms (index = time step i): last to first as the kernels do, first to last, or interleaved"""
+    seq = {"torch": terms[::-1], "rev128": terms, "il128": terms[0::2] + terms[1::2]}[order]
+    out = seq[0]
+    for x in seq[1:]:
+        out = out + x
+    return out
+
+
+def _cast(d, sd, dtype):
+    c = lambda v: v.to(dtype) if torch.is_tensor(v) and v.is_floating_point() else v
+    return {k: c(v) for k, v in d.items()}, {k: c(v) for k, v in sd.items()}
+
+
+def _norm_words(rw, t):
+    """:1129-1132 r_words / max|r_words| over words 0..t, unless all zero"""
+    out = rw.clone()
+    m = rw[:t + 1].abs().max()
+    if m > 0:
+        out[:t + 1] = rw[:t + 1] / m
+    return out
+
+
+def _len(lens, b, T):
+    return T if lens is None else int(lens[b])
+
+
+# ---- gridTD relevance --------------------------------------------------------------------------------------------------------------------
+def gridtd_rel(d, sd, lens, dtype, order):
+    """-> r_h2n, r_c2, r_c1, r_ch0, r_h2p (rows, H), r_glob (rows, E), A (rows, H), rx (rows, 2E+2H), wacc (rows, T, H) = r_ctx / z~(ctx)
+    per time step, r_words / r_words_norm (rows, T), a_glob (rows, E), a_proj (rows, P, H).  The mean path continues outside with
+    r_avg = avg * (a_glob @ W_glob) (:1116-1119) - a projector GEMM - and U = r_avg / (P z~(avg)) (:1121-1124): `gridtd_u`."""
+    t_, w = _cast(d, sd, dtype)
+    B, T = t_["beta"].shape
+    P = t_["alpha"].shape[-1]
+    a, l = "AdaLSTM.lstm_cell.", "LanguageLSTM."
+    wg1 = torch.cat([w[a + "weight_ih"][2 * H:3 * H], w[a + "weight_hh"][2 * H:3 * H]], 1)          # (H, 2E+2H)  :1019-1024
+    wg2 = torch.cat([w[l + "weight_ih"][2 * H:3 * H], w[l + "weight_hh"][2 * H:3 * H]], 1)          # (H, 3H)
+    rows = B * T
+    z = lambda *s: torch.zeros(*s, dtype=dtype)
+    out = dict(r_h2n=z(rows, H), r_c2=z(rows, H), r_c1=z(rows, H), r_ch0=z(rows, H), r_h2p=z(rows, H), r_glob=z(rows, E), A=z(rows, H),
+               rx=z(rows, 2 * E + 2 * H), wacc=z(rows, T, H), r_words=z(rows, T), r_words_norm=z(rows, T), a_glob=z(rows, E),
+               a_proj=z(rows, P, H))
+    for b in range(B):
+        for t in range(_len(lens, b, T)):
+            row = b * T + t
+            hc, lg = t_["hc"][b, t], t_["logit"][row]
+            r_hc = w["fc.weight"][t_["tok"][b, t + 1]] * hc / stab(lg) * lg                          # :1033-1050
+            r_h2 = t_["h2"][b, t + 1] / stab(hc) * r_hc                                              # :1051-1054
+            r_ch = t_["ctx_hat"][b, t] / stab(hc) * r_hc                                             # :1056-1059
+            out["r_ch0"][row] = r_ch
+            r_c2, r_c1, r_glob = z(H), z(H), z(E)
+            for i in range(t, -1, -1):
+                rc = r_c2 + r_h2                                                                     # :1061
+                g2, cn = t_["g2"][b, i], t_["c2"][b, i + 1]
+                r_g = t_["i2"][b, i] * torch.tanh(g2) / stab(cn) * rc                                # :1062-1065
+                r_c2 = t_["f2"][b, i] * t_["c2"][b, i] / stab(cn) * rc                               # :1066-1069
+                rx2 = t_["xh2"][b, i] * mm(r_g / stab(g2), wg2, order)                               # :1070-1073  [ctx_hat | h1 | h2]
+                r_h2p, r_h1 = rx2[2 * H:], rx2[H:2 * H]                                              # :1074, :1075
+                r_ch = (r_ch if i == t else 0) + rx2[:H]                                             # :1076 (r_ctx_hat[i] is zero but at i = t)
+                ch, cx, beta = t_["ctx_hat"][b, i], t_["ctx"][b, i], t_["beta"][b, i]
+                r_s = beta * t_["s"][b, i] / stab(ch) * r_ch                                         # :1077-1080
+                r_cx = cx * (1 - beta) / stab(ch) * r_ch                                             # :1081-1084
+                out["wacc"][row, i] = r_cx / stab(cx)                                                # :1091-1095, the pixel spread's factor
+                rc = (r_c1 + r_s) + r_h1                                                             # :1096, :1097
+                g1, cn = t_["g1"][b, i], t_["c1"][b, i + 1]
+                r_g = t_["i1"][b, i] * torch.tanh(g1) / stab(cn) * rc                                # :1098-1101
+                r_c1 = t_["f1"][b, i] * t_["c1"][b, i] / stab(cn) * rc                               # :1102-1105
+                A = r_g / stab(g1)
+                rx1 = t_["xh1"][b, i] * mm(A, wg1, order)                                            # :1106-1109  [h2 | glob | emb | h1]
+                r_h2 = r_h2p + rx1[:H]                                                               # :1111 (:1110's r_h1[i] is dead)
+                r_glob = r_glob + rx1[H:H + E]                                                       # :1114
+                out["r_words"][row, i] = tot(rx1[H + E:H + 2 * E], order)                            # :1115, :1129
+            if t == T - 1:                 # what the last lock-step leaves in the GEMM buffers
+                out["A"][row], out["rx"][row] = A, rx1
+            out["r_h2n"][row], out["r_h2p"][row], out["r_c2"][row], out["r_c1"][row], out["r_glob"][row] = r_h2, r_h2p, r_c2, r_c1, r_glob
+            out["r_words_norm"][row] = _norm_words(out["r_words"][row], t)
+            out["a_glob"][row] = r_glob / stab(t_["glob_pre"][b])                                    # :1116-1119, prologue
+            spread = _over_steps([t_["alpha"][b, i][:, None] * out["wacc"][row, i][None] for i in range(t + 1)], order)
+            out["a_proj"][row] = t_["Vp"][b] * spread / stab(t_["proj_pre"][b])                      # :1091-1095 summed, :1125-1128 prologue
+    return out
+
+
+def gridtd_u(r_avg, avg, T, P):
+    """:1121-1124 folded into the projector rule's bracket: U[row] = r_avg[row] / (P z~(avg[image]))"""
+    return r_avg / (P * stab(avg.to(r_avg.dtype)).repeat_interleave(T, 0))
+
+
+# ---- AoA relevance -----------------------------------------------------------------------------------------------------------------------
+def aoa_rel(d, sd, head, lens, dtype, order):
+    """-> A0 (rows, H) = r_caoa / z~(lin), r_ctx (rows, H), r_hn, r_glob, A (rows, H), rx (rows, E+2H), r_words / r_words_norm (rows, T),
+    a_val (rows, P, H) (zero outside the head's columns), U (rows, H) = r_glob / (P z~(glob))"""
+    t_, w = _cast(d, sd, dtype)
+    B, T, NH, P = t_["alpha"].shape
+    dk = H // NH
+    l = "LanguageLSTM."
+    wg = torch.cat([w[l + "weight_ih"][2 * H:3 * H], w[l + "weight_hh"][2 * H:3 * H]], 1)            # (H, E+2H)
+    rows = B * T
+    z = lambda *s: torch.zeros(*s, dtype=dtype)
+    out = dict(A0=z(rows, H), r_ctx=z(rows, H), r_hn=z(rows, H), r_glob=z(rows, H), A=z(rows, H), rx=z(rows, E + 2 * H), r_words=z(rows, T),
+               r_words_norm=z(rows, T), a_val=z(rows, P, H), U=z(rows, H))
+    sl = slice(head * dk, (head + 1) * dk)
+    for b in range(B):
+        for t in range(_len(lens, b, T)):
+            row = b * T + t
+            hc, lg = t_["hc"][b, t], t_["logit"][row]
+            r_hc = w["fc.weight"][t_["tok"][b, t + 1]] * hc / stab(lg) * lg                          # :1081-1095
+            r_h = t_["h"][b, t + 1] / stab(hc) * r_hc                                                # :1096-1099
+            r_ca = t_["c_aoa"][b, t] / stab(hc) * r_hc                                               # :1101-1104
+            out["A0"][row] = r_ca / stab(t_["lin"][b, t])
+            r_ctx = t_["ctx"][b, t] * mm(out["A0"][row], w["decoder_aoa_linear.weight"], order)      # :1107-1110
+            out["r_ctx"][row] = r_ctx
+            val = t_["value"][b][:, sl]                                                              # lrp_mha :848-860: one head
+            r_val = val * t_["alpha"][b, t, head][:, None] / stab(t_["ctx"][b, t][sl])[None] * r_ctx[sl][None]
+            out["a_val"][row][:, sl] = r_val / stab(val)                                             # :1141-1144, prologue
+            r_glob = z(H)
+            for i in range(t, -1, -1):
+                g = t_["g"][b, i]
+                r_g = t_["i"][b, i] * torch.tanh(g) / stab(t_["c"][b, i + 1]) * r_h                  # :1116-1120 (r_c = r_h, an assignment)
+                A = r_g / stab(g)
+                rx = t_["xh"][b, i] * mm(A, wg, order)                                               # :1125-1128  [emb | glob | h]
+                r_h = rx[E + H:]                                                                     # :1129
+                r_glob = r_glob + rx[E:E + H]                                                        # :1131
+                out["r_words"][row, i] = tot(rx[:E], order)                                          # :1130, :1149
+            if t == T - 1:
+                out["A"][row], out["rx"][row] = A, rx
+            out["r_hn"][row], out["r_glob"][row] = r_h, r_glob
+            out["r_words_norm"][row] = _norm_words(out["r_words"][row], t)
+            out["U"][row] = r_glob / (P * stab(t_["glob"][b]))                                       # :1136-1140
+    return out
+
+
+# ---- gridTD gradient / guided ------------------------------------------------------------------------------------------------------------
+def _cell_bwd(dh, dc, c_new, c_old, i, f, gpre, o):
+    """:1627-1637 / :1647-1657 -> (gate pre-activation gradients [i | f | g | o], d_c of the step before)"""
+    tc, ga = torch.tanh(c_new), torch.tanh(gpre)
+    dc = dc + dh * o * (1 - tc * tc)
+    gates = torch.cat([dc * ga * i * (1 - i), dc * c_old * f * (1 - f), dc * i * (1 - ga * ga), dh * tc * o * (1 - o)])
+    return gates, dc * f
+
+
+def gridtd_grad(d, sd, lens, dtype, order):
+    """-> d_h2n, d_c2, d_c1, d_ch0, d_h2p (rows, H), d_glob (rows, E), gates (rows, 4H), dx (rows, 3H), wacc (rows, T, H) = d_context per
+    time step, r_words / r_words_norm, a_proj (rows, P, H) = the pixel spread (:1642-1643)"""
+    t_, w = _cast(d, sd, dtype)
+    B, T = t_["beta"].shape
+    P = t_["alpha"].shape[-1]
+    a, l = "AdaLSTM.lstm_cell.", "LanguageLSTM."
+    w2 = torch.cat([w[l + "weight_ih"], w[l + "weight_hh"]], 1)                                      # (4H, 3H)
+    w1 = w[a + "weight_ih"]                                                                          # (4H, H+2E)
+    rows = B * T
+    z = lambda *s: torch.zeros(*s, dtype=dtype)
+    out = dict(d_h2n=z(rows, H), d_c2=z(rows, H), d_c1=z(rows, H), d_ch0=z(rows, H), d_h2p=z(rows, H), d_glob=z(rows, E), gates=z(rows, 4 * H),
+               dx=z(rows, 3 * H), wacc=z(rows, T, H), r_words=z(rows, T), r_words_norm=z(rows, T), a_proj=z(rows, P, H))
+    for b in range(B):
+        for t in range(_len(lens, b, T)):
+            row = b * T + t
+            d_h2 = w["fc.weight"][t_["tok"][b, t + 1]].clone()                                       # :1592-1625
+            d_ch = d_h2.clone()
+            out["d_ch0"][row] = d_ch
+            d_c2, d_c1, d_glob = z(H), z(H), z(E)
+            for i in range(t, -1, -1):
+                g2, d_c2 = _cell_bwd(d_h2, d_c2, t_["c2"][b, i + 1], t_["c2"][b, i], t_["i2"][b, i], t_["f2"][b, i], t_["g2"][b, i],
+                                     t_["o2"][b, i])                                                 # :1627-1637
+                dx2 = mm(g2, w2, order)                                                              # :1638-1639  [d_ctx_hat | d_h1 | d_h2]
+                d_h2p = dx2[2 * H:]
+                d_ch = (d_ch if i == t else 0) + dx2[:H]                                             # :1640
+                beta = t_["beta"][b, i]
+                out["wacc"][row, i] = d_ch * (1 - beta)                                              # :1641
+                tc1 = torch.tanh(t_["c1"][b, i + 1])
+                dc = d_c1 + d_ch * beta * t_["sgate"][b, i] * (1 - tc1 * tc1)                        # :1644-1645
+                g1, d_c1 = _cell_bwd(dx2[H:2 * H], dc, t_["c1"][b, i + 1], t_["c1"][b, i], t_["i1"][b, i], t_["f1"][b, i], t_["g1"][b, i],
+                                     t_["o1"][b, i])                                                 # :1646-1657
+                dx1 = mm(g1, w1, order)                                                              # :1659  [d_h2 | d_glob | d_emb]
+                d_h2 = d_h2p + dx1[:H]                                                               # :1660
+                d_glob = d_glob + dx1[H:H + E]                                                       # :1661
+                out["r_words"][row, i] = tot(dx1[H + E:], order)                                     # :1662
+            if t == T - 1:
+                out["gates"][row], out["dx"][row] = g1, dx1
+            out["d_h2n"][row], out["d_h2p"][row], out["d_c2"][row], out["d_c1"][row], out["d_glob"][row] = d_h2, d_h2p, d_c2, d_c1, d_glob
+            out["r_words_norm"][row] = _norm_words(out["r_words"][row], t)
+            out["a_proj"][row] = _over_steps([t_["alpha"][b, i][:, None] * out["wacc"][row, i][None] for i in range(t + 1)], order)
+    return out
+
+
+# ---- AoA gradient ------------------------------------------------------------------------------------------------------------------------
+def aoa_grad(d, sd, head, lens, dtype, order):
+    """-> d_h, d_c, dA, dB, d_glob (rows, H), gates (rows, 4H), dx (rows, E+2H), r_words / r_words_norm, d_ctx (rows, H) (zero outside the
+    head's columns), v1, v2 (rows, C) and d_feat (rows, P, C) = alpha[head] (x) v1 + v2 (gradient_mha :1415-1433 through v_proj and the
+    projector, both rank-1 in the pixel index)"""
+    t_, w = _cast(d, sd, dtype)
+    B, T, NH, P = t_["alpha"].shape
+    dk = H // NH
+    l = "LanguageLSTM."
+    wc = torch.cat([w[l + "weight_ih"], w[l + "weight_hh"]], 1)                                      # (4H, E+2H)
+    w_proj = w["img_projector.weight"].reshape(H, -1)
+    Cc = w_proj.shape[1]
+    rows = B * T
+    z = lambda *s: torch.zeros(*s, dtype=dtype)
+    out = dict(d_h=z(rows, H), d_c=z(rows, H), dA=z(rows, H), dB=z(rows, H), d_glob=z(rows, H), gates=z(rows, 4 * H), dx=z(rows, E + 2 * H),
+               r_words=z(rows, T), r_words_norm=z(rows, T), d_ctx=z(rows, H), v1=z(rows, Cc), v2=z(rows, Cc), d_feat=z(rows, P, Cc))
+    sl = slice(head * dk, (head + 1) * dk)
+    for b in range(B):
+        for t in range(_len(lens, b, T)):
+            row = b * T + t
+            d_hc = w["fc.weight"][t_["tok"][b, t + 1]]                                               # :1461-1466
+            sg = t_["sg"][b, t]
+            dA, dB = d_hc * sg, d_hc * t_["lin"][b, t] * (1 - sg) * sg                               # :1467-1468
+            out["dA"][row], out["dB"][row] = dA, dB
+            out["d_ctx"][row][sl] = mm(dA, w["decoder_aoa_linear.weight"], order)[sl]                # :1469, gradient_mha :1428
+            d_h = d_hc + mm(dB, w["decoder_aoa_linear_gate.weight"], order)                          # :1470
+            d_c, d_glob = z(H), z(H)
+            for i in range(t, -1, -1):
+                gates, d_c = _cell_bwd(d_h, d_c, t_["c"][b, i + 1], t_["c"][b, i], t_["i"][b, i], t_["f"][b, i], t_["g"][b, i],
+                                       t_["o"][b, i])                                                # :1474-1484
+                dx = mm(gates, wc, order)                                                            # :1485  [d_emb | d_glob | d_h]
+                d_glob = dx[E:E + H]                                                                 # :1487, an assignment: i = 0 survives
+                d_h = dx[E + H:]
+                out["r_words"][row, i] = tot(dx[:E], order)                                          # :1488
+            if t == T - 1:
+                out["gates"][row], out["dx"][row] = gates, dx
+            out["d_h"][row], out["d_c"][row], out["d_glob"][row] = d_h, d_c, d_glob
+            out["r_words_norm"][row] = _norm_words(out["r_words"][row], t)
+            u = mm(out["d_ctx"][row], w["decoder_v_proj.weight"], order)                             # :1489
+            out["v1"][row] = mm(u, w_proj, order)                                                    # :1492
+            out["v2"][row] = mm(d_glob, w_proj, order) / P                                           # :1491
+            out["d_feat"][row] = t_["alpha"][b, t, head][:, None] * out["v1"][row][None] + out["v2"][row][None]
+    return out
+
+
+# ---- the drawn traces ---------------------------------------------------------------------------------------------------------------------
+# (family, T, lens) of every committed case; B = len(lens) or 2.  tests/test_decoder_restate_host.py holds every one of them to the
+# yardstick condition on the CPU; tests/test_gpu_decoder_alone.py runs the kernels on them.
+T_CASES = [(3, None), (3, (3, 2)), (3, (2, 0)), (26, None), (26, (26, 2)), (26, (2, 0))]
+AOA_B3 = (11, (3, 0, 11))
+P_DRAW, NH_DRAW = 36, 8
+
+
+def _plant(x, gen):
+    """one channel of every row exact 0, one -0.0, and in the first row one entry each at +0.004 and -0.004 (the branches of z~)"""
+    c = torch.randperm(x.shape[-1], generator=gen)[:4].tolist()
+    x[..., c[0]] = 0.0
+    x[..., c[1]] = -0.0
+    first = (0,) * (x.dim() - 1)
+    x[first + (c[2],)], x[first + (c[3],)] = 0.004, -0.004
+    return x
+
+
+def _floor(x, lo):
+    """|x| >= lo, signs kept (the conditioning of the gridTD chain at T = 26: tests/test_gpu_decoder_alone.py)"""
+    return torch.where(x.abs() < lo, lo * torch.where(x < 0, -torch.ones_like(x), torch.ones_like(x)), x)
+
+
+def _common(B, T, gen, V):
+    rnd = lambda *s: torch.randn(*s, generator=gen)
+    tok = torch.randint(1, V - 3, (B, T + 1), generator=gen)
+    tok[0, 3] = 0                                   # the target of row 2 is token 0, whose fc row `np_state` zeroes: an all-zero row
+    logit = rnd(B * T)
+    logit[1] = 0.0                                  # one logit = 0 (row 1: live in every case)
+    logit[0], logit[3] = 0.004, -0.004
+    return rnd, tok, logit
+
+
+@functools.lru_cache(maxsize=None)
+def draw_gridtd(B, T, seed, V, floor=False, grad=False):
+    """trace and encoder tensors of the gridTD decoder, drawn: randn pre-activations and states, sigmoid gates and beta, softmax alpha,
+    relu(randn) ctx / Vp, the planted edges.  floor: |c1|, |c2|, |g1|, |g2| >= 0.2 outside the planted entries."""
+    gen = torch.Generator(device="cpu").manual_seed(seed)
+    rnd, tok, logit = _common(B, T, gen, V)
+    P = P_DRAW
+    sig = lambda *s: torch.sigmoid(rnd(*s))
+    d = dict(xh1=rnd(B, T, 2 * E + 2 * H), xh2=rnd(B, T, 3 * H), h2=0.5 * rnd(B, T + 1, H), tok=tok, logit=logit,
+             alpha=torch.softmax(rnd(B, T, P), -1), beta=sig(B, T), s=0.5 * rnd(B, T, H), ctx=torch.relu(rnd(B, T, H)))
+    for k in ("c1", "c2"):
+        d[k] = rnd(B, T + 1, H)
+    for k in ("g1", "g2"):
+        d[k] = rnd(B, T, H)
+    if floor:
+        for k in ("c1", "c2", "g1", "g2"):
+            d[k] = _floor(d[k], 0.2)
+    for k in ("i1", "f1", "i2", "f2") + (("o1", "o2", "sgate") if grad else ()):
+        d[k] = sig(B, T, H)
+    d["proj_pre"], d["glob_pre"], d["avg"] = rnd(B, P, H), rnd(B, E), torch.relu(rnd(B, H))
+    for k in ("ctx", "c1", "c2", "g1", "g2", "proj_pre", "glob_pre", "avg"):
+        # (c[i + 1] is the denominator; the running denominators are planted at time step 0 alone - every live row ends there -: a zero
+        # under z~ multiplies by 100, and one in every step of a chain that feeds itself leaves fp32 nothing to be graded on)
+        _plant(d[k][:, 1] if k in ("c1", "c2") else d[k][:, 0] if k in ("g1", "g2") else d[k], gen)
+    d["Vp"] = torch.relu(d["proj_pre"])
+    d["ctx_hat"] = d["beta"][..., None] * d["s"] + (1 - d["beta"][..., None]) * d["ctx"]
+    d["hc"] = d["h2"][:, 1:] + d["ctx_hat"]
+    return d
+
+
+@functools.lru_cache(maxsize=None)
+def draw_aoa(B, T, seed, V, grad=False):
+    """the same for the AoA decoder: relu(randn) ctx / Vp / value, planted ctx, lin, value, glob, proj_pre, c[i + 1], g"""
+    gen = torch.Generator(device="cpu").manual_seed(seed)
+    rnd, tok, logit = _common(B, T, gen, V)
+    P, NH = P_DRAW, NH_DRAW
+    sig = lambda *s: torch.sigmoid(rnd(*s))
+    d = dict(xh=rnd(B, T, E + 2 * H), h=0.5 * rnd(B, T + 1, H), c=rnd(B, T + 1, H), g=rnd(B, T, H), i=sig(B, T, H), f=sig(B, T, H), tok=tok,
+             logit=logit, ctx=torch.relu(rnd(B, T, H)), lin=rnd(B, T, H), alpha=torch.softmax(rnd(B, T, NH, P), -1),
+             value=torch.relu(rnd(B, P, H)), proj_pre=rnd(B, P, H))
+    if grad:
+        d["o"], d["sg"] = sig(B, T, H), sig(B, T, H)
+    d["glob"] = torch.relu(rnd(B, H))
+    for k in ("ctx", "lin", "value", "glob", "proj_pre", "c", "g"):
+        _plant(d[k][:, 1] if k == "c" else d[k][:, 0] if k == "g" else d[k], gen)          # (as in draw_gridtd)
+    d["Vp"] = torch.relu(d["proj_pre"])
+    d["c_aoa"] = sig(B, T, H) * d["lin"]
+    d["hc"] = d["h"][:, 1:] + d["c_aoa"]
+    return d
+
+
+V_DRAW = 203
+FAMILIES = {"gridtd_rel": (gridtd_rel, False), "gridtd_grad": (gridtd_grad, False), "aoa_rel": (aoa_rel, True), "aoa_grad": (aoa_grad, True)}
+CASES = [(f, T, lens) for f in FAMILIES for (T, lens) in T_CASES + ([AOA_B3] if f.startswith("aoa") else [])]
+
+
+# draws that missed the yardstick condition (tests/test_decoder_restate_host.py) and were drawn again: (family, T, lens) -> how often
+RESEED = {("gridtd_rel", 3, None): 1}
+
+
+def head_of(T, lens):
+    """the attention head an AoA case explains: 0, 4 and 7 over the cases"""
+    return (0, 4, 7)[(T_CASES + [AOA_B3]).index((T, lens)) % 3]
+
+
+@functools.lru_cache(maxsize=None)
+def np_state(kind):
+    """the small-V model the kernel tests build their engine from (numpy, as lrp_amd.weights makes it), fc row 0 zeroed"""
+    from lrp_amd import weights
+    if kind == "gridtd":
+        sd = weights.make_gridtd_bu_state(seed=5, vocab_size=V_DRAW, feat_dim=64, num_pixels=P_DRAW)
+    else:
+        sd = weights.make_aoa_state(seed=5, vocab_size=V_DRAW, feat_dim=64, with_encoder=False)
+    sd["fc.weight"][0] = 0.0          # <pad>: the row whose relevance is zero everywhere (r_words / max|r_words| must leave it alone)
+    return sd
+
+
+@functools.lru_cache(maxsize=None)
+def state(kind):
+    return {k: torch.from_numpy(v) for k, v in np_state(kind).items()}
+
+
+@functools.lru_cache(maxsize=None)
+def case(family, T, lens):
+    """(d, sd, B) of a committed case.  gridTD relevance at T = 26 takes the floored draw: unfloored, |r| grows to 1e19 along the chain
+    and plain fp32 is 1e-4 from fp64 - a bound from that has no teeth (tests/test_gpu_decoder_alone.py, Conditioning)."""
+    B = 2 if lens is None else len(lens)
+    seed = 1000 + 37 * T + 7 * B + (0 if lens is None else 1 + sum(lens)) + 100000 * RESEED.get((family, T, lens), 0)
+    grad = family.endswith("grad")
+    if family.startswith("gridtd"):
+        return draw_gridtd(B, T, seed, V_DRAW, floor=(T > 3 and not grad), grad=grad), state("gridtd"), B
+    return draw_aoa(B, T, seed, V_DRAW, grad=grad), state("aoa"), B
+
+
+@functools.lru_cache(maxsize=None)
+def references(family, T, lens):
+    """(fp64 evaluation, [fp32 evaluation per order in ORDERS], mask of the live rows) of a committed case - computed once per process"""
+    d, sd, B = case(family, T, lens)
+    fn, has_head = FAMILIES[family]
+    args = (d, sd, head_of(T, lens), lens) if has_head else (d, sd, lens)
+    live = torch.tensor([t < _len(lens, b, T) for b in range(B) for t in range(T)])
+    return fn(*args, torch.float64, "torch"), [fn(*args, torch.float32, o) for o in ORDERS], live
+
+
+def worst_of(refs32, ref64, key, sel=None):
+    """of the fp32 evaluations `refs32` (one per order), the one farthest from fp64 at `key` - the yardstick of the kernel tests"""
+    pick = (lambda v: v) if sel is None else (lambda v: v[sel])
+    scale = pick(ref64[key]).abs().max().clamp_min(1e-300)
+    errs = [float((pick(r[key]).double() - pick(ref64[key])).abs().max() / scale) for r in refs32]
+    return refs32[errs.index(max(errs))][key], errs
