@@ -15,13 +15,6 @@
 #pragma once
 #include "conv_mfma.h"
 
-#ifndef LRPX6_NBQ
-#define LRPX6_NBQ ((HW <= 56) ? 5 : 4)   // B-fragment register queue depth (k-steps in flight: NBQ-1); 5 spills at 112/224
-#endif
-#ifndef LRPX6_APIPE
-#define LRPX6_APIPE 0    // 1: A fragments read one accumulator tile ahead (sched_group_barrier pinned)
-#endif
-
 namespace lrpx {
 
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
@@ -155,7 +148,7 @@ __global__ __launch_bounds__(64 * MT * NWN, 2) void conv_bf16x6_kernel(ConvArgs 
         for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
 
     // B fragments: per k-step three planes of 64 lanes x 16 B, one contiguous stream per channel block
-    constexpr int NBQ = LRPX6_NBQ;
+    constexpr int NBQ = (HW <= 56) ? 5 : 4;   // register queue depth (k-steps in flight: NBQ-1); 5 spills at 112/224
     const u32x4* wp = reinterpret_cast<const u32x4*>(a.wp) + (long)ocb * nchunk * (TAPS * 3 * 64) + lane;
     const int last_step = nchunk * TAPS - 1;
     u32x4 bq[NBQ][3];
@@ -179,14 +172,8 @@ __global__ __launch_bounds__(64 * MT * NWN, 2) void conv_bf16x6_kernel(ConvArgs 
         LRPX_T(tb);
         if (wave_active) {
             const char* abuf = ldsb + (DB ? (chunk & 1) : 0) * BUFB;
-            // A fragments run one accumulator tile ahead of the MFMAs that consume them (the LDS latency of a read
-            // issued right before its MFMA is otherwise exposed 63 times per chunk)
-#if LRPX6_APIPE
-            bf16x8 n0 = *reinterpret_cast<const bf16x8*>(abuf + abase[0]);
-            bf16x8 n1 = *reinterpret_cast<const bf16x8*>(abuf + abase[0] + 32);
-            bf16x8 n2 = *reinterpret_cast<const bf16x8*>(abuf + abase[0] + 64);
-            __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);           // (tile 0 of tap 0)
-#endif
+            // (A fragments are read where they are used and the compiler schedules them; the B6 kernels of conv_f16x3.h pin the
+            // reads one accumulator tile ahead)
 #pragma unroll
             for (int tap = 0; tap < TAPS; ++tap) {
                 const long nxt = (long)min(chunk * TAPS + tap + NBQ - 1, last_step) * 3;
@@ -197,21 +184,10 @@ __global__ __launch_bounds__(64 * MT * NWN, 2) void conv_bf16x6_kernel(ConvArgs 
                 const bf16x8 b2 = __builtin_bit_cast(bf16x8, bq[0][2]);
 #pragma unroll
                 for (int j = 0; j < 7; ++j) {
-#if LRPX6_APIPE
-                    const bf16x8 a0 = n0, a1 = n1, a2 = n2;
-                    if (!(tap == TAPS - 1 && j == 6)) {
-                        const int jn = (j + 1) % 7, tn = tap + (j == 6 ? 1 : 0);
-                        const char* ap = abuf + abase[jn] + (tn / 3) * PITCH + (tn % 3) * PSTRIDE;
-                        n2 = *reinterpret_cast<const bf16x8*>(ap + 64);
-                        n1 = *reinterpret_cast<const bf16x8*>(ap + 32);
-                        n0 = *reinterpret_cast<const bf16x8*>(ap);
-                    }
-#else
                     const char* ap = abuf + abase[j] + (tap / 3) * PITCH + (tap % 3) * PSTRIDE;
                     const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(ap);
                     const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(ap + 32);
                     const bf16x8 a2 = *reinterpret_cast<const bf16x8*>(ap + 64);
-#endif
                     // smallest terms first
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b0, acc[j], 0, 0, 0);
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc[j], 0, 0, 0);
@@ -219,10 +195,6 @@ __global__ __launch_bounds__(64 * MT * NWN, 2) void conv_bf16x6_kernel(ConvArgs 
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc[j], 0, 0, 0);
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc[j], 0, 0, 0);
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc[j], 0, 0, 0);
-#if LRPX6_APIPE
-                    __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);   // the 3 reads of the NEXT tile ...
-                    __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);   // ... then the 6 MFMAs of this one
-#endif
                 }
 #pragma unroll
                 for (int i = 0; i < NBQ - 1; ++i)

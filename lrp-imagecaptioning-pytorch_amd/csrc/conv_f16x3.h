@@ -38,22 +38,8 @@ __host__ __device__ __forceinline__ int f16_scale_exp(unsigned amax_bits) {
     const int k = 14 - (e - 127);
     return k > 120 ? 120 : k;
 }
-// Which narrow format carries the two cross products of the F8 kernels: 1 = block-scaled fp6 e2m3 (v_mfma_scale_f32_32x32x64_f8f6f4
-// at 32 cycles per K = 64, as fast as one fp16 MFMA of K = 16), 0 = fp8 e4m3 (64 cycles; rounds 1-2 of this kernel)
-#ifndef LRPXH_XP6
-#define LRPXH_XP6 1
-#endif
-// F8 variant (cross products on the fp8 matrix cores, see below): operands are scaled into [2^11, 2^12) instead, so
-// that x * 2^-4 fits fp8 e4m3 (max 448) and the fp16 residual * 2^4 does too.  (fp6: every 16-channel slice carries its own
-// block exponent, the operands keep the fp16 range.)
-template <bool F8>
-__host__ __device__ __forceinline__ int split_scale_exp(unsigned amax_bits) {
-    if constexpr (!F8 || (LRPXH_XP6 != 0)) return f16_scale_exp(amax_bits);
-    const int e = (int)((amax_bits >> 23) & 0xff);
-    if (e == 0 || e == 255) return 0;
-    const int k = 11 - (e - 127);
-    return k > 120 ? 120 : k;
-}
+// (The F8 kernels - two cross products in block-scaled fp6 e2m3, below - scale their operands the same way: every 16-channel slice
+// carries its own block exponent, the operands keep the fp16 range.)
 __host__ __device__ __forceinline__ float exp2i(int k) {   // 2^k, |k| <= 126
     const unsigned b = (unsigned)(k + 127) << 23;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -63,9 +49,6 @@ __host__ __device__ __forceinline__ float exp2i(int k) {   // 2^k, |k| <= 126
 #endif
 }
 
-__device__ __forceinline__ unsigned pack_f16(_Float16 a, _Float16 b) {
-    return (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
-}
 // two-way split of an (already scaled) value: x ~= hi + lo
 __device__ __forceinline__ void split2(float x, _Float16& hi, _Float16& lo) {
     hi = (_Float16)x;                 // v_cvt_f16_f32, round to nearest even; inf / nan stay inf / nan
@@ -75,22 +58,12 @@ __device__ __forceinline__ void split2(float x, _Float16& hi, _Float16& lo) {
 // the same for two values at once, results as packed fp16 pairs: v_cvt_pk_f16_f32 (gfx950) converts and packs in one instruction
 // (round to nearest even, bit-identical to two scalar conversions: 5 VALU instructions per pair instead of 10)
 typedef _Float16 f16x2_ __attribute__((ext_vector_type(2)));
-#ifndef LRPXH_PK_CVT
-#define LRPXH_PK_CVT 1
-#endif
 __device__ __forceinline__ void split2_pk(const f32x2_ x, unsigned& hi, unsigned& lo, f32x2_& hi_f) {
-    if constexpr (LRPXH_PK_CVT != 0) {
-        const f16x2_ h = __builtin_convertvector(x, f16x2_);
-        hi_f = __builtin_convertvector(h, f32x2_);
-        const f16x2_ l = __builtin_convertvector(x - hi_f, f16x2_);
-        hi = __builtin_bit_cast(unsigned, h);
-        lo = __builtin_bit_cast(unsigned, l);
-    } else {
-        _Float16 h0, h1, l0, l1;
-        split2(x[0], h0, l0); split2(x[1], h1, l1);
-        hi_f = f32x2_{(float)h0, (float)h1};
-        hi = pack_f16(h0, h1); lo = pack_f16(l0, l1);
-    }
+    const f16x2_ h = __builtin_convertvector(x, f16x2_);
+    hi_f = __builtin_convertvector(h, f32x2_);
+    const f16x2_ l = __builtin_convertvector(x - hi_f, f16x2_);
+    hi = __builtin_bit_cast(unsigned, h);
+    lo = __builtin_bit_cast(unsigned, l);
 }
 
 // B6 (conv mode 1, "bf16x6" in this kernel's tiling): EXACT three-way split of two values at once, x == p0 + p1 + p2 with every part a
@@ -108,12 +81,6 @@ __device__ __forceinline__ void split3_pk(const f32x2_ x, unsigned& p0, unsigned
     p2 = __builtin_bit_cast(unsigned, __builtin_convertvector(r2, bf16x2_));
 }
 
-// two / four floats -> fp8 e4m3 (OCP, round to nearest even), packed
-__device__ __forceinline__ unsigned pack_fp8x4(float x0, float x1, float x2, float x3) {
-    int w = __builtin_amdgcn_cvt_pk_fp8_f32(x0, x1, 0, false);
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(x2, x3, w, true);
-    return (unsigned)w;
-}
 typedef int i32x8_ __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ float wave_max(float v) {
@@ -142,12 +109,6 @@ static __device__ unsigned long long g_stamp_h3[12];
 #define LRPXH_T(v)
 #endif
 
-// F8 slot map (shared with pack_weights_f16f8_kernel).  The 18 cross-product (tap, 16 channels) K-slices of a K-chunk -
-// "L": (x - hi) * W and "S": x * (W - hi_W), taps 0-8 each - fill five K = 64 fp8 MFMAs of four slices: MFMA m covers
-// taps 2m and 2m+1 (tap 9 does not exist: zero weights), lanes 0-31 (k = 0..31) hold the L slices of both taps, lanes
-// 32-63 (k = 32..63) the S slices.  The two lane halves then read the same pixels, 16 bytes apart (planes 48 / 32).
-__host__ __device__ constexpr int f8_slot_tap(int m, int i) { return 2 * m + i; }        // > 8: zero weights
-
 // REL_MUL epilogue with 16-byte accesses ("wide"): out = x * acc for the wave's 7 accumulator tiles of 32 pixels x 32
 // channels.  In the MFMA result layout a lane owns ONE channel of 16 pixels, so the plain epilogue issues 112 dword loads
 // and 112 dword stores per lane, each touching two 128-byte runs - measured 21 % of a workgroup tile's time on the 28x28
@@ -156,10 +117,12 @@ __host__ __device__ constexpr int f8_slot_tap(int m, int i) { return 2 * m + i; 
 // comes back as float4 along the channels: lane L owns the channel quad L % 8 of pixel rows L / 8 + 8k, k = 0..3 - 4
 // loads + 4 stores of 16 bytes per lane and tile, 4x fewer memory instructions, whole 128-byte runs per 8 lanes.
 // Arithmetic, results and the per-map maxima are the same as in epi_gather / epi_finish (bit-identical outputs).
+// Only the map-straddling kernels (28x28 / 14x14) take it: the aligned ones are 1-5 % slower with it than with epi_rel_mul_al.
 template <int HW, bool AL, int EPI>
 __device__ __forceinline__ void epi_rel_mul_wide(const ConvArgs& a, f32x16 (&acc)[7], float* __restrict__ scr, const int wm,
                                                  const int ocb, const int lane, const long g0, const long total_pix,
                                                  unsigned* __restrict__ oamax, const int* __restrict__ tab) {
+    static_assert(!AL, "epi_rel_mul_wide: map-straddling tiles only (map-aligned kernels use epi_rel_mul_al)");
     constexpr int PITCH_F = 36;
     const int li = lane & 31, lh = lane >> 5;
     const int qd = lane & 7, r0 = lane >> 3;
@@ -179,26 +142,21 @@ __device__ __forceinline__ void epi_rel_mul_wide(const ConvArgs& a, f32x16 (&acc
     const long pix0 = g0 * HW;
     // Per accumulator tile j (32 consecutive pixels, shorter than a map: at most ONE map boundary inside it) everything
     // but the lane's pixel offset dq = r0 + 8k is wave-uniform: first map n0 and pixel-in-map p0 of the tile's first pixel,
-    // the images of n0 and n0 + 1.  (Aligned tiles: the whole workgroup tile lies in one map.)
+    // the images of n0 and n0 + 1 (from the workgroup's table, filled in the prologue).
     auto tile_base = [&](const int j, unsigned& n0, int& p0, long& b0, long& b1) {
         const unsigned q0t = (unsigned)(wm * 224 + 32 * j);
         const unsigned rr = q0t / (unsigned)HW, c0 = q0t - rr * HW;
         const unsigned g = (unsigned)g0 + rr;
         n0 = g / (unsigned)HW;
         p0 = (int)((g - n0 * HW) * HW + c0);
-        long img0, img1;
-        if constexpr (AL) {
-            img0 = img1 = a.map2img ? a.map2img[min((int)n0, nmax)] : (long)n0;
-        } else {       // map-straddling tiles: the two images of the tile from the workgroup's table (filled in the prologue)
-            img0 = tab[(wm * 7 + j) * 4 + 2]; img1 = tab[(wm * 7 + j) * 4 + 3];
-        }
+        const long img0 = tab[(wm * 7 + j) * 4 + 2], img1 = tab[(wm * 7 + j) * 4 + 3];
         b0 = (img0 * P + p0) * (long)ncol + oc4;
         b1 = (img1 * P + p0 - (long)P) * (long)ncol + oc4;
     };
-    // ---- multiplicand loads run ahead of the tiles: all 28 up front for aligned tiles; map-straddling tiles (two
-    // candidate addresses per load, more live registers) keep a ring of 3 tiles (issued two tiles ahead: such a load is
-    // older than the stores it would otherwise queue behind in the in-order vmcnt)
-    constexpr int RING = AL ? 7 : 3;
+    // ---- multiplicand loads run ahead of the tiles: two candidate addresses per load, many live registers, so a ring of
+    // 3 tiles (issued two tiles ahead: such a load is older than the stores it would otherwise queue behind in the
+    // in-order vmcnt)
+    constexpr int RING = 3;
     f32x4 xv[RING][4];
     auto load_x = [&](const int j) {
         unsigned n0; int p0; long b0, b1;
@@ -207,24 +165,23 @@ __device__ __forceinline__ void epi_rel_mul_wide(const ConvArgs& a, f32x16 (&acc
         for (int k = 0; k < 4; ++k) {
             const int dq = r0 + 8 * k;
             const long gp = pix0 + wm * 224 + 32 * j + dq;
-            const bool ok = col_ok && (AL || gp < total_pix);
-            const long xi = ((AL || p0 + dq < (int)P) ? b0 : b1) + (long)dq * ncol;
+            const bool ok = col_ok && gp < total_pix;
+            const long xi = (p0 + dq < (int)P ? b0 : b1) + (long)dq * ncol;
             xv[j % RING][k] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (ok && !(LRPX_EPI_EXP & 1)) xv[j % RING][k] = *reinterpret_cast<const f32x4*>(X + xi);
         }
     };
 #pragma unroll
-    for (int j = 0; j < (AL ? 7 : 2); ++j) load_x(j);
+    for (int j = 0; j < 2; ++j) load_x(j);
     const unsigned n_first = (unsigned)g0 / (unsigned)HW;    // map of the workgroup tile's first pixel
-    float m_al = 0.f;
-    // map-straddling tiles: the 224 pixels of the workgroup touch at most the maps n_first, + 1, + 2 (a map has >= 196 pixels).  Their
+    // the 224 pixels of the workgroup touch at most the maps n_first, + 1, + 2 (a map has >= 196 pixels).  Their
     // maxima are kept per lane and reduced ONCE behind the last tile: amax_update reads the word first, and a wait for that read is a
     // wait for every store issued before it (one in-order counter) - two such waits per tile made the wave sit out the write latency
     // of each of its 7 tiles
     float mm0 = 0.f, mm1 = 0.f, mm2 = 0.f;
 #pragma unroll
     for (int j = 0; j < 7; ++j) {
-        if constexpr (!AL) { if (j + 2 < 7) load_x(j + 2); }
+        if (j + 2 < 7) load_x(j + 2);
 #pragma unroll
         for (int e = 0; e < 16; ++e) scr[((e & 3) + 8 * (e >> 2) + 4 * lh) * PITCH_F + li] = acc[j][e];
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // wave-private patch: LDS ops of one wave run in order
@@ -247,46 +204,33 @@ __device__ __forceinline__ void epi_rel_mul_wide(const ConvArgs& a, f32x16 (&acc
             }
             const int dq = r0 + 8 * k;
             const long gp = pix0 + wm * 224 + 32 * j + dq;
-            if (col_ok && (AL || gp < total_pix)) {
+            if (col_ok && gp < total_pix) {
                 float* op = reinterpret_cast<float*>(Ou + ((unsigned)((32 * j + 8 * k) * ostr * 4) + ooff));     // scalar base + 32-bit offset
 #if LRPX_EPI_EXP & 2
                 if (r[0] == 1.2345e-30f) *reinterpret_cast<f32x4*>(op) = r;
-#elif LRPXH_NT_STORE & 1
-                __builtin_nontemporal_store(r, reinterpret_cast<f32x4*>(op));
 #else
-                *reinterpret_cast<f32x4*>(op) = r;
+                __builtin_nontemporal_store(r, reinterpret_cast<f32x4*>(op));
 #endif
                 const float m = fmaxf(fmaxf(fabsf(r[0]), fabsf(r[1])), fmaxf(fabsf(r[2]), fabsf(r[3])));
-                if (AL || p0 + dq < (int)P) m0 = fmaxf(m0, m); else m1 = fmaxf(m1, m);
+                if (p0 + dq < (int)P) m0 = fmaxf(m0, m); else m1 = fmaxf(m1, m);
             }
         }
         if (oamax) {
-            if constexpr (AL) {
-                m_al = fmaxf(m_al, m0);
-            } else {
-                const int k0 = (int)(nt0 - n_first);               // 0 .. 2, wave-uniform
-                mm0 = fmaxf(mm0, k0 == 0 ? m0 : 0.f);
-                mm1 = fmaxf(mm1, k0 == 0 ? m1 : (k0 == 1 ? m0 : 0.f));
-                mm2 = fmaxf(mm2, k0 == 1 ? m1 : (k0 == 2 ? m0 : 0.f));
-            }
+            const int k0 = (int)(nt0 - n_first);               // 0 .. 2, wave-uniform
+            mm0 = fmaxf(mm0, k0 == 0 ? m0 : 0.f);
+            mm1 = fmaxf(mm1, k0 == 0 ? m1 : (k0 == 1 ? m0 : 0.f));
+            mm2 = fmaxf(mm2, k0 == 1 ? m1 : (k0 == 2 ? m0 : 0.f));
         }
     }
-    if constexpr (AL) {
-        if (oamax) {
-            m_al = wave_max(m_al);
-            if (lane == 0 && (int)n_first <= nmax) amax_update(&oamax[n_first], m_al);
-        }
-    } else {
-        if (oamax) {
-            mm0 = wave_max(mm0); mm1 = wave_max(mm1); mm2 = wave_max(mm2);
-            if (lane == 0 && (int)n_first <= nmax) amax_update(&oamax[n_first], mm0);
-            if (lane == 0 && (int)n_first + 1 <= nmax) amax_update(&oamax[n_first + 1], mm1);
-            if (lane == 0 && (int)n_first + 2 <= nmax) amax_update(&oamax[n_first + 2], mm2);
-        }
+    if (oamax) {
+        mm0 = wave_max(mm0); mm1 = wave_max(mm1); mm2 = wave_max(mm2);
+        if (lane == 0 && (int)n_first <= nmax) amax_update(&oamax[n_first], mm0);
+        if (lane == 0 && (int)n_first + 1 <= nmax) amax_update(&oamax[n_first + 1], mm1);
+        if (lane == 0 && (int)n_first + 2 <= nmax) amax_update(&oamax[n_first + 2], mm2);
     }
 }
 
-// ---- fp6 cross products (LRPXH_XP6) ----
+// ---- fp6 cross products of the F8 kernels ----
 typedef unsigned u32x6_ __attribute__((ext_vector_type(6)));
 typedef unsigned u32x3_ __attribute__((ext_vector_type(3)));
 typedef unsigned u32x16_ __attribute__((ext_vector_type(16)));
@@ -359,7 +303,7 @@ __device__ __forceinline__ void epi_rel_mul_al(const ConvArgs& a, f32x16 (&acc)[
     const unsigned p0 = ((unsigned)g0 - n * HW) * HW;           // pixel-in-map of the tile's first pixel
     const long img = a.map2img ? a.map2img[min((int)n, nmax)] : (long)n;
     float f = 1.f;                                              // (B6: exact bf16 splits, nothing was scaled)
-    if constexpr (!B6) f = exp2i(-split_scale_exp<F8>(in_amax[min((int)n, nmax)])) * inv_w;
+    if constexpr (!B6) f = exp2i(-f16_scale_exp(in_amax[min((int)n, nmax)])) * inv_w;
     const int ch = a.out_chunk;
     const int ostr = ch > 0 ? ch : ncol;
     // uniform bases (bytes) and the lane's offsets (bytes, 32-bit)
@@ -387,10 +331,8 @@ __device__ __forceinline__ void epi_rel_mul_al(const ConvArgs& a, f32x16 (&acc)[
             float* op = reinterpret_cast<float*>(Ou + (ub + ooff));
 #if LRPX_EPI_EXP & 2
             if (r == 1.2345e-30f) *op = r;
-#elif LRPXH_NT_STORE & 2
-            __builtin_nontemporal_store(r, op);
 #else
-            *op = r;
+            __builtin_nontemporal_store(r, op);
 #endif
             m = fmaxf(m, fabsf(r));
         }
@@ -411,7 +353,7 @@ __device__ __forceinline__ void epi_fwd_dual_al(const ConvArgs& a, f32x16 (&acc)
     const int nmax = a.n_maps - 1;
     const unsigned n = (unsigned)g0 / (unsigned)HW;             // the tile's image
     float f = 1.f;
-    if constexpr (!B6) f = exp2i(-split_scale_exp<F8>(in_amax[min((int)n, nmax)])) * inv_w;
+    if constexpr (!B6) f = exp2i(-f16_scale_exp(in_amax[min((int)n, nmax)])) * inv_w;
     const bool is_act = ocb * 32 < ncol;                        // wave-uniform
     const int ocl = (is_act ? ocb * 32 : ocb * 32 - ncol);      // first channel of the block inside its tensor
     if (ocl + li >= ncol) return;
@@ -462,10 +404,8 @@ __device__ __forceinline__ void epi_rel_mul_blk(const ConvArgs& a, f32x16 (&acc)
     auto store4 = [&](float* op, const f32x4 r) {
 #if LRPX_EPI_EXP & 2
         if (r[0] == 1.2345e-30f) *reinterpret_cast<f32x4*>(op) = r;
-#elif LRPXH_NT_STORE & 1
-        __builtin_nontemporal_store(r, reinterpret_cast<f32x4*>(op));
 #else
-        *reinterpret_cast<f32x4*>(op) = r;
+        __builtin_nontemporal_store(r, reinterpret_cast<f32x4*>(op));
 #endif
     };
     if constexpr (AL) {
@@ -473,7 +413,7 @@ __device__ __forceinline__ void epi_rel_mul_blk(const ConvArgs& a, f32x16 (&acc)
         const unsigned n = (unsigned)g0 / (unsigned)HW;
         const unsigned p0 = ((unsigned)g0 - n * HW) * HW + wm * 224;
         const long img = a.map2img ? a.map2img[min((int)n, nmax)] : (long)n;
-        const float f = exp2i(-split_scale_exp<F8>(in_amax[min((int)n, nmax)])) * inv_w;
+        const float f = exp2i(-f16_scale_exp(in_amax[min((int)n, nmax)])) * inv_w;
         const float* __restrict__ Xp = X + img * ximg + (long)chunk * cs_x + ((long)(p0 >> 5) << 9) + li * 4;
         f32x4 xv[7][4];
 #pragma unroll
@@ -522,10 +462,7 @@ __device__ __forceinline__ void epi_rel_mul_blk(const ConvArgs& a, f32x16 (&acc)
             f = __builtin_bit_cast(float, tab[(wm * 7 + j) * 4 + (second ? 1 : 0)]) * inv_w;
             kmap = (int)(n0 - n_first) + (second ? 1 : 0);         // 0 .. 2: the 224 pixels of a wave touch at most three maps
         };
-#ifndef LRPXH_BLK_RING
-#define LRPXH_BLK_RING 3          // multiplicand tiles in flight in the map-straddling epilogue (7: all loads before the first store)
-#endif
-        constexpr int RING = LRPXH_BLK_RING;
+        constexpr int RING = 3;           // multiplicand tiles in flight (as in epi_rel_mul_wide's map-straddling branch)
         f32x4 xv[RING][4];
         auto load_x = [&](const int j) {
             long gp, xoff; float f; int kmap;
@@ -575,11 +512,11 @@ __device__ __forceinline__ void epi_rel_mul_blk(const ConvArgs& a, f32x16 (&acc)
     }
 }
 
-// F8 ("f16+f8x2"): the two CROSS products a0*b1 + a1*b0 - 2^-11 of the result - do not need fp16 operands: with both
-// factors rounded to fp8 e4m3 (4 significand bits) their error is 2^-11 * 2^-4 per product, random sign; simulated
-// through all 13 layers the maps move by < 1e-5 of their maximum (tolerance 1e-4; plain f16x3: ~1e-6).  They run on
-// v_mfma_f32_32x32x64_f8f6f4, K = 64 = 4 (tap, 16-channel) slices: 5 fp8 MFMAs per K-chunk (f8_slot_*) instead of 18
-// fp16 ones.  LDS pixel (80 B as before): 16 fp16 hi | 16 fp8 of x*2^-4 | 16 fp8 of (x-hi)*2^4 | pad.
+// F8: the two CROSS products a0*b1 + a1*b0 - 2^-11 of the result - do not need fp16 operands.  They run as block-scaled fp6 e2m3
+// (one exponent per 16-channel slice) on v_mfma_scale_f32_32x32x64_f8f6f4, K = 64: 5 narrow MFMAs of 32 cycles per K-chunk
+// instead of 18 fp16 ones; MFMA m covers tap 2m in lanes 0-31 and tap 2m + 1 in lanes 32-63 (tap 9 does not exist: zero weights).
+// (Rounds 1-2 carried them as fp8 e4m3 at 64 cycles per MFMA; the name of the template argument is from then.  Error analysis of
+// both: DESIGN.md 5.1a / 5.1e.)  LDS pixel: see F8 in the kernel.
 //
 // B6 (conv mode 1): the same tiling, staging, B queue and epilogues with EXACT operand splits on the bf16 matrix cores - every fp32
 // operand a = a0 + a1 + a2 (three bf16 parts, 24 significand bits, fp32's exponent range: no operand scales, in_amax unused), the six
@@ -589,6 +526,7 @@ __device__ __forceinline__ void epi_rel_mul_blk(const ConvArgs& a, f32x16 (&acc)
 template <int HW, int MT, int NWN, bool DB, int EPI, bool POOL = false, bool F8 = false, bool B6 = false>
 __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f16x3_kernel(ConvArgs a, int m_tiles, int n_blocks) {
     static_assert(!(F8 && B6), "conv_f16x3_kernel: F8 (fp16 + narrow cross products) and B6 (exact bf16 splits) exclude each other");
+    static_assert(HW >= 14, "conv_f16x3_kernel: the A-fragment pipelines were measured on maps of 14 x 14 and larger only");
     LRPXH_T(t_start);
 #ifdef LRPX_STAMP
     unsigned long long s_issue = 0, s_mfma = 0, s_commit = 0, s_barrier = 0, s_tap0 = 0, s_tap1 = 0, s_tap2 = 0;
@@ -603,54 +541,29 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
     constexpr int STAGE_SCRATCH = NBUF * BUFB + 16;    // 256 bytes behind the buffers take the writes of items with nothing to write
     constexpr int POOL_SCRATCH = STAGE_SCRATCH;
     constexpr bool AL = (H % C::R == 0);               // a workgroup tile never straddles two maps
-#ifndef LRPXH_HOIST_MASK
-#define LRPXH_HOIST_MASK 1
-#endif
-    // staging descriptors stay in registers (see item()): bit 0: 56 non-pooled, 1: 56 pooled, 2: 112 pooled, 3: 224 pooled
-#ifndef LRPXH_F8_HOIST
-#define LRPXH_F8_HOIST 1      // measured with the row-wise item layout: 56x56 F8 kernel 2.33 -> 2.12 ms per launch
-#endif
-    constexpr bool HOIST = (!F8 || LRPXH_F8_HOIST) && AL && (((LRPXH_HOIST_MASK & 1) && HW == 56 && !POOL) || ((LRPXH_HOIST_MASK & 2) && HW == 56 && POOL) ||
-                                  ((LRPXH_HOIST_MASK & 4) && HW == 112 && POOL) || ((LRPXH_HOIST_MASK & 8) && HW == 224 && POOL));
-#ifndef LRPXH_APIPE_MIN_HW
-#define LRPXH_APIPE_MIN_HW 14
-#endif
-#ifndef LRPXB6_APIPE
-#define LRPXB6_APIPE 1
-#endif
-    constexpr bool APIPE = B6 ? (LRPXB6_APIPE != 0) : ((HW >= LRPXH_APIPE_MIN_HW) && !F8);
-    // X6: the cross products as block-scaled fp6.  LDS pixel: 16 fp16 hi (32 B) | 32 fp6 e2m3 = x_0..x_15, then (x_c - hi_c) * 2^11,
+    // staging descriptors stay in registers (see item()) in the 56x56 non-pooled kernels (measured with the row-wise item layout: 56x56
+    // F8 kernel 2.33 -> 2.12 ms per launch)
+    constexpr bool HOIST = AL && HW == 56 && !POOL;
+    // F8: the cross products as block-scaled fp6.  LDS pixel: 16 fp16 hi (32 B) | 32 fp6 e2m3 = x_0..x_15, then (x_c - hi_c) * 2^11,
     // c = 0..15, all divided by the slice's block scale 2^s (24 B) | E8M0 byte s - 11 + 127 (dword at byte 60; byte 56 stays clear so that the 8 + 4 byte reads do not fuse into a slower ds_read_b96) | pad.  A staging item is one
     // pixel's whole 16-channel slice (4 float4): the block maximum and v_cvt_scalef32_pk32_fp6_f16 need the 16 values in one lane.
-    constexpr bool X6 = F8 && (LRPXH_XP6 != 0);
     // BLK: the mode-3 relevance kernels (REL_MUL) read S and the multiplicand and write S in the BLOCKED layout (blocked.h) and
     // accumulate channels x pixels (TR: the arguments of every MFMA swapped, weight rows permuted at pack time): see epi_rel_mul_blk.
     // conv1_2 (HW == 224, pooled fp32 input, BLOCKED) keeps the plain accumulators and its NHWC multiplicand / 32-channel-chunk output:
     // its consumer, the first-layer kernel, walks 34-pixel halo rows, and 32-pixel blocks cost it 1.4x the lines (0.98 -> 1.42 ms)
     // for the 3 % the transposed epilogue gave conv1_2.
-    constexpr bool BLK = X6 && (EPI == EPI_REL_MUL);
+    constexpr bool BLK = F8 && (EPI == EPI_REL_MUL);
     constexpr bool TR = BLK && (HW != 224);
-    constexpr int NV = X6 ? 4 : 1;                     // float4 loads per staging item
-#ifndef LRPXH_X6_READ
-#define LRPXH_X6_READ 1
-#endif
-    // fp6 operands from LDS as two conflict-free 16-byte reads (else 16 + 8 + 4 bytes: 2- and 4-way bank conflicts over pixels 80 bytes apart)
-    constexpr bool X6RD = X6 && (EPI == EPI_REL_MUL) && (LRPXH_X6_READ != 0) && !(HW == 112 && MT == 2);      // (measured on the relevance chain only)
+    constexpr int NV = F8 ? 4 : 1;                     // float4 loads per staging item
+    // fp6 operands from LDS as two conflict-free 16-byte reads (else 16 + 8 + 4 bytes: 2- and 4-way bank conflicts over pixels 80 bytes
+    // apart); measured on the relevance chain only
+    constexpr bool X6RD = BLK && !(HW == 112 && MT == 2);
     extern __shared__ __attribute__((aligned(16))) char ldsb[];
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / NWN, wn = wave % NWN;
-#ifdef LRPXB6_PRIO
-    // (experiment, round 6) the two workgroups of a CU tend to phase-lock - the one that is alone in its matrix phase runs at twice the
-    // speed and catches up with the other's barrier - so that both stage at the same time and the matrix pipe idles (busy 0.79).  A STATIC
-    // asymmetry per SIMD: the wave in an odd hardware slot issues with priority, the other fills the gaps.
-    if constexpr (B6) {
-        const unsigned hwid = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (3 << 11));      // HW_REG_HW_ID, WAVE_ID[3:0]
-        if (hwid & 1u) __builtin_amdgcn_s_setprio(LRPXB6_PRIO); else __builtin_amdgcn_s_setprio(0);
-    }
-#endif
     // (the body stays in the __global__ function: as an inlined device function taking the argument struct by value it spilled 12 - 25
     // registers in every instantiation - the struct no longer lived in the kernel-argument segment - and ran 6 - 8 % slower)
     const int bid = blockIdx.x;
@@ -658,21 +571,13 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
     // Workgroup ids go round-robin over the 8 XCDs (each with its own L2): XCD x walks a CONTIGUOUS range of tiles, so the
     // halo rows that neighbouring tiles share and the multiplicand tiles of an image's words are re-read from one L2
     // (round-robin tiles, mtile = (idx / n_blocks) * 8 + xcd: 28x28 layers +6 %, conv1_2 +4 %, chain 18.4 vs 18.1 ms)
-#ifndef LRPXH_XCD_BLOCKED
-#define LRPXH_XCD_BLOCKED 1
-#endif
-    int mtile = (idx / n_blocks) * 8 + xcd;
-    if constexpr (LRPXH_XCD_BLOCKED != 0) {
-        // balanced ranges: XCD x owns tiles [x * m / 8, (x + 1) * m / 8) (small grids - the forward trace - stay spread)
-        const int t0 = (int)(((long)xcd * m_tiles) >> 3), t1 = (int)(((long)(xcd + 1) * m_tiles) >> 3);
-        mtile = t0 + idx / n_blocks;
-        if (mtile >= t1 && !(AL && a.tile_group > 1)) return;       // (grouped order: decided below)
-    }
+    // balanced ranges: XCD x owns tiles [x * m / 8, (x + 1) * m / 8) (small grids - the forward trace - stay spread)
+    const int tpos = idx / n_blocks;                            // position in this XCD's sequence
+    const int t0 = (int)(((long)xcd * m_tiles) >> 3), t1 = (int)(((long)(xcd + 1) * m_tiles) >> 3);
+    int mtile = t0 + tpos;
+    if (mtile >= t1 && !(AL && a.tile_group > 1)) return;       // (grouped order: decided below)
     const int nblk = idx % n_blocks;
-#ifndef LRPXH_TILE_GROUP
-#define LRPXH_TILE_GROUP 1
-#endif
-    if constexpr (AL && (LRPXH_TILE_GROUP != 0)) {
+    if constexpr (AL) {
         // a.tile_group maps per image: the tiles (image row block r) of the words w of one image run back to back on ONE
         // XCD, so the image's multiplicand tile stays in that L2 for all of them instead of being fetched from HBM once
         // per word; an XCD walks a contiguous range of (image, row block) groups - consecutive row blocks of an image
@@ -680,13 +585,10 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
             constexpr int TPM = H / C::R;                          // tiles per map
             const int q = idx / n_blocks;                          // position in this XCD's sequence
             const int gl = q / a.tile_group, w = q - gl * a.tile_group;
-            int G = gl * 8 + xcd;                                  // (image, row block) group
             const int n_groups = (a.n_maps / a.tile_group) * TPM;
-            if constexpr (LRPXH_XCD_BLOCKED != 0) {
-                const int g0x = (int)(((long)xcd * n_groups) >> 3), g1x = (int)(((long)(xcd + 1) * n_groups) >> 3);
-                G = g0x + gl;
-                if (G >= g1x) return;
-            }
+            const int g0x = (int)(((long)xcd * n_groups) >> 3), g1x = (int)(((long)(xcd + 1) * n_groups) >> 3);
+            const int G = g0x + gl;                                // (image, row block) group
+            if (G >= g1x) return;
             const int i = G / TPM, r = G - i * TPM;
             mtile = (i * a.tile_group + w) * TPM + r;
             if (G >= n_groups) return;
@@ -730,8 +632,8 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
             const int n0 = (int)(g / (unsigned)HW), nmax_ = a.n_maps - 1;
             const int na = min(n0, nmax_), nb = min(n0 + 1, nmax_);
             if constexpr (!B6) {
-                tile_tab[tid * 4 + 0] = __builtin_bit_cast(int, exp2i(-split_scale_exp<F8>(in_amax[na])));
-                tile_tab[tid * 4 + 1] = __builtin_bit_cast(int, exp2i(-split_scale_exp<F8>(in_amax[nb])));
+                tile_tab[tid * 4 + 0] = __builtin_bit_cast(int, exp2i(-f16_scale_exp(in_amax[na])));
+                tile_tab[tid * 4 + 1] = __builtin_bit_cast(int, exp2i(-f16_scale_exp(in_amax[nb])));
             }
             tile_tab[tid * 4 + 2] = a.map2img ? a.map2img[na] : n0;
             tile_tab[tid * 4 + 3] = a.map2img ? a.map2img[nb] : n0 + 1;
@@ -762,20 +664,17 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
     // (lrp_modules.py:182-195) is applied while staging - pixel (y, x) receives S_lo[y/2][x/2] if it is the winner of
     // its window, else 0 - so the 4x larger unpooled tensor (75 % zeros) never exists in HBM.  The global pixel is
     // then the LOW-resolution one, the window position rides in bits 26-27 of the LDS offset.
-    constexpr int SEG = X6 ? 1 : KC / 4;
+    constexpr int SEG = F8 ? 1 : KC / 4;
     constexpr int NITEM = C::NSLOT * W * SEG;
     // map-aligned tiles: staging items are laid out ROW-WISE over the threads - item slot u of thread tid is LDS row
     // u*RPS + tid/RI (narrow maps: RPS whole rows per slot) or row u/SPR, part u%SPR (wide maps: SPR slots per row) - so
     // that row, pixel and segment need no division, the row validity is wave-uniform and the descriptors are not worth
     // keeping in registers
-#ifndef LRPXH_ROWMAP
-#define LRPXH_ROWMAP 1
-#endif
     constexpr int RI = W * SEG;                                   // items per LDS row
     // narrow maps under a wide workgroup (512 threads, 224 items per row): RPS = 2 rows per slot, 256 threads each
     constexpr int RPS = (RI <= NT / 2) ? 2 : 1;
     constexpr int TPR = NT / RPS;                                 // threads per row of a slot
-    constexpr bool ROWMAP = AL && (LRPXH_ROWMAP != 0) && (RI <= NT ? (RI > NT / 2 || (RPS == 2 && RI > NT / 4)) : true);
+    constexpr bool ROWMAP = AL && (RI <= NT ? (RI > NT / 2 || (RPS == 2 && RI > NT / 4)) : true);
     constexpr int SPR = (RI + NT - 1) / NT;                       // slots per row (1 when a row fits the workgroup)
     constexpr int U = ROWMAP ? ((C::NSLOT + RPS - 1) / RPS) * SPR : (NITEM + NT - 1) / NT;
     constexpr int UR = AL ? 1 : U;
@@ -787,7 +686,7 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
     long img_al = 0;
     if constexpr (AL) {
         ssc[0] = 1.f;
-        if constexpr (!B6) ssc[0] = exp2i(split_scale_exp<F8>(in_amax[min(n_al, a.n_maps - 1)]));
+        if constexpr (!B6) ssc[0] = exp2i(f16_scale_exp(in_amax[min(n_al, a.n_maps - 1)]));
         if constexpr (POOL) img_al = a.map2img ? a.map2img[min(n_al, a.n_maps - 1)] : n_al;
     } else {
 #pragma unroll
@@ -805,7 +704,7 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
                 if ((v_ >= 0) && (y < H) && (n < a.n_maps)) {
                     sdst[u] = (s * PITCH + (px + 1) * PSTRIDE + seg * 8) | (seg << 28);
                     sgp[u] = (int)((n * H + y - (g0 - 1)) * W + px);     // relative to the row above the tile's first
-                    if constexpr (!B6) ssc[u] = exp2i(split_scale_exp<F8>(in_amax[n]));
+                    if constexpr (!B6) ssc[u] = exp2i(f16_scale_exp(in_amax[n]));
                     if constexpr (POOL) {
                         const int lo = (y >> 1) * WO + (px >> 1);
                         const long img = a.map2img ? a.map2img[n] : n;
@@ -904,10 +803,9 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
     constexpr int NITEM_LO = RL * WO * SEG;
     // row-wise item layout as above: RPSL pooled rows per slot (narrow) or SPRL slots per pooled row (wide)
     constexpr int RIL = WO * SEG;
-    constexpr bool ROWMAP_LO = LOSTAGE && AL && (LRPXH_ROWMAP != 0);
     constexpr int RPSL = RIL <= NT ? NT / RIL : 1;
     constexpr int SPRL = (RIL + NT - 1) / NT;
-    constexpr int UL = !LOSTAGE ? 1 : (ROWMAP_LO ? (RIL <= NT ? (RL + RPSL - 1) / RPSL : RL * SPRL) : (NITEM_LO + NT - 1) / NT);
+    constexpr int UL = !LOSTAGE ? 1 : (AL ? (RIL <= NT ? (RL + RPSL - 1) / RPSL : RL * SPRL) : (NITEM_LO + NT - 1) / NT);
     const int lo_q = tid / RIL, lo_r = tid - lo_q * RIL;          // (row within the slot, item within the row) of this thread
     constexpr int ULR = (LOSTAGE && !AL) ? UL : 1;
     int ldst[ULR], lgp[ULR], lam[ULR];
@@ -932,7 +830,7 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
                     ldst[u] = ((s0 < 0 ? 0 : s0) * PITCH + (2 * pxl + 1) * PSTRIDE + seg * 8) | (seg << 28) | (rowmask << 26);
                     lgp[u] = (int)(n * (HO * WO) + lo);
                     lam[u] = (int)((img * (HO * WO) + lo) * a.cin);
-                    if constexpr (!B6) lsc[u] = exp2i(split_scale_exp<F8>(in_amax[n]));
+                    if constexpr (!B6) lsc[u] = exp2i(f16_scale_exp(in_amax[n]));
                 }
             }
         }
@@ -943,16 +841,10 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
             if constexpr (!HOIST) asm volatile("" : "+v"(it));
             int sl, rem;
             bool in_row;
-            if constexpr (ROWMAP_LO) {
-                int q_ = lo_q, r_ = lo_r;
-                if constexpr (!HOIST) asm volatile("" : "+v"(q_), "+v"(r_));
-                if constexpr (RIL <= NT) { sl = u * RPSL + q_; rem = r_; in_row = (q_ < RPSL) && (sl < RL); }
-                else { sl = u / SPRL; rem = it - (u / SPRL) * SPRL * NT; in_row = rem < RIL; }
-            } else {
-                sl = it / (WO * SEG);
-                rem = it - sl * (WO * SEG);
-                in_row = it < NITEM_LO;
-            }
+            int q_ = lo_q, r_ = lo_r;
+            if constexpr (!HOIST) asm volatile("" : "+v"(q_), "+v"(r_));
+            if constexpr (RIL <= NT) { sl = u * RPSL + q_; rem = r_; in_row = (q_ < RPSL) && (sl < RL); }
+            else { sl = u / SPRL; rem = it - (u / SPRL) * SPRL * NT; in_row = rem < RIL; }
             const int pxl = rem / SEG, seg = rem - pxl * SEG;
             const int ylo = (y_al >> 1) - 1 + sl;
             const bool ok = in_row && (ylo >= 0) && (ylo < HO);
@@ -989,8 +881,8 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
     }
     constexpr int VSTEP = BLK ? 32 : 1;       // float4 units between the four parts of a staging item's slice
     f32x4 sv[LOSTAGE ? UL : U][NV];
-    unsigned amv[(POOL && !X6) ? (LOSTAGE ? UL : U) : 1];
-    u32x4_ amv4[(POOL && X6) ? (LOSTAGE ? UL : U) : 1];      // X6: the 16 winner bytes of the item's slice
+    unsigned amv[(POOL && !F8) ? (LOSTAGE ? UL : U) : 1];
+    u32x4_ amv4[(POOL && F8) ? (LOSTAGE ? UL : U) : 1];      // F8: the 16 winner bytes of the item's slice
 #define LRPXH_ISSUE_LO(CHUNK) _Pragma("unroll") for (int u = 0; u < UL; ++u) LRPXH_ISSUE_LO1(u, CHUNK)
 #define LRPXH_COMMIT_LO(BUFIDX) _Pragma("unroll") for (int u = 0; u < UL; ++u) LRPXH_COMMIT_LO1(u, BUFIDX)
 #define LRPXH_ISSUE_LO1(u, CHUNK)                                                                            \
@@ -1014,7 +906,7 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
             if constexpr (BLK) sp_ = in_tile + (CHUNK) * in_chunk_step + blk_pix_off32((int)g_);    \
         }                                                                                                    \
         _Pragma("unroll") for (int v_ = 0; v_ < NV; ++v_) sv[u][v_] = reinterpret_cast<const f32x4*>(sp_)[v_ * VSTEP]; \
-        if constexpr (X6) amv4[u] = *reinterpret_cast<const u32x4_*>(ap_);                                   \
+        if constexpr (F8) amv4[u] = *reinterpret_cast<const u32x4_*>(ap_);                                   \
         else amv[u] = *reinterpret_cast<const unsigned*>(ap_);                                               \
     }
 // The four window positions of an item differ only in the lanes that are kept: byte masks from one SWAR compare of the
@@ -1027,20 +919,12 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
         int dst_, gp_, amo_, rm_;                                                                            \
         float sc_;                                                                                           \
         item_lo(u, dst_, gp_, amo_, rm_, sc_);                                                               \
-        if constexpr (X6) { LRPXH_COMMIT_LO1_X6(u, BUFIDX) } else if constexpr (B6) { LRPXH_COMMIT_LO1_B6(u, BUFIDX) } else { \
+        if constexpr (F8) { LRPXH_COMMIT_LO1_X6(u, BUFIDX) } else if constexpr (B6) { LRPXH_COMMIT_LO1_B6(u, BUFIDX) } else { \
         const f32x2_ xa_ = f32x2_{sv[u][0][0], sv[u][0][1]} * f32x2_{sc_, sc_}, xb_ = f32x2_{sv[u][0][2], sv[u][0][3]} * f32x2_{sc_, sc_}; \
         unsigned hw0_, hw1_, lw0_, lw1_;                                                                     \
         f32x2_ ha_, hb_;                                                                                     \
         split2_pk(xa_, hw0_, lw0_, ha_); split2_pk(xb_, hw1_, lw1_, hb_);                                    \
-        unsigned w8_ = 0, wl8_ = 0;                                                                          \
-        if constexpr (F8) {                                                                                  \
-            const f32x2_ ya_ = xa_ * f32x2_{0.0625f, 0.0625f}, yb_ = xb_ * f32x2_{0.0625f, 0.0625f};         \
-            const f32x2_ ra_ = (xa_ - ha_) * f32x2_{16.f, 16.f}, rb_ = (xb_ - hb_) * f32x2_{16.f, 16.f};     \
-            w8_ = pack_fp8x4(ya_[0], ya_[1], yb_[0], yb_[1]);                                                \
-            wl8_ = pack_fp8x4(ra_[0], ra_[1], rb_[0], rb_[1]);                                               \
-        }                                                                                                    \
         const int o0_ = (BUFIDX) * BUFB + (dst_ & 0x03ffffff);                                               \
-        const int sg4_ = ((dst_ >> 28) & 3) * 4;                                                             \
         const int rb0_ = ((rm_ & 1) && !(LRPXH_EXP & 4)) ? o0_ : POOL_SCRATCH;   /* window row dy = 0 */    \
         const int rb1_ = ((rm_ & 2) && !(LRPXH_EXP & 4)) ? o0_ + ((rm_ & 1) ? PITCH : 0) : POOL_SCRATCH;     \
         _Pragma("unroll") for (int pos = 0; pos < 4; ++pos) {                                                \
@@ -1051,12 +935,7 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
             const unsigned m23_ = __builtin_amdgcn_perm(bm_, bm_, 0x03030202u);                              \
             char* d_ = ldsb + ((pos >> 1) ? rb1_ : rb0_) + (pos & 1) * PSTRIDE;                              \
             *reinterpret_cast<u32x2_*>(d_) = u32x2_{hw0_ & m01_, hw1_ & m23_};                               \
-            if constexpr (F8) {                                                                              \
-                *reinterpret_cast<unsigned*>(d_ - sg4_ + 32) = w8_ & bm_;                                    \
-                *reinterpret_cast<unsigned*>(d_ - sg4_ + 48) = wl8_ & bm_;                                   \
-            } else {                                                                                         \
-                *reinterpret_cast<u32x2_*>(d_ + 32) = u32x2_{lw0_ & m01_, lw1_ & m23_};                      \
-            }                                                                                                \
+            *reinterpret_cast<u32x2_*>(d_ + 32) = u32x2_{lw0_ & m01_, lw1_ & m23_};                          \
         }                                                                                                    \
         }                                                                                                    \
     }
@@ -1084,19 +963,17 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
 // there are zeroed on the fp32 values (bit masks replicated from the SWAR compare of the 16 winner bytes), then hi = cvt_pk of the
 // masked values and one fp6 conversion with the slice's common block scale (the maximum over all 16 channels: a position that
 // keeps only small entries is rounded against the pooled pixel's largest one - the same absolute error as in a layer without pool)
-#ifndef LRPXH_LO_SKIP
-#define LRPXH_LO_SKIP 1       // wave-uniform skips in the pooled commit: a wave none of whose lanes has the window row does not compute it
-#endif
+// Wave-uniform skips: a wave none of whose lanes has the window row does not compute it.
 #define LRPXH_COMMIT_LO1_X6(u, BUFIDX)                                                                       \
-    if (!LRPXH_LO_SKIP || __builtin_amdgcn_ballot_w64(rm_ != 0) != 0) {                                      \
+    if (__builtin_amdgcn_ballot_w64(rm_ != 0) != 0) {                                                        \
         unsigned hwu_[8], rwu_[8], sb_;                                                                      \
         float bs_;                                                                                           \
         x6_split(sv[u], sc_, hwu_, rwu_, bs_, sb_);                                                          \
         const int o0_ = (BUFIDX) * BUFB + (dst_ & 0x03ffffff);                                               \
         const int rb0_ = ((rm_ & 1) && !(LRPXH_EXP & 4)) ? o0_ : POOL_SCRATCH;   /* window row dy = 0 */    \
         const int rb1_ = ((rm_ & 2) && !(LRPXH_EXP & 4)) ? o0_ + ((rm_ & 1) ? PITCH : 0) : POOL_SCRATCH;     \
-        const bool need0_ = !LRPXH_LO_SKIP || __builtin_amdgcn_ballot_w64((rm_ & 1) != 0) != 0;              \
-        const bool need1_ = !LRPXH_LO_SKIP || __builtin_amdgcn_ballot_w64((rm_ & 2) != 0) != 0;              \
+        const bool need0_ = __builtin_amdgcn_ballot_w64((rm_ & 1) != 0) != 0;                                \
+        const bool need1_ = __builtin_amdgcn_ballot_w64((rm_ & 2) != 0) != 0;                                \
         _Pragma("unroll") for (int pos = 0; pos < 4; ++pos) if ((pos >> 1) ? need1_ : need0_) {              \
             unsigned hm_[8], rm2_[8];                                                                        \
             _Pragma("unroll") for (int q_ = 0; q_ < 4; ++q_) {                                               \
@@ -1147,8 +1024,8 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
         item(u, dst_, gp_, amo_);                                                                            \
         /* (an item with nothing to write converts whatever its registers hold into the scratch bytes) */    \
         char* d_ = ldsb + ((dst_ >= 0 && !(LRPXH_EXP & 4)) ? (BUFIDX) * BUFB + (dst_ & 0x03ffffff) : STAGE_SCRATCH); \
-        if constexpr (X6) {                                                                                  \
-            if (!LRPXH_LO_SKIP || __builtin_amdgcn_ballot_w64(dst_ >= 0) != 0) {                             \
+        if constexpr (F8) {                                                                                  \
+            if (__builtin_amdgcn_ballot_w64(dst_ >= 0) != 0) {                                               \
             unsigned hwu_[8], rwu_[8], sb_;                                                                  \
             float bs_;                                                                                       \
             x6_split(sv[u], ssc[AL ? 0 : u], hwu_, rwu_, bs_, sb_);                                          \
@@ -1171,15 +1048,7 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
         f32x2_ ha_, hb_;                                                                                     \
         split2_pk(xa_, hw0_, lw0_, ha_); split2_pk(xb_, hw1_, lw1_, hb_);                                    \
         *reinterpret_cast<u32x2_*>(d_) = u32x2_{hw0_, hw1_};                                                 \
-        if constexpr (F8) {                                                                                  \
-            const int sg4_ = ((dst_ >> 28) & 3) * 4;                                                         \
-            const f32x2_ ya_ = xa_ * f32x2_{0.0625f, 0.0625f}, yb_ = xb_ * f32x2_{0.0625f, 0.0625f};         \
-            const f32x2_ ra_ = (xa_ - ha_) * f32x2_{16.f, 16.f}, rb_ = (xb_ - hb_) * f32x2_{16.f, 16.f};     \
-            *reinterpret_cast<unsigned*>(d_ - sg4_ + 32) = pack_fp8x4(ya_[0], ya_[1], yb_[0], yb_[1]);       \
-            *reinterpret_cast<unsigned*>(d_ - sg4_ + 48) = pack_fp8x4(ra_[0], ra_[1], rb_[0], rb_[1]);       \
-        } else {                                                                                             \
-            *reinterpret_cast<u32x2_*>(d_ + 32) = u32x2_{lw0_, lw1_};                                        \
-        }                                                                                                    \
+        *reinterpret_cast<u32x2_*>(d_ + 32) = u32x2_{lw0_, lw1_};                                            \
         }                                                                                                    \
     }
 
@@ -1193,19 +1062,12 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
     // suggests); grouping odd / even waves instead is 1 % slower than no skew: w and w + 4 are the SIMD partners.
     // Buffers: chunk c is read from buffer c & 1 between barrier c - 1 and barrier c by everyone; writes to it happen
     // after barrier c - 2 (group 1, chunk c: right behind that barrier; group 0: at the end of interval c - 1).
-#ifndef LRPXH_STAGGER
-#define LRPXH_STAGGER 1
-#endif
 #ifndef LRPXH_EXP
 #define LRPXH_EXP 0       // timing experiments (wrong results): 1 = no staging commits in the K loop, 2 = no staging loads, 16 = no A-operand reads,
                           // 32 = no epilogue, 64 = no barrier in the (double-buffered) K loop
 #endif
-    constexpr bool STAG = DB && (LRPXH_STAGGER != 0) && (MT * NWN >= 8);
-#ifdef LRPXH_ISSUE_LATE
-    constexpr bool ISSUE_LATE = LRPXH_ISSUE_LATE != 0;
-#else
-    constexpr bool ISSUE_LATE = (HW == 112 && MT == 2);
-#endif
+    constexpr bool STAG = DB && (MT * NWN >= 8);
+    constexpr bool ISSUE_LATE = (HW == 112 && MT == 2);       // (see PRECISE in the K loop)
     const int grp = STAG ? (wave >= MT * NWN / 2 ? 1 : 0) : 0;     // wave-uniform (waves w and w + 4 share a SIMD)
     if constexpr (!(LRPXH_EXP & 8)) { if constexpr (LOSTAGE) { LRPXH_ISSUE_LO(0) } else { LRPXH_ISSUE(0) } }
     else {      // (EXP 8: what the exposed first load of a tile costs - zeros instead)
@@ -1213,8 +1075,8 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
         for (int u = 0; u < (LOSTAGE ? UL : U); ++u) {
 #pragma unroll
             for (int v_ = 0; v_ < NV; ++v_) sv[u][v_] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if constexpr (POOL && !X6) amv[u] = 0;
-            if constexpr (POOL && X6) amv4[u] = u32x4_{0, 0, 0, 0};
+            if constexpr (POOL && !F8) amv[u] = 0;
+            if constexpr (POOL && F8) amv4[u] = u32x4_{0, 0, 0, 0};
         }
     }
     for (int i = tid; i < NBUF * BUFB / 16; i += NT) reinterpret_cast<u32x4_*>(ldsb)[i] = u32x4_{0, 0, 0, 0};
@@ -1230,49 +1092,32 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
         for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
 
     // B fragments: per k-step two planes (hi, lo) of 64 lanes x 16 B, one contiguous stream per channel block
-#ifdef LRPXH_NBQ
-    constexpr int NBQ = LRPXH_NBQ;
-#else
     // measured (tools/variant_sweep2.sh, chain of 320 maps): depth 2 -> 28.9 ms, 4 -> 26.9, 6 -> 25.9, 8 -> 25.0; the
     // map-straddling tiles (28/14) spill beyond 7
     constexpr int NBQ_H3 = !AL ? 7 : (HW == 224 ? (POOL ? 10 : 5) : (((HW == 112 && NWN == 2) || (HOIST && !POOL)) ? 8 : 9));
     // B6: three planes per entry (12 registers)
     // (measured, same-box A/B of builds: the map-aligned pooled-input kernels have the registers for a deeper queue - their staging items
     // are a quarter as many - conv1_2 5.16 -> 5.04 ms, conv2_2 4.41 -> 4.25; one entry more spills in every other instantiation)
-#ifndef LRPXB6_NBQ
-#define LRPXB6_NBQ ((POOL && AL) ? (HW == 112 ? 7 : 6) : ((HW <= 56) ? 5 : 4))
-#endif
-    constexpr int NBQ = B6 ? LRPXB6_NBQ : NBQ_H3;
-#endif
+    constexpr int NBQ_B6 = (POOL && AL) ? (HW == 112 ? 7 : 6) : ((HW <= 56) ? 5 : 4);
+    constexpr int NBQ = B6 ? NBQ_B6 : NBQ_H3;
     float inv_w = 1.f;
     if constexpr (!B6) inv_w = a.wp[0];
-    // F8: one queue entry per tap ROW g = 7 planes of 64 lanes x 16 B: fp16 hi of dx = 0,1,2 | the B operands of fp8
-    // MFMAs 2g and 2g+1 (2 planes each = the lane's two slots x 16 channels; row 2 has MFMA 4 only)
+    // F8: one queue entry per tap ROW g = 7 planes of 64 lanes x 16 B: fp16 hi of dx = 0,1,2 | the B operands of fp6
+    // MFMAs 2g and 2g+1 (2 planes each; row 2 has MFMA 4 only)
     constexpr int BP = F8 ? 7 : (B6 ? 3 : 2);       // planes per queue entry
     constexpr int BSTEPS = F8 ? 3 : TAPS;           // queue entries per K-chunk
-    // measured (tools/variant_sweep3.sh, chain of 320 maps): 2 entries 24.1 ms, 3 entries 25.1 (spills), 4: 30.1; the
-    // pooled-input 112 / 56 kernels have the registers for a third entry (2.39 -> 2.27 ms, 1.96 -> 1.89 ms)
-#ifdef LRPXH_NBQ8
-    constexpr int NQ = F8 ? LRPXH_NBQ8 : NBQ;
-#else
-#ifndef LRPXH_NQ_112P
-#define LRPXH_NQ_112P 3
-#endif
-    // X6 (a staging item holds 16 floats): a third entry spills everywhere
-    #ifndef LRPXH_X6_NQ3
-#define LRPXH_X6_NQ3 0
-#endif
-    constexpr int NQ = F8 ? (((!X6 || (LRPXH_X6_NQ3 && HW == 112 && MT * NWN == 4)) && POOL && AL && HW <= 112) ? ((HW == 112 && MT * NWN == 4) ? LRPXH_NQ_112P : 3) : 2) : NBQ;
-#endif
+    // measured (tools/variant_sweep3.sh, chain of 320 maps): 2 entries 24.1 ms, 3 entries 25.1 (spills), 4: 30.1; with fp6
+    // staging items of 16 floats a third entry spills everywhere
+    constexpr int NQ = F8 ? 2 : NBQ;
     // (a wave without a channel block of its own - n_oc not a multiple of the workgroup's channels - multiplies the last
     // valid block again and drops the result: one code path, see PRECISE below)
     const int ocb_w = wave_active ? ocb : (a.n_oc - 1) / 32;
     const u32x4_* wp = reinterpret_cast<const u32x4_*>(a.wp + (B6 ? 0 : F16X3_HEADER_FLOATS)) +
                        ((long)ocb_w * nchunk_all + c_begin) * (BSTEPS * BP * 64) + lane;
     const int last_step = nchunk * BSTEPS - 1;
-    // plane p of queue entry `e`; X6: planes 4 and 6 hold 8 bytes of fp6 + the block-scale dword - 12 bytes, loaded as such
+    // plane p of queue entry `e`; F8: planes 4 and 6 hold 8 bytes of fp6 + the block-scale dword - 12 bytes, loaded as such
     auto ldb = [&](const long e, const int p) -> u32x4_ {
-        if constexpr (X6) {
+        if constexpr (F8) {
             if (p == 4 || p == 6) {
                 const u32x3_ t = *reinterpret_cast<const u32x3_*>(wp + (e * BP + p) * 64);
                 return u32x4_{t[0], t[1], t[2], 0u};
@@ -1289,12 +1134,7 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
     for (int i = 0; i < NQ - 1; ++i)
 #pragma unroll
         for (int p = 0; p < BP; ++p) bq[i][p] = ldb(min(i, last_step), p);
-    // F8: LDS byte offsets of the lane's two fp8 tap slots of a tap row (dx = 0 / 1 for lanes 0-31; dx = 2 / 2 for lanes
-    // 32-63, whose second slot carries zero weights)
-    // F8: lanes 0-31 read the fp8 plane of x - hi (byte 48 of the pixel), lanes 32-63 that of x (byte 32; abase[] already
-    // carries + 16 for them)
-    const int c8 = lh ? 16 : 48;
-    // X6: the operand of fp6 MFMA mm = 0..4 is the 32 bytes at byte 32 of ONE pixel per lane: tap 2mm for lanes 0-31, tap 2mm + 1
+    // F8: the operand of fp6 MFMA mm = 0..4 is the 32 bytes at byte 32 of ONE pixel per lane: tap 2mm for lanes 0-31, tap 2mm + 1
     // for lanes 32-63 (mm = 4: tap 8 again, against zero weights) - the lane halves differ by one pixel (mm = 0, 2, 3), by a row
     // less two pixels (mm = 1) or not at all (mm = 4); abase[] carries + 16 for lanes 32-63
     const int e6a = 32 - 16 * lh + lh * PSTRIDE, e6b = 32 - 16 * lh + lh * (PITCH - 2 * PSTRIDE), e6c = 32 - 16 * lh;
@@ -1304,10 +1144,7 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
     }
 
     LRPXH_T(t_loop);
-#ifndef LRPXH_CHUNK_UNROLL
-#define LRPXH_CHUNK_UNROLL 1
-#endif
-#pragma unroll LRPXH_CHUNK_UNROLL
+#pragma unroll 1
     for (int chunk = 0; chunk < nchunk; ++chunk) {
         const bool more = chunk + 1 < nchunk;
         LRPXH_REFRESH
@@ -1337,91 +1174,53 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
 #ifdef LRPX_STAMP
             unsigned long long tprev = tb;
 #endif
-            // APIPE (wide maps with few K-chunks: the partner wave of the SIMD is mostly outside its MFMA phase, so this
-            // wave's LDS latency is not covered by the partner's MFMAs): A fragments are read one accumulator tile ahead
+            // In every path the A fragments are read from LDS ahead of their MFMAs (the partner wave of the SIMD is mostly outside
+            // its MFMA phase, so this wave's LDS latency is not covered by the partner's MFMAs)
             if constexpr (F8) {
-#ifndef LRPXH_F8_SGB
-#define LRPXH_F8_SGB 0
-#endif
-                // (experiment) software pipeline by scheduling groups: the LDS reads of accumulator tile t+1 are placed
-                // before the MFMAs of tile t
-                if constexpr (LRPXH_F8_SGB != 0) __builtin_amdgcn_sched_group_barrier(0x100, 7, 0);
-#ifndef LRPXH_F8_PIPE
-#define LRPXH_F8_PIPE 3
-#endif
-                                // 4-wave workgroups (twice the staging registers per thread): depth 1 pays on the pooled-input 224x224 kernel
-                // only (conv1_2 2.94 -> 2.83 ms with 5 spilled registers; conv2_1 +15 %, conv2_2 +2 %, conv3_1 +-0 with depth 1
-                // or 2 and their 10-25 spills - same-box A/B)
-#ifndef LRPXH_F8_PIPE_TALL
-#define LRPXH_F8_PIPE_TALL 1      // 8-wave workgroups with MT >= 2 (tall tiles of the <= 128-channel layers)
-#endif
-#ifdef LRPXH_F8_PIPE4
-                constexpr int PIPE_D = (MT * NWN >= 8) ? (MT >= 2 ? LRPXH_F8_PIPE_TALL : LRPXH_F8_PIPE) : LRPXH_F8_PIPE4;
-#else
-#ifndef LRPXH_PIPE_4W
-#define LRPXH_PIPE_4W 0        // the other 4-wave kernels
-#endif
-#ifndef LRPXH_PIPE_112P
-#define LRPXH_PIPE_112P 1      // conv2_2: 2.26 -> 2.12 ms (depth 3 with a B queue of 2: the same)
-#endif
-#ifndef LRPXH_F8_PIPE_POOLS
-#define LRPXH_F8_PIPE_POOLS LRPXH_F8_PIPE      // the map-straddling pooled-input 8-wave kernel (conv4_3): the only one that spills
-#endif
-#ifndef LRPXH_PIPE_4W_X6
-#define LRPXH_PIPE_4W_X6 1     // fp6 build: the explicit operand ring keeps fewer temporaries alive than the compiler's own schedule (35 -> 1..4 spills)
-#endif
-                constexpr int PIPE_D = (MT * NWN >= 8) ? (MT >= 2 ? LRPXH_F8_PIPE_TALL : ((POOL && !AL) ? LRPXH_F8_PIPE_POOLS : LRPXH_F8_PIPE))
-                                                       : ((HW == 224 && POOL) ? 1 : ((HW == 112 && POOL) ? LRPXH_PIPE_112P : (X6 ? LRPXH_PIPE_4W_X6 : LRPXH_PIPE_4W)));
-#endif
-                if constexpr (PIPE_D != 0) {
-                // Operand pipeline of depth D = LRPXH_F8_PIPE.  Left to itself the compiler (at 240+ VGPRs) keeps ONE set of
+                // Operand pipeline of depth D.  Left to itself the compiler (at 240+ VGPRs) keeps ONE set of
                 // A-fragment registers and emits read -> s_waitcnt lgkmcnt(0) -> MFMA for every MFMA: each one waits for its
                 // own LDS round trip and only the partner wave fills the pipe (busy 79 % of the phase).  Here the 98 MFMAs
                 // of a K-chunk are one sequence of ops k = (tap row g, tile j, kind m); the A operand of op k + D is read
                 // before MFMA k is issued (D operand sets in a ring); `sched_barrier(0)` fences keep the compiler's scheduler
                 // from sinking the reads back to their uses (scheduling groups alone did not hold the order).  Measured
                 // (chain of 320 maps): 56x56 -10 %, 28x28 -7 %, 14x14 -9 % per launch at D = 2 (D = 3: the same).
-                constexpr int D = PIPE_D != 0 ? PIPE_D : 1;
+                // Depth 3 in the 8-wave kernels with one pixel sub-tile (the map-straddling pooled-input one, conv4_3, is the only one
+                // that spills), depth 1 in the tall 8-wave tiles (MT >= 2) of the <= 128-channel layers and in the 4-wave workgroups
+                // (twice the staging registers per thread): conv1_2 2.94 -> 2.83 ms with 5 spilled registers, conv2_2 2.26 -> 2.12 ms
+                // (depth 3 with a B queue of 2: the same); in the other 4-wave kernels the explicit ring keeps fewer temporaries alive
+                // than the compiler's own schedule (35 -> 1..4 spills).
+                constexpr int D = (MT * NWN >= 8 && MT < 2) ? 3 : 1;
                 constexpr int TPX[10] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 8};
-                // op k -> (g, j, m): tap rows 0 and 1 have 5 MFMAs per tile (2 fp8 + 3 fp16), row 2 has 4 (1 fp8 + 3 fp16)
+                // op k -> (g, j, m): tap rows 0 and 1 have 5 MFMAs per tile (2 fp6 + 3 fp16), row 2 has 4 (1 fp6 + 3 fp16)
                 auto og = [](const int k) constexpr { return k < 35 ? 0 : (k < 70 ? 1 : 2); };
                 auto oj = [](const int k) constexpr { return k < 70 ? (k % 35) / 5 : (k - 70) / 4; };
-                auto om = [](const int k) constexpr { return k < 70 ? (k % 35) % 5 : ((k - 70) % 4 == 0 ? 0 : (k - 70) % 4 + 1); };   // 0,1: fp8; 2..4: fp16 dx 0..2
+                auto om = [](const int k) constexpr { return k < 70 ? (k % 35) % 5 : ((k - 70) % 4 == 0 ? 0 : (k - 70) % 4 + 1); };   // 0,1: fp6; 2..4: fp16 dx 0..2
                 auto rd = [&](const int k) {
                     const int g = og(k), j = oj(k), m = om(k);
                     if constexpr ((LRPXH_EXP & 16) != 0) return i32x8_{lane, lane + 1, lane + 2, lane + 3, lane, lane, 0x7f, 0};   // (EXP 16: no LDS reads)
-                    if (m < 2) {                                   // fp8 operand: taps 4g + 2m, 4g + 2m + 1
+                    if (m < 2) {                                   // fp6 operand: taps 4g + 2m, 4g + 2m + 1
                         const int t = 4 * g + 2 * m;
-                        if constexpr (X6) {
-                            const char* a6 = abuf + abase[j] + (t == 2 ? e6b : (t == 8 ? e6c : e6a)) + (TPX[t] / 3) * PITCH + (TPX[t] % 3) * PSTRIDE;
-                            // 16 + 8 + 4 bytes: every register a read returns is used (a register that is loaded but dead gets
-                            // re-used by the allocator while the read is in flight, and the wait for that write-after-write
-                            // hazard is a full drain of the counter)
-                            const u32x4_ x0 = *reinterpret_cast<const u32x4_*>(a6);
-#ifndef LRPXH_X6_READ
-#define LRPXH_X6_READ 1
-#endif
-                            if constexpr (X6RD) {
-                                // (round 4: the default except for conv2_1's 4-row 112 x 112 kernel, which spills with the extra live register:
-                                // 1.05 -> 1.19 ms; same-box A/B of the rest: conv4_3 1.68 -> 1.60, conv1_2 2.50 -> 2.44, conv5_x 0.51 -> 0.50, conv2_2
-                                // 1.89 -> 1.87, the others +-0.01: profiles/r04_ab_x6_read.txt)
-                                // two 16-byte reads, conflict-free over consecutive pixels 80 bytes apart; the clear dword
-                                // behind the fields is kept alive past the MFMA by an empty asm (see the MFMA below).  The 8- and 4-byte
-                                // reads of the default hit their banks 2 and 4 times over pixels 80 bytes apart (SQ_LDS_BANK_CONFLICT
-                                // 0.33 of the LDS cycles against 0.03 with fp8) - but the kernels are not bound by the LDS: same-box A/B
-                                // chain 17.33 / 17.27 ms with the conflicts, 17.46 / 17.38 without (the extra live register costs conv2_1
-                                // 12 spilled VGPRs: 1.10 -> 1.26 ms; every other layer +-0.01)
-                                const u32x4_ x1 = *reinterpret_cast<const u32x4_*>(a6 + 16);
-                                return i32x8_{(int)x0[0], (int)x0[1], (int)x0[2], (int)x0[3], (int)x1[0], (int)x1[1], (int)x1[3], (int)x1[2]};
-                            }
-                            const u32x2_ x1 = *reinterpret_cast<const u32x2_*>(a6 + 16);
-                            const unsigned xs = *reinterpret_cast<const unsigned*>(a6 + 28);
-                            return i32x8_{(int)x0[0], (int)x0[1], (int)x0[2], (int)x0[3], (int)x1[0], (int)x1[1], (int)xs, 0};
+                        const char* a6 = abuf + abase[j] + (t == 2 ? e6b : (t == 8 ? e6c : e6a)) + (TPX[t] / 3) * PITCH + (TPX[t] % 3) * PSTRIDE;
+                        const u32x4_ x0 = *reinterpret_cast<const u32x4_*>(a6);
+                        if constexpr (X6RD) {
+                            // (round 4: the default except for conv2_1's 4-row 112 x 112 kernel, which spills with the extra live register:
+                            // 1.05 -> 1.19 ms; same-box A/B of the rest: conv4_3 1.68 -> 1.60, conv1_2 2.50 -> 2.44, conv5_x 0.51 -> 0.50, conv2_2
+                            // 1.89 -> 1.87, the others +-0.01: profiles/r04_ab_x6_read.txt)
+                            // two 16-byte reads, conflict-free over consecutive pixels 80 bytes apart; the clear dword
+                            // behind the fields is kept alive past the MFMA by an empty asm (see the MFMA below).  The 8- and 4-byte
+                            // reads of the other branch hit their banks 2 and 4 times over pixels 80 bytes apart (SQ_LDS_BANK_CONFLICT
+                            // 0.33 of the LDS cycles against 0.03 with fp8) - but the kernels are not bound by the LDS: same-box A/B
+                            // chain 17.33 / 17.27 ms with the conflicts, 17.46 / 17.38 without (the extra live register costs conv2_1
+                            // 12 spilled VGPRs: 1.10 -> 1.26 ms; every other layer +-0.01)
+                            const u32x4_ x1 = *reinterpret_cast<const u32x4_*>(a6 + 16);
+                            return i32x8_{(int)x0[0], (int)x0[1], (int)x0[2], (int)x0[3], (int)x1[0], (int)x1[1], (int)x1[3], (int)x1[2]};
                         }
-                        const char* a8 = abuf + abase[j] + c8;
-                        const u32x4_ x0 = *reinterpret_cast<const u32x4_*>(a8 + (TPX[t] / 3) * PITCH + (TPX[t] % 3) * PSTRIDE);
-                        const u32x4_ x1 = *reinterpret_cast<const u32x4_*>(a8 + (TPX[t + 1] / 3) * PITCH + (TPX[t + 1] % 3) * PSTRIDE);
-                        return i32x8_{(int)x0[0], (int)x0[1], (int)x0[2], (int)x0[3], (int)x1[0], (int)x1[1], (int)x1[2], (int)x1[3]};
+                        // 16 + 8 + 4 bytes: every register a read returns is used (a register that is loaded but dead gets
+                        // re-used by the allocator while the read is in flight, and the wait for that write-after-write
+                        // hazard is a full drain of the counter)
+                        const u32x2_ x1 = *reinterpret_cast<const u32x2_*>(a6 + 16);
+                        const unsigned xs = *reinterpret_cast<const unsigned*>(a6 + 28);
+                        return i32x8_{(int)x0[0], (int)x0[1], (int)x0[2], (int)x0[3], (int)x1[0], (int)x1[1], (int)xs, 0};
                     }
                     const u32x4_ x0 = *reinterpret_cast<const u32x4_*>(abuf + abase[j] + g * PITCH + (m - 2) * PSTRIDE);
                     return i32x8_{(int)x0[0], (int)x0[1], (int)x0[2], (int)x0[3], 0, 0, 0, 0};
@@ -1456,16 +1255,13 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
                             __builtin_amdgcn_sched_barrier(0);       // (a fence for the compiler's scheduler, no instruction)
                         }
                         if (m < 2) {
-                            if constexpr (X6) {      // fp6 x fp6, block scales: dword 6 of either operand (byte 0)
-                                if constexpr (TR)
-                                    acc[j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(m == 0 ? bm0 : bm1, cur, acc[j], 2, 2, 0,
-                                                                                             m == 0 ? bm0[6] : bm1[6], 0, cur[6]);
-                                else
-                                    acc[j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(cur, m == 0 ? bm0 : bm1, acc[j], 2, 2, 0, cur[6], 0,
-                                                                                             m == 0 ? bm0[6] : bm1[6]);
-                            } else {
-                                acc[j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(cur, m == 0 ? bm0 : bm1, acc[j], 0, 0, 0, 0, 0, 0);
-                            }
+                            // fp6 x fp6, block scales: dword 6 of either operand (byte 0)
+                            if constexpr (TR)
+                                acc[j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(m == 0 ? bm0 : bm1, cur, acc[j], 2, 2, 0,
+                                                                                         m == 0 ? bm0[6] : bm1[6], 0, cur[6]);
+                            else
+                                acc[j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(cur, m == 0 ? bm0 : bm1, acc[j], 2, 2, 0, cur[6], 0,
+                                                                                         m == 0 ? bm0[6] : bm1[6]);
                             if constexpr (X6RD) {      // (the unused 4th dword of the second read stays allocated until here)
                                 const int keep = cur[7];
                                 asm volatile("" : : "v"(keep));
@@ -1482,98 +1278,12 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
 #pragma unroll
                         for (int p = 0; p < BP; ++p) bq[i][p] = bq[i + 1][p];
                 }
-                } else {
-#pragma unroll
-                for (int g = 0; g < 3; ++g) {
-                    const long nxt = (long)min(chunk * 3 + g + NQ - 1, last_step);
-                    // (the entry of tap row 2 has one fp8 MFMA: its last two planes are padding and stay out of registers)
-#pragma unroll
-                    for (int p = 0; p < BP; ++p)
-                        if (p < 5 || (g + NQ - 1) % 3 != 2) bq[NQ - 1][p] = ldb(nxt, p);
-                    if (g == 0 && ISSUE_LATE) { __builtin_amdgcn_sched_barrier(0); LRPXH_ISSUE_NEXT }
-                    const f16x8 bh0 = __builtin_bit_cast(f16x8, bq[0][0]);
-                    const f16x8 bh1 = __builtin_bit_cast(f16x8, bq[0][1]);
-                    const f16x8 bh2 = __builtin_bit_cast(f16x8, bq[0][2]);
-                    const i32x8_ bm0 = {(int)bq[0][3][0], (int)bq[0][3][1], (int)bq[0][3][2], (int)bq[0][3][3],
-                                        (int)bq[0][4][0], (int)bq[0][4][1], (int)bq[0][4][2], (int)bq[0][4][3]};
-                    const i32x8_ bm1 = {(int)bq[0][5][0], (int)bq[0][5][1], (int)bq[0][5][2], (int)bq[0][5][3],
-                                        (int)bq[0][6][0], (int)bq[0][6][1], (int)bq[0][6][2], (int)bq[0][6][3]};
-#pragma unroll
-                    for (int j = 0; j < 7; ++j) {
-                        const char* ap = abuf + abase[j] + g * PITCH;
-                        const char* a8 = abuf + abase[j] + c8;
-                        // taps 2m, 2m+1 of fp8 MFMA m = 2g (+1); the slice of the non-existent tap 9 re-reads tap 8 against
-                        // zero weights (leaving it out of the read with an exec mask was 45 % slower: every masked region
-                        // fences the scheduler)
-                        constexpr int TP[10] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 8};
-#define LRPXH_TOFF(t) ((TP[t] / 3) * PITCH + (TP[t] % 3) * PSTRIDE)
-                        u32x4_ p0, p1;
-                        if constexpr (X6) {
-                            const char* a6 = abuf + abase[j] + (g == 2 ? e6c : e6a) + LRPXH_TOFF(4 * g);
-                            p0 = *reinterpret_cast<const u32x4_*>(a6);
-                            const u32x4_ y_ = *reinterpret_cast<const u32x4_*>(a6 + 16);
-                            p1 = u32x4_{y_[0], y_[1], y_[3], y_[2]};
-                        } else {
-                            p0 = *reinterpret_cast<const u32x4_*>(a8 + LRPXH_TOFF(4 * g));
-                            p1 = *reinterpret_cast<const u32x4_*>(a8 + LRPXH_TOFF(4 * g + 1));
-                        }
-                        const f16x8 h0 = *reinterpret_cast<const f16x8*>(ap);
-                        const f16x8 h1 = *reinterpret_cast<const f16x8*>(ap + PSTRIDE);
-                        const f16x8 h2 = *reinterpret_cast<const f16x8*>(ap + 2 * PSTRIDE);
-                        const i32x8_ am0 = {(int)p0[0], (int)p0[1], (int)p0[2], (int)p0[3], (int)p1[0], (int)p1[1], (int)p1[2], (int)p1[3]};
-                        // small terms first: the cross products on the fp8 cores, then hi * hi_W
-                        if constexpr (TR) acc[j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(bm0, am0, acc[j], 2, 2, 0, bm0[6], 0, am0[6]);
-                        else if constexpr (X6) acc[j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(am0, bm0, acc[j], 2, 2, 0, am0[6], 0, bm0[6]);
-                        else acc[j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(am0, bm0, acc[j], 0, 0, 0, 0, 0, 0);
-                        if (g < 2) {          // (compile-time after unrolling)
-                            u32x4_ q0, q1;
-                            if constexpr (X6) {       // taps 4g + 2 / 4g + 3: g = 0: a row less two pixels apart, g = 1: one pixel
-                                const char* a6 = abuf + abase[j] + (g == 0 ? e6b : e6a) + LRPXH_TOFF(g < 2 ? 4 * g + 2 : 0);
-                                q0 = *reinterpret_cast<const u32x4_*>(a6);
-                                const u32x4_ y_ = *reinterpret_cast<const u32x4_*>(a6 + 16);
-                                q1 = u32x4_{y_[0], y_[1], y_[3], y_[2]};
-                            } else {
-                                q0 = *reinterpret_cast<const u32x4_*>(a8 + LRPXH_TOFF(g < 2 ? 4 * g + 2 : 0));
-                                q1 = *reinterpret_cast<const u32x4_*>(a8 + LRPXH_TOFF(g < 2 ? 4 * g + 3 : 0));
-                            }
-#undef LRPXH_TOFF
-                            const i32x8_ am1 = {(int)q0[0], (int)q0[1], (int)q0[2], (int)q0[3], (int)q1[0], (int)q1[1], (int)q1[2], (int)q1[3]};
-                            if constexpr (TR) acc[j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(bm1, am1, acc[j], 2, 2, 0, bm1[6], 0, am1[6]);
-                            else if constexpr (X6) acc[j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(am1, bm1, acc[j], 2, 2, 0, am1[6], 0, bm1[6]);
-                            else acc[j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(am1, bm1, acc[j], 0, 0, 0, 0, 0, 0);
-                        }
-                        if constexpr (TR) {
-                            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh0, h0, acc[j], 0, 0, 0);
-                            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh1, h1, acc[j], 0, 0, 0);
-                            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh2, h2, acc[j], 0, 0, 0);
-                        } else {
-                        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h0, bh0, acc[j], 0, 0, 0);
-                        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h1, bh1, acc[j], 0, 0, 0);
-                        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h2, bh2, acc[j], 0, 0, 0);
-                        }
-                        if constexpr (LRPXH_F8_SGB != 0) {
-                            const int gn = (j == 6) ? g + 1 : g;                     // tap row of the next tile
-                            if (gn < 2) __builtin_amdgcn_sched_group_barrier(0x100, 7, 0);
-                            else if (gn == 2) __builtin_amdgcn_sched_group_barrier(0x100, 5, 0);
-                            if (g < 2) __builtin_amdgcn_sched_group_barrier(0x008, 5, 0);
-                            else __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-                        }
-                    }
-#pragma unroll
-                    for (int i = 0; i < NQ - 1; ++i)
-#pragma unroll
-                        for (int p = 0; p < BP; ++p) bq[i][p] = bq[i + 1][p];
-                }
-                }
             } else if constexpr (B6) {
             // six bf16 products per (tap, accumulator tile), smallest first; A fragments (three planes) one tile ahead of their MFMAs
-            bf16x8 n0, n1, n2;
-            if constexpr (APIPE) {
-                n0 = *reinterpret_cast<const bf16x8*>(abuf + abase[0]);
-                n1 = *reinterpret_cast<const bf16x8*>(abuf + abase[0] + 32);
-                n2 = *reinterpret_cast<const bf16x8*>(abuf + abase[0] + 64);
-                __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
-            }
+            bf16x8 n0 = *reinterpret_cast<const bf16x8*>(abuf + abase[0]);
+            bf16x8 n1 = *reinterpret_cast<const bf16x8*>(abuf + abase[0] + 32);
+            bf16x8 n2 = *reinterpret_cast<const bf16x8*>(abuf + abase[0] + 64);
+            __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
 #pragma unroll
             for (int tap = 0; tap < TAPS; ++tap) {
                 const long nxt = (long)min(chunk * TAPS + tap + NBQ - 1, last_step) * 3;
@@ -1585,21 +1295,13 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
                 const bf16x8 b2 = __builtin_bit_cast(bf16x8, bq[0][2]);
 #pragma unroll
                 for (int j = 0; j < 7; ++j) {
-                    bf16x8 a0, a1, a2;
-                    if constexpr (APIPE) {
-                        a0 = n0; a1 = n1; a2 = n2;
-                        if (!(tap == TAPS - 1 && j == 6)) {
-                            const int jn = (j + 1) % 7, tn = tap + (j == 6 ? 1 : 0);
-                            const char* apn = abuf + abase[jn] + (tn / 3) * PITCH + (tn % 3) * PSTRIDE;
-                            n2 = *reinterpret_cast<const bf16x8*>(apn + 64);
-                            n1 = *reinterpret_cast<const bf16x8*>(apn + 32);
-                            n0 = *reinterpret_cast<const bf16x8*>(apn);
-                        }
-                    } else {
-                        const char* ap = abuf + abase[j] + (tap / 3) * PITCH + (tap % 3) * PSTRIDE;
-                        a0 = *reinterpret_cast<const bf16x8*>(ap);
-                        a1 = *reinterpret_cast<const bf16x8*>(ap + 32);
-                        a2 = *reinterpret_cast<const bf16x8*>(ap + 64);
+                    const bf16x8 a0 = n0, a1 = n1, a2 = n2;
+                    if (!(tap == TAPS - 1 && j == 6)) {
+                        const int jn = (j + 1) % 7, tn = tap + (j == 6 ? 1 : 0);
+                        const char* apn = abuf + abase[jn] + (tn / 3) * PITCH + (tn % 3) * PSTRIDE;
+                        n2 = *reinterpret_cast<const bf16x8*>(apn + 64);
+                        n1 = *reinterpret_cast<const bf16x8*>(apn + 32);
+                        n0 = *reinterpret_cast<const bf16x8*>(apn);
                     }
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b0, acc[j], 0, 0, 0);
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc[j], 0, 0, 0);
@@ -1607,10 +1309,8 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc[j], 0, 0, 0);
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc[j], 0, 0, 0);
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc[j], 0, 0, 0);
-                    if constexpr (APIPE) {
-                        __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);   // the 3 reads of the NEXT tile ...
-                        __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);   // ... then the 6 MFMAs of this one
-                    }
+                    __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);   // the 3 reads of the NEXT tile ...
+                    __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);   // ... then the 6 MFMAs of this one
                 }
 #pragma unroll
                 for (int i = 0; i < NBQ - 1; ++i)
@@ -1618,24 +1318,18 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
                     for (int p = 0; p < 3; ++p) bq[i][p] = bq[i + 1][p];
             }
             } else {
-#ifndef LRPXH_APIPE_D
-#define LRPXH_APIPE_D 1       // A fragments read this many accumulator tiles ahead of their MFMAs (non-F8 path: forward trace, mode 2)
-#endif
-            constexpr int AD = LRPXH_APIPE_D;
+            constexpr int AD = 1;     // A fragments read this many accumulator tiles ahead of their MFMAs (forward trace, mode 2)
             f16x8 nq[AD][2];          // ring: nq[t % AD] = fragments (hi, lo) of op t = tap * 7 + j
-            if constexpr (APIPE) {
 #pragma unroll
-                for (int d = 0; d < AD; ++d) {
-                    const int jn = d % 7, tn = d / 7;
-                    const char* apn = abuf + abase[jn] + (tn / 3) * PITCH + (tn % 3) * PSTRIDE;
-                    nq[d][0] = *reinterpret_cast<const f16x8*>(apn);
-                    nq[d][1] = *reinterpret_cast<const f16x8*>(apn + 32);
-                }
-                __builtin_amdgcn_sched_group_barrier(0x100, 2 * AD, 0);
+            for (int d = 0; d < AD; ++d) {
+                const int jn = d % 7, tn = d / 7;
+                const char* apn = abuf + abase[jn] + (tn / 3) * PITCH + (tn % 3) * PSTRIDE;
+                nq[d][0] = *reinterpret_cast<const f16x8*>(apn);
+                nq[d][1] = *reinterpret_cast<const f16x8*>(apn + 32);
             }
+            __builtin_amdgcn_sched_group_barrier(0x100, 2 * AD, 0);
 #pragma unroll
             for (int tap = 0; tap < TAPS; ++tap) {
-                const int tapoff = (tap / 3) * PITCH + (tap % 3) * PSTRIDE;
                 const long nxt = (long)min(chunk * TAPS + tap + NBQ - 1, last_step) * 2;
 #pragma unroll
                 for (int p = 0; p < 2; ++p) bq[NBQ - 1][p] = wp[(nxt + p) * 64];
@@ -1644,29 +1338,20 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
                 const f16x8 b1 = __builtin_bit_cast(f16x8, bq[0][1]);
 #pragma unroll
                 for (int j = 0; j < 7; ++j) {
-                    f16x8 a0, a1;
-                    if constexpr (APIPE) {
-                        const int t = tap * 7 + j;
-                        a0 = nq[t % AD][0]; a1 = nq[t % AD][1];
-                        if (t + AD < TAPS * 7) {
-                            const int jn = (t + AD) % 7, tn = (t + AD) / 7;
-                            const char* apn = abuf + abase[jn] + (tn / 3) * PITCH + (tn % 3) * PSTRIDE;
-                            nq[t % AD][1] = *reinterpret_cast<const f16x8*>(apn + 32);
-                            nq[t % AD][0] = *reinterpret_cast<const f16x8*>(apn);
-                        }
-                    } else {
-                        const char* ap = abuf + abase[j] + tapoff;
-                        a0 = *reinterpret_cast<const f16x8*>(ap);
-                        a1 = *reinterpret_cast<const f16x8*>(ap + 32);
+                    const int t = tap * 7 + j;
+                    const f16x8 a0 = nq[t % AD][0], a1 = nq[t % AD][1];
+                    if (t + AD < TAPS * 7) {
+                        const int jn = (t + AD) % 7, tn = (t + AD) / 7;
+                        const char* apn = abuf + abase[jn] + (tn / 3) * PITCH + (tn % 3) * PSTRIDE;
+                        nq[t % AD][1] = *reinterpret_cast<const f16x8*>(apn + 32);
+                        nq[t % AD][0] = *reinterpret_cast<const f16x8*>(apn);
                     }
                     // small terms first
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b0, acc[j], 0, 0, 0);
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1, acc[j], 0, 0, 0);
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0, acc[j], 0, 0, 0);
-                    if constexpr (APIPE) {
-                        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);   // the 2 reads of a LATER tile ...
-                        __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);   // ... then the 3 MFMAs of this one
-                    }
+                    __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);   // the 2 reads of a LATER tile ...
+                    __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);   // ... then the 3 MFMAs of this one
                 }
 #pragma unroll
                 for (int i = 0; i < NBQ - 1; ++i)
@@ -1770,15 +1455,9 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
         return;
     }
 
-#ifndef LRPXH_AL_EPI
-#define LRPXH_AL_EPI 1
-#endif
     // (measured, same box: conv1_2 2.77 -> 2.60 ms, conv2_2 2.07 -> 2.00, conv3_1 0.96 -> 0.93, the 8-wave 56x56 layers +-0; the
     // 4-row 112x112 kernel of conv2_1 spills 9 registers with it, 1.09 -> 1.14: it keeps the generic epilogue)
-#ifndef LRPXH_AL_EPI_H3
-#define LRPXH_AL_EPI_H3 1      // mode 2 (three fp16 products) too: round 5
-#endif
-    if constexpr ((X6 || (!F8 && (LRPXH_AL_EPI_H3 != 0))) && AL && (LRPXH_AL_EPI != 0) && !(HW == 112 && MT == 2 && !B6) && (EPI == EPI_REL_MUL || EPI == EPI_GUIDED)) {
+    if constexpr (AL && !(HW == 112 && MT == 2 && !B6) && (EPI == EPI_REL_MUL || EPI == EPI_GUIDED)) {
         unsigned* __restrict__ oamax_a = (EPI == EPI_GUIDED) ? a.out0_amax : (a.out1 ? a.out1_amax : nullptr);
         epi_rel_mul_al<HW, EPI, F8, false, B6>(a, acc, wm, ocb, lane, g0, total_pix, oamax_a, inv_w, in_amax);
 #ifdef LRPX_STAMP
@@ -1799,10 +1478,7 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
 #endif
         return;
     }
-#ifndef LRPXH_AL_FWD
-#define LRPXH_AL_FWD 1
-#endif
-    if constexpr (AL && (LRPXH_AL_FWD != 0) && EPI == EPI_FWD_DUAL) {
+    if constexpr (AL && EPI == EPI_FWD_DUAL) {
         if ((a.oc_split & 31) == 0) {                      // (uniform; every VGG16 layer)
             epi_fwd_dual_al<HW, F8, B6>(a, acc, wm, ocb, lane, g0, inv_w, in_amax);
             return;
@@ -1830,7 +1506,7 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
         // exact splits: nothing to undo
     } else if constexpr (AL) {
         const unsigned n = (unsigned)g0 / (unsigned)H;
-        const float inv_a = exp2i(-split_scale_exp<F8>(in_amax[min((int)n, nmax)]));
+        const float inv_a = exp2i(-f16_scale_exp(in_amax[min((int)n, nmax)]));
 #pragma unroll
         for (int j = 0; j < 7; ++j)
 #pragma unroll
@@ -1860,14 +1536,11 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
     unsigned* __restrict__ oamax = (EPI == EPI_FWD_DUAL || EPI == EPI_GUIDED) ? a.out0_amax
                                    : (((EPI == EPI_REL || EPI == EPI_REL_MUL) && a.out1) ? a.out1_amax : nullptr);
     EpiMax mx0 = {0.f, 0.f}, mx1 = mx0, mx2 = mx0, mx3 = mx0, mx4 = mx0, mx5 = mx0, mx6 = mx0;   // (scalars: an array
-#ifndef LRPXH_WIDE_EPI
-#define LRPXH_WIDE_EPI 1
-#endif
     // measured per layer (chain of 320 maps, tools/ab_chain.sh): the map-straddling 28x28 / 14x14 kernels gain 4-6 % (and
     // lose their 11-13 spilled VGPRs: the two-map dword epilogue held two candidate addresses per element); the aligned
     // 56 / 112 / 224 kernels are 1-5 % SLOWER with it (their dword epilogue has compile-time offsets from one base), so
-    // LRPXH_WIDE_EPI = 1 selects it for the straddling kernels only, 2 everywhere
-    if constexpr ((EPI == EPI_REL_MUL || EPI == EPI_GUIDED) && ((LRPXH_WIDE_EPI == 1 && !AL) || LRPXH_WIDE_EPI == 2)) {
+    // only the straddling kernels take it
+    if constexpr ((EPI == EPI_REL_MUL || EPI == EPI_GUIDED) && !AL) {
         // (the K loop ends with a barrier: nobody reads the staging buffers any more; 32 x 36 floats per wave)
         float* scr = reinterpret_cast<float*>(ldsb) + wave * (32 * 36);
         epi_rel_mul_wide<HW, AL, EPI>(a, acc, scr, wm, ocb, lane, g0, total_pix, oamax, tile_tab);

@@ -21,10 +21,6 @@
 
 #include "build_guard.h"
 
-#ifndef LRPXH_NT_STORE
-#define LRPXH_NT_STORE 3      // bit 0: float4 (wide) REL_MUL epilogue, bit 1: dword epilogue: streaming stores
-#endif
-
 #ifndef LRPX_EPI_EXP
 #define LRPX_EPI_EXP 0      // timing experiments on the epilogues (wrong results): 1 = no multiplicand loads, 2 = no stores
 #endif
@@ -252,10 +248,8 @@ __device__ __forceinline__ void epi_finish(const ConvArgs& a, const EpiCtx& cx, 
             // of the weights and multiplicands in L2 is worth 2 % on the wide layers (chain 21.23 -> 21.06 ms)
 #if LRPX_EPI_EXP & 2
             if (rel == 1.2345e-30f) ob[dq * ostr] = rel;
-#elif LRPXH_NT_STORE & 2
-            __builtin_nontemporal_store(rel, &ob[dq * ostr]);
 #else
-            ob[dq * ostr] = rel;
+            __builtin_nontemporal_store(rel, &ob[dq * ostr]);
 #endif
             if (mx) {
                 const bool past = !ALIGNED && TAPS == 9 && p0t + dq >= (int)P;

@@ -22,9 +22,6 @@
 namespace lrpx {
 
 constexpr int DH_BN = 128;
-#ifndef LRPXB_SCHED
-#define LRPXB_SCHED 1       // 1: fences around the A-fragment prefetch and the k-steps; 0: the compiler's own schedule; 2: commit spread over the k-steps
-#endif
 #ifndef LRPXB_EXP
 #define LRPXB_EXP 0       // timing experiments (wrong results): 1 no epilogue, 2 no MFMAs, 4 no staging loads / commits, 8 no B loads
 #endif
@@ -87,16 +84,6 @@ __global__ __launch_bounds__(WM * 128, WM == 2 ? 2 : 1) void dense_f16x3_kernel(
         *reinterpret_cast<u32x2_*>(d_) = u32x2_{h0_, h1_};                                                 \
         *reinterpret_cast<u32x2_*>(d_ + 32) = u32x2_{l0_, l1_};                                            \
     }
-#define DH_COMMIT_PART(BUFI, U0, NUM)                                                                     \
-    _Pragma("unroll") for (int u = (U0); u < (U0) + (NUM); ++u) {                                          \
-        unsigned h0_, h1_, l0_, l1_;                                                                       \
-        f32x2_ f0_, f1_;                                                                                   \
-        split2_pk(f32x2_{sv[u][0], sv[u][1]} * f32x2_{ssc[u], ssc[u]}, h0_, l0_, f0_);                     \
-        split2_pk(f32x2_{sv[u][2], sv[u][3]} * f32x2_{ssc[u], ssc[u]}, h1_, l1_, f1_);                     \
-        char* d_ = ldsb + (BUFI) * C::BUF + (s_row + C::RP * u) * C::ROWB + s_off;                         \
-        *reinterpret_cast<u32x2_*>(d_) = u32x2_{h0_, h1_};                                                 \
-        *reinterpret_cast<u32x2_*>(d_ + 32) = u32x2_{l0_, l1_};                                            \
-    }
     DH_ISSUE(0)
 
     // ---- B fragments: [ocb][chunk16][plane 2][lane 64][16 B]; a wave without a column block of its own multiplies the
@@ -151,13 +138,13 @@ __global__ __launch_bounds__(WM * 128, WM == 2 ? 2 : 1) void dense_f16x3_kernel(
                 f[3] = *reinterpret_cast<const f16x8*>(abuf + 32 * C::ROWB + s_ * 64 + 32);
             };
             read_a(0, af[0]);
-            if constexpr (LRPXB_SCHED == 1) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);     // (fences around the A-fragment prefetch and the k-steps)
 #pragma unroll
             for (int s = 0; s < C::KS; ++s) {
                 const int q = cc * C::KS + s;                  // position in the iteration's 4 k-steps: static ring indices
                 if constexpr (!(LRPXB_EXP & 8)) load_b(chunk * C::KS + s + DH_NBQ - 1, bq[(q + DH_NBQ - 1) % DH_NBQ]);
                 if (s + 1 < C::KS) read_a(s + 1, af[(s + 1) & 1]);
-                if constexpr (LRPXB_SCHED == 1) __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);
                 const f16x8 a0h = af[s & 1][0], a0l = af[s & 1][1], a1h = af[s & 1][2], a1l = af[s & 1][3];
                 const u32x4_(&b)[4] = bq[q % DH_NBQ];
                 const f16x8 b0h = __builtin_bit_cast(f16x8, b[0]), b0l = __builtin_bit_cast(f16x8, b[1]);
@@ -176,21 +163,14 @@ __global__ __launch_bounds__(WM * 128, WM == 2 ? 2 : 1) void dense_f16x3_kernel(
                 acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0h, b1h, acc[0][1], 0, 0, 0);
                 acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1h, b0h, acc[1][0], 0, 0, 0);
                 acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1h, b1h, acc[1][1], 0, 0, 0);
-                if constexpr (LRPXB_SCHED == 1) __builtin_amdgcn_sched_barrier(0);
-                if constexpr (LRPXB_SCHED == 2 && !(LRPXB_EXP & 4)) {
-                    // a quarter (half) of the next chunk's commit behind every k-step: conversions and LDS writes in the shadow of
-                    // the 12 MFMAs just issued (the last chunk commits into the idle buffer: harmless, no branch)
-                    constexpr int PER = C::NU / C::KS;
-                    DH_COMMIT_PART(C::CPI == 1 ? ((chunk + 1) & 1) : (1 - cc), s * PER, PER)
-                }
+                __builtin_amdgcn_sched_barrier(0);
             }
-            if constexpr (LRPXB_SCHED != 2) { if (chunk + 1 < nchunk && !(LRPXB_EXP & 4)) { DH_COMMIT(C::CPI == 1 ? ((chunk + 1) & 1) : (1 - cc)) } }
+            if (chunk + 1 < nchunk && !(LRPXB_EXP & 4)) { DH_COMMIT(C::CPI == 1 ? ((chunk + 1) & 1) : (1 - cc)) }
             __syncthreads();
         }
     }
 #undef DH_ISSUE
 #undef DH_COMMIT
-#undef DH_COMMIT_PART
 
     if constexpr (LRPXB_EXP & 1) { if (acc[0][0][0] + acc[0][1][1] + acc[1][0][2] + acc[1][1][3] == 12345.f) a.out0[0] = 1.f; return; }
     // ---- epilogue (EPI_REL of conv_mfma.h): element e of tile (i, j): row = row0 + wm*64 + 32 i + (e&3) + 8 (e>>2) + 4 lh,
@@ -297,10 +277,7 @@ __global__ __launch_bounds__(WM * 128, WM == 2 ? 2 : 1) void dense_f16x3_kernel(
 // Same products in the same order per accumulator as dense_f16x3_kernel: bit-identical results.
 // The per-row constants of the epilogue (map, multiplicand row, result scale) are computed ONCE by the first 128 threads at the
 // start and parked in LDS: the epilogue's loads no longer hang on a chain row -> map -> image -> operand maximum.
-#ifndef LRPXB_KC
-#define LRPXB_KC 32        // K chunk of the 128 x 256 kernel (one barrier and one commit per chunk)
-#endif
-constexpr int DN_BM = 128, DN_BN = 256, DN_KC = LRPXB_KC, DN_KS = DN_KC / 16;
+constexpr int DN_BM = 128, DN_BN = 256, DN_KC = 32, DN_KS = DN_KC / 16;      // (K chunk: one barrier and one commit per chunk)
 // LDS row of the A chunk: per k-step [hi | lo] (f16x3) or [p0 | p1 | p2] (B6: exact bf16 split) x 2 lane groups x 16 B, + 16 B pad (9 / 13
 // 16-byte units per row: odd, conflict-free ds_read_b128)
 template <bool B6> struct DnCfg {
@@ -308,16 +285,6 @@ template <bool B6> struct DnCfg {
 };
 #ifdef LRPX_STAMP
 static __device__ unsigned long long g_stamp_dn[16384 * 10];      // per wave: start, loop start, loop end, stores issued, stores drained, sum issue..MFMAs, sum commit, sum barrier, HW_ID, XCC_ID
-#endif
-#ifndef LRPXB_SCR_PITCH
-#define LRPXB_SCR_PITCH 32   // epilogue scratch of the 128 x 256 kernel, floats per row: 32 = no padding - the dword writes of a half wave and the
-                            // 16-byte reads of two rows each cover 32 / 64 distinct banks (36: the reads of rows r, r + 1 overlap in 4 banks)
-#endif
-#ifndef LRPXB_SHADOW
-#define LRPXB_SHADOW 1     // the 128 x 256 kernel converts / commits the next chunk between the MFMAs of the current one (0: a commit phase per chunk)
-#endif
-#ifndef LRPXB_NBQ
-#define LRPXB_NBQ 2        // B ring of the 128 x 256 kernel: k-steps in registers (2: one ahead; 3: two ahead - measured +-0, 16 registers more)
 #endif
 // B6 (round 6): the same tile on the bf16 matrix cores with EXACT operands - a = a0 + a1 + a2 (three bf16 parts, split while staged; weights
 // from lrpx_pack_weights_bf16x3, taps = 1), the six products with i + j <= 2 on v_mfma_f32_32x32x16_bf16, small terms first
@@ -377,8 +344,8 @@ __global__ __launch_bounds__(256, 2) void dense_f16x3_n256_kernel(ConvArgs a, in
         else ssc[u] = 1.f;
     }
     const int s_off = (s_seg >> 2) * (32 * PL) + ((s_seg >> 1) & 1) * 16 + (s_seg & 1) * 8;
-    constexpr bool SHADOW = LRPXB_SHADOW != 0;      // the next chunk's conversion + LDS writes between the MFMAs of this one (loads two chunks ahead)
-    f32x4 sv[SHADOW ? 2 : 1][NU];
+    // "shadow" commits: the next chunk's conversion + LDS writes go between the MFMAs of this one, so the loads run two chunks ahead
+    f32x4 sv[2][NU];
     const float* __restrict__ A = a.in;
     auto issue = [&](const int chunk, const int set) {
         const float* __restrict__ Ac = A + chunk * DN_KC;
@@ -416,7 +383,7 @@ __global__ __launch_bounds__(256, 2) void dense_f16x3_n256_kernel(ConvArgs a, in
     const u32x4_* wp0 = reinterpret_cast<const u32x4_*>(a.wp + (B6 ? 0 : F16X3_HEADER_FLOATS)) + (long)min(ocb0, ocb_last) * nks * (64 * PL) + lane;
     const u32x4_* wp1 = reinterpret_cast<const u32x4_*>(a.wp + (B6 ? 0 : F16X3_HEADER_FLOATS)) + (long)min(ocb0 + 1, ocb_last) * nks * (64 * PL) + lane;
     // B ring: k-step s + NBQ - 1 is loaded while k-step s multiplies (24 MFMAs = 768 matrix cycles per k-step)
-    constexpr int NBQ = LRPXB_NBQ;
+    constexpr int NBQ = 2;           // k-steps in registers: one ahead (two ahead: measured +-0, 16 registers more)
     u32x4_ bq[NBQ][2 * PL];          // [tile 0 hi, lo, tile 1 hi, lo]; B6: [tile 0 p0, p1, p2, tile 1 p0, p1, p2]
     auto load_b = [&](const int ks, u32x4_ (&b)[2 * PL]) {
         const int k = min(ks, nks - 1);
@@ -435,15 +402,15 @@ __global__ __launch_bounds__(256, 2) void dense_f16x3_n256_kernel(ConvArgs a, in
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
     commit(0, 0);
-    if constexpr (SHADOW) issue(min(1, nchunk - 1), 1);
+    issue(min(1, nchunk - 1), 1);
     __syncthreads();
     LRPXH_T(ts1);
     const int a_off = li * DN_ROWB + lh * 16;
-    static_assert(!SHADOW || (NU <= 2 * DN_KS && NBQ == 2), "at most one staging item per (k-step, pair) step; two chunks per loop trip");
+    static_assert(NU <= 2 * DN_KS && NBQ == 2, "at most one staging item per (k-step, pair) step; two chunks per loop trip");
     static_assert(RT == 4 || RT == 3, "two pairs of row tiles, or a pair and a single one");
     // (NBQ chunks per loop iteration: the ring positions are compile-time constants - 2 NBQ k-steps, a multiple of the ring)
     if constexpr (B6) {
-        static_assert(SHADOW && NBQ == 2 && NU <= RT * DN_KS, "B6: shadow commits, a two-deep B ring");
+        static_assert(NBQ == 2 && NU <= RT * DN_KS, "B6: shadow commits, a two-deep B ring");
         for (int c0 = 0; c0 < nchunk; c0 += 2) {
 #pragma unroll
             for (int cc = 0; cc < 2; ++cc) {
@@ -500,9 +467,9 @@ __global__ __launch_bounds__(256, 2) void dense_f16x3_n256_kernel(ConvArgs a, in
             const int chunk = c0 + cc;
             if (chunk >= nchunk) break;                      // (uniform)
             LRPXH_T(ta);
-            // SHADOW: chunk + 2 into the register set chunk's data left at the end of the previous trip (set index = cc: c0 is even)
-            if constexpr (SHADOW) issue(min(chunk + 2, nchunk - 1), cc & 1);
-            else issue(min(chunk + 1, nchunk - 1), 0);       // (past the last chunk: re-read it, nobody commits it)
+            // chunk + 2 into the register set chunk's data left at the end of the previous trip (set index = cc: c0 is even; past the last
+            // chunk: re-read it)
+            issue(min(chunk + 2, nchunk - 1), cc & 1);
             __builtin_amdgcn_sched_barrier(0);               // keep the loads here (cf. dense_f16x3_kernel)
             const char* abuf = ldsb + (chunk & 1) * DN_BUF + a_off;
             // A fragments of a PAIR of row tiles one step ahead of their 12 MFMAs: [tile 2p hi, lo, tile 2p + 1 hi, lo]
@@ -525,10 +492,10 @@ __global__ __launch_bounds__(256, 2) void dense_f16x3_n256_kernel(ConvArgs a, in
                 if (pr == 0) load_b(chunk * DN_KS + s + NBQ - 1, bq[(q + NBQ - 1) % NBQ]);
                 if (t + 1 < 2 * DN_KS) read_pair(t + 1, af[(t + 1) & 1]);
                 __builtin_amdgcn_sched_barrier(0);
-                // SHADOW: item t of the NEXT chunk (loaded a chunk ago) is scaled, split and written to the other buffer under these
+                // item t of the NEXT chunk (loaded a chunk ago) is scaled, split and written to the other buffer under these
                 // 12 MFMAs - two vector instructions behind each (the vector issue is free for most of an MFMA's 32 cycles)
                 // (no branch around it - the scheduler mixes within a basic block only: the last chunk writes a copy of itself into the idle buffer)
-                if constexpr (SHADOW) { if (t < NU) commit_item((chunk + 1) & 1, (cc + 1) & 1, t); }
+                if (t < NU) commit_item((chunk + 1) & 1, (cc + 1) & 1, t);
                 const f16x8 a0h = af[t & 1][0], a0l = af[t & 1][1], a1h = af[t & 1][2], a1l = af[t & 1][3];
                 const u32x4_(&b)[2 * PL] = bq[q % NBQ];
                 const f16x8 b0h = __builtin_bit_cast(f16x8, b[0]), b0l = __builtin_bit_cast(f16x8, b[1]);
@@ -554,28 +521,25 @@ __global__ __launch_bounds__(256, 2) void dense_f16x3_n256_kernel(ConvArgs a, in
                     c10 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1h, b0h, c10, 0, 0, 0);
                     c11 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1h, b1h, c11, 0, 0, 0);
                 }
-                if constexpr (SHADOW) {
-                    if (two) {
+                if (two) {
 #pragma unroll
-                        for (int g = 0; g < 10; ++g) {
-                            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // one MFMA
-                            __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);      // two vector instructions
-                        }
-                    } else {
-#pragma unroll
-                        for (int g = 0; g < 4; ++g) {
-                            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                            __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-                        }
+                    for (int g = 0; g < 10; ++g) {
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // one MFMA
+                        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);      // two vector instructions
                     }
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x200, 2, 0);          // the LDS writes
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                } else {
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+                    }
                 }
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x200, 2, 0);          // the LDS writes
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
             LRPXH_T(tb);
-            if constexpr (!SHADOW) { if (chunk + 1 < nchunk) commit((chunk + 1) & 1, 0); }
             LRPXH_T(tc);
             __syncthreads();
 #ifdef LRPX_STAMP
@@ -603,7 +567,9 @@ __global__ __launch_bounds__(256, 2) void dense_f16x3_n256_kernel(ConvArgs a, in
     // addend, the denominator and the result move as 16 bytes per lane: 4 + 4 memory instructions per tile instead of 16 + 16, every
     // wave instruction 8 rows x 128 bytes.  (With dword accesses the epilogue ran at 3.8 TB/s of stores when it was all the kernel
     // did - K = 64 - against 6.9 for a fill of the same bytes.)  The loads of unit u + 1 are in flight while unit u is finished.
-    constexpr int SP = LRPXB_SCR_PITCH;                                        // floats per scratch row
+    // 32 floats per scratch row = no padding: the dword writes of a half wave and the 16-byte reads of two rows each cover 32 / 64
+    // distinct banks (36: the reads of rows r, r + 1 overlap in 4 banks)
+    constexpr int SP = 32;
     float* scr = reinterpret_cast<float*>(ldsb) + wave * (32 * SP);            // [32 rows][SP]
     const int tr = lane >> 3, tc = (lane & 7) * 4;
     constexpr int DEPTH = 2;
@@ -720,9 +686,6 @@ __global__ __launch_bounds__(256, 2) void dense_f16x3_n256_kernel(ConvArgs a, in
 // B queue: 11 k-steps ahead (a k-step is 3 MFMAs = 96 matrix cycles, an L2 round trip ~1000: 5 ahead left the K loop bound by
 // the load latency - 28 us per GEMM against 25 for the fp32 kernel it replaces)
 constexpr int DS_NB = 12;
-#ifndef LRPXD_EARLY
-#define LRPXD_EARLY 1     // few-row kernel, K = 512: the epilogue's multiplicand / addend loads issued before the K loop (0: in the epilogue)
-#endif
 #ifndef LRPXD_EXP
 #define LRPXD_EXP 0       // timing experiments (wrong results): 1 no multiplicand / addend loads in the epilogue, 2 no K loop, 4 no A staging, 8 no stores
 #endif
@@ -758,7 +721,7 @@ __global__ __launch_bounds__(256, 2) void dense_small_f16x3_kernel(ConvArgs a, i
     // EARLY (K = 512, where the registers allow it): the epilogue's operands do not depend on the product - the row -> source-row
     // lookups are issued HERE, the multiplicands and addends right after the slab has gone to LDS, and both arrive under the K loop:
     // three dependent round trips (~3.5 of the kernel's 17 us) leave the epilogue.  Same arithmetic, bit-identical.
-    constexpr bool EARLY = (LRPXD_EARLY != 0) && MAXU == 16;
+    constexpr bool EARLY = MAXU == 16;
     const int* __restrict__ m2i = a.map2img;
     const unsigned P = (unsigned)a.pix_per_map;
     const unsigned last = (unsigned)(rows - 1);

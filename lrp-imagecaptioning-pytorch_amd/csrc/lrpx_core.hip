@@ -442,16 +442,15 @@ __global__ void pack_weights_f16x2_kernel(const float* __restrict__ w, float* __
     out[base + 512] = __builtin_bit_cast(unsigned short, lo);
 }
 
-// weights for the F8 variant of conv_f16x3.h (fp16 hi.hi product + two fp8 cross products): 64-byte header {2^-kW, amax
-// bits}, then [ocb][chunk 16][tap row g 3][plane 7][lane 64][16 B]: planes 0-2 = fp16 hi of taps (g, dx = 0,1,2) (lane
-// map as the f16x2 pack), planes 3/4 and 5/6 = B operands of the fp8 MFMAs 2g and 2g+1 of the chunk (conv_f16x3.h,
-// f8_slot_*: per lane two (tap, 16 channels) slots of fp8 e4m3: W*2^-4 for an "L" slot, (W - hi)*2^4 for an "S" slot,
-// zero for a pad slot).  W is scaled into [2^11, 2^12) first.
+// weights for the F8 variant of conv_f16x3.h (fp16 hi.hi product + two block-scaled fp6 cross products): 64-byte header {2^-kW,
+// amax bits}, then [ocb][chunk 16][tap row g 3][plane 7][lane 64][16 B]: planes 0-2 = fp16 hi of taps (g, dx = 0,1,2) (lane
+// map as the f16x2 pack), planes 3/4 and 5/6 = B operands of the fp6 MFMAs 2g and 2g+1 of the chunk (below).  W is scaled into
+// the fp16 range [2^14, 2^15) first.
 __global__ void pack_weights_f16f8_kernel(const float* __restrict__ w, float* __restrict__ header, int cout, int cin,
                                           int mode, int k_pad, long total) {
     long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
-    const int kw = split_scale_exp<true>(reinterpret_cast<const unsigned*>(header)[1]);
+    const int kw = f16_scale_exp(reinterpret_cast<const unsigned*>(header)[1]);
     if (idx == 0) header[0] = exp2i(-kw);
     const float sc = exp2i(kw);
     const int lane = idx & 63;
@@ -480,7 +479,6 @@ __global__ void pack_weights_f16f8_kernel(const float* __restrict__ w, float* __
         unsigned short* o = reinterpret_cast<unsigned short*>(out + dx * 1024);
         for (int j = 0; j < 8; ++j) o[j] = __builtin_bit_cast(unsigned short, (_Float16)wv(chunk * 16 + 8 * lh + j, dx));
     }
-#if LRPXH_XP6
     // fp6 cross products: planes 3/4 = B operand of MFMA m = 2g, planes 5/6 = MFMA 2g + 1 (none for g = 2).  A lane's 32 e2m3
     // values belong to ONE tap - 2m for lanes 0-31, 2m + 1 for lanes 32-63 (tap 9: zeros) - in the field order of the staging
     // code: field c meets x_c and holds (W_c - hi(W_c)) * 2^11, field 16 + c meets (x_c - hi) * 2^11 and holds W_c; all divided
@@ -518,35 +516,6 @@ __global__ void pack_weights_f16f8_kernel(const float* __restrict__ w, float* __
         }
         for (int q = 0; q < 4; ++q) { o[q] = words[q]; o[256 + q] = words[4 + q]; }
     }
-#else
-    // planes 3/4: B operand of fp8 MFMA m = 2g (taps 2m, 2m+1; lanes 0-31: "L" slices, lanes 32-63: "S" slices);
-    // planes 5/6: MFMA 2g+1 (none for g = 2)
-    for (int mm = 0; mm < 2; ++mm) {
-        const int m = 2 * g + mm;
-        for (int i = 0; i < 2; ++i) {
-            const int tap = f8_slot_tap(m, i);
-            const int kind = (m < 5 && tap <= 8) ? lh : 2;
-            unsigned* o = reinterpret_cast<unsigned*>(out + (3 + 2 * mm + i) * 1024);
-            for (int q = 0; q < 4; ++q) {
-                float v[4];
-                for (int e = 0; e < 4; ++e) {
-                    float x = 0.f;
-                    if (kind != 2) {
-                        const int k = chunk * 16 + q * 4 + e;
-                        float wsc = 0.f;
-                        if (mode == LRPX_PACK_BWD_POS) { if (k < cout && oc < cin) wsc = fmaxf(w[((long)k * cin + oc) * 9 + (8 - tap)], 0.f); }
-                        else if (mode == LRPX_PACK_BWD_PLAIN) { if (k < cout && oc < cin) wsc = w[((long)k * cin + oc) * 9 + (8 - tap)]; }
-                        wsc *= sc;
-                        // kind 0 ("L": activations' residual x - hi): weight operand W * 2^-4;  kind 1 ("S"): (W - hi_W) * 2^4
-                        x = kind == 0 ? wsc * 0.0625f : (wsc - (float)(_Float16)wsc) * 16.f;
-                    }
-                    v[e] = x;
-                }
-                o[q] = pack_fp8x4(v[0], v[1], v[2], v[3]);
-            }
-        }
-    }
-#endif
 }
 
 static void pack_dims(int cout, int cin, int mode, int kc, int* n_oc_pad, int* k_pad) {
