@@ -119,9 +119,11 @@ typedef struct lrpx_conv_desc {
     int in_chunked;       /* input stored in K-chunks of lrpx_conv_kc(hw,taps,cin) channels (see lrpx_maxpool2x2_relevance) */
     int bf16x6;           /* 1: contraction on the bf16 matrix cores with exact 3-way operand splits and the 6 leading
                              partial products (fp32 accuracy, 2.67x less matrix-pipe time); wpacked must come from
-                             lrpx_pack_weights_bf16x3; 3x3 convs, cin %% 16 == 0.  Epilogues: REL, FWD_DUAL (conv_bf16x6.h) and - round 6,
-                             on the conv_f16x3.h tiling - REL_MUL (x = the precomputed multiplicand; with pool_am the input is the
-                             relevance at the pool's output and is unpooled while staged).  No operand scales: in_amax / out1_amax unused.
+                             lrpx_pack_weights_bf16x3; 3x3 convs, cin %% 16 == 0.  Epilogues: REL (conv_bf16x6.h) and - round 6,
+                             on the conv_f16x3.h tiling - FWD_DUAL, GUIDED, bias-free PLAIN at hw <= 56 and REL_MUL (x = the precomputed
+                             multiplicand; with pool_am the input is the relevance at the pool's output and is unpooled while staged).
+                             FWD_DUAL needs oc_split %% 32 == 0 (a 32-channel block goes to out0 or to out1 as a whole; every VGG16
+                             layer): any other oc_split is LRPX_EINVAL.  No operand scales: in_amax / out1_amax unused.
                              taps = 1 (round 6): the (word, pixel) epsilon rules of the decoders (gridTDmodel.py:1125-1128, aoamodel.py:1135-1148)
                              in the same exact arithmetic - REL epilogue with x, map2img and ONE of out0 / out1 (+ zdiv), optional u;
                              cin %% 32 == 0, oc_split %% 4 == 0, 16-byte aligned operands, any number of rows (one kernel: a row's sum

@@ -100,32 +100,14 @@ inline int reserve_lds_once(LdsOnce& st, K kern, int bytes, const char* what) {
     return LRPX_OK;
 }
 
-// A/B switches of the shipped dispatch paths: ONE getenv pass per process, latched on first use, so that paired decisions
-// (LRPX_FIRST_VALU picks both the first-layer kernel and the chunk width its producer writes) cannot diverge.  Defaults are
-// what every number in DESIGN.md is measured with; the non-default values are exercised by tests/test_gpu_switches.py.
+// The two dispatch switches that tests use as seams (both values of each are reachable by descriptor anyway): ONE getenv pass per
+// process, latched on first use.  Every other former LRPX_* A/B switch is frozen at the value all measurements in DESIGN.md
+// were taken with (table in DESIGN.md, "Frozen runtime switches"); setting such a name in the environment changes nothing.
 struct Switches {
-    int wide;            // LRPX_WIDE (bit mask, default 7): 8-wave relevance kernels for 56/28 (1), 14 (2), pooled-input 56/28 (4)
-    int fwd_ksplit14;    // LRPX_FWD_KSPLIT (default 8): K ranges per tile of the 14x14 forward layers (1 = unsplit)
-    int fwd_ksplit28;    // LRPX_FWD_KSPLIT28 (default 1 = unsplit; 2 / 4 built and tested): ... of the 28x28 forward layers
-    int fwd_wide;        // LRPX_FWD_WIDE (bit mask, default 0): 8-wave forward kernels for 112 (1), 56 (2), 28 (4), K-split 14 (8)
-    int conv11_f16;      // LRPX_CONV11_F16 (default 1): conv1_1 of the forward trace on the f16x3 kernel; 0 = fp32 MFMA kernel
-    int first_valu;      // LRPX_FIRST_VALU: first-layer rule on the VALU kernel (and S from conv1_2 in 16-channel chunks)
-    int s21_nhwc;        // LRPX_S21_NHWC: S between conv2_2 and conv2_1 as NHWC instead of 16-channel chunks
-    int guided_poolbwd;  // LRPX_GUIDED_POOLBWD: image-gradient chain with pool-backward kernels
-    int dense_wide;      // LRPX_DENSE_WIDE (default 0): 256-row 8-wave tiles for the many-row dense f16x3 GEMM (1), 128-row tiles (0)
-    int dense_ks_rel;    // LRPX_DENSE_KS_REL: the few-row epsilon rule (the decoders' lock-steps in the exact modes) with K split over four waves (dense_ks_kernel)
     int dense_n256;      // LRPX_DENSE_N256 (default 1): 128 x 256 tiles with the waves side by side for the many-row dense f16x3 GEMM
-    int dense_rt;        // LRPX_DENSE_RT (default 0 = by the grid): row tiles per wave of that kernel, 4 (128-row tiles) or 3 (96-row tiles)
-    int dense_1wave;     // LRPX_DENSE_1WAVE: PLAIN few-row GEMMs without the 4-wave K split
-    int linear_valu;     // LRPX_LINEAR_VALU: the VALU skinny linear instead of the fp32-MFMA one
-    int b6_fwd_ksplit28; // LRPX_B6_FWD_KSPLIT28 (default 4): K ranges per tile of the 28x28 layers of the exact-split (conv mode 1) forward trace
-    int b6_fwd_ksplit56; // LRPX_B6_FWD_KSPLIT56 (default 2): ... of the 56x56 layers
-    int b6_wide;         // LRPX_B6_WIDE (bit mask): 8-wave conv-mode-1 relevance kernels for 56/28 (1), 14 (2), pooled-input 56/28 (4)
-    int b6_rel_ksplit14; // LRPX_B6_REL_KSPLIT14 (default 2; 1 = unsplit, 4 built): K ranges per tile of the 14x14 RELEVANCE layers of conv mode 1 (partial sums + rel_mul_finish)
     int b6_wino;         // LRPX_B6_WINO (bit mask, default 15): conv-mode-1 relevance convs that are not under a pool on the Winograd F(2x2,3x3) kernel
                          // (conv_wino_b6.h) at 56 x 56 (1), 28 x 28 (2), 14 x 14 (4); needs lrpx_conv_desc.wpacked_wino.  lrpx_set_b6_wino overrides it.
                          // 8: every staging thread fetches its whole patch (legacy staging); without it the outer columns come from the neighbouring lanes (same bits, not faster)
-    int x6_legacy;       // LRPX_X6_LEGACY: conv mode 1 on round 1's flow (conv_bf16x6.h with EPI_REL + pool kernels) instead of the fused B6 kernels
 };
 const Switches& switches();      // (lrpx_core.hip)
 int b6_wino_bits();              // switches().b6_wino unless lrpx_set_b6_wino moved it (lrpx_core.hip)

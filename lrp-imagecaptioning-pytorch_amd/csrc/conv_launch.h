@@ -50,16 +50,13 @@ int launch_conv_14_16_1_4_9_guided(const ConvArgs& a, hipStream_t s);
 int launch_conv_14_16_1_4_9_plain(const ConvArgs& a, hipStream_t s);
 int launch_conv_224_8_1_4_9_plain(const ConvArgs& a, hipStream_t s);       // Z+ / Z- of the alpha-beta rule at 224 x 224
 
+// round 1's exact-split kernels (conv_bf16x6.h): the EPI_REL relevance passes only; every other bf16x6 descriptor runs on the B6 kernels below
 int launch_x6_56_rel(const ConvArgs& a, hipStream_t s);
 int launch_x6_28_rel(const ConvArgs& a, hipStream_t s);
 int launch_x6_14_rel(const ConvArgs& a, hipStream_t s);
 int launch_x6_112_rel(const ConvArgs& a, hipStream_t s);
 int launch_x6_224_rel(const ConvArgs& a, hipStream_t s);
 int launch_x6_112n_rel(const ConvArgs& a, hipStream_t s);
-int launch_x6_112_fwd(const ConvArgs& a, hipStream_t s);
-int launch_x6_56_fwd(const ConvArgs& a, hipStream_t s);
-int launch_x6_28_fwd(const ConvArgs& a, hipStream_t s);
-int launch_x6_14_fwd(const ConvArgs& a, hipStream_t s);
 
 // conv mode 1 on the conv_f16x3.h tiling (B6: exact bf16 splits, six products) with the fused multiplicand (REL_MUL) and pooled-input staging
 int launch_b6_224_rel(const ConvArgs& a, hipStream_t s);
@@ -72,12 +69,6 @@ int launch_b6_224_pool(const ConvArgs& a, hipStream_t s);
 int launch_b6_112_pool(const ConvArgs& a, hipStream_t s);
 int launch_b6_56_pool(const ConvArgs& a, hipStream_t s);
 int launch_b6_28_pool(const ConvArgs& a, hipStream_t s);
-int launch_b6_56w_rel(const ConvArgs& a, hipStream_t s);       // ... 8-wave workgroups (LRPX_B6_WIDE)
-int launch_b6_28w_rel(const ConvArgs& a, hipStream_t s);
-int launch_b6_14w_rel(const ConvArgs& a, hipStream_t s);
-int launch_b6_56w_pool(const ConvArgs& a, hipStream_t s);
-int launch_b6_28w_pool(const ConvArgs& a, hipStream_t s);
-int launch_b6_112w_pool(const ConvArgs& a, hipStream_t s);
 int launch_b6_112n_guided(const ConvArgs& a, hipStream_t s);   // ... image-gradient chains (GUIDED: guided backprop / plain gradient)
 int launch_b6_56_guided(const ConvArgs& a, hipStream_t s);
 int launch_b6_28_guided(const ConvArgs& a, hipStream_t s);
@@ -145,10 +136,6 @@ int launch_h3_112_fwd(const ConvArgs& a, hipStream_t s);
 int launch_h3_56_fwd(const ConvArgs& a, hipStream_t s);
 int launch_h3_28_fwd(const ConvArgs& a, hipStream_t s);
 int launch_h3_14_fwd(const ConvArgs& a, hipStream_t s);
-int launch_h3_112w_fwd(const ConvArgs& a, hipStream_t s);   // ... 8-wave workgroups (A/B: LRPX_FWD_WIDE)
-int launch_h3_56w_fwd(const ConvArgs& a, hipStream_t s);
-int launch_h3_28w_fwd(const ConvArgs& a, hipStream_t s);
-int launch_h3_14w_plain(const ConvArgs& a, hipStream_t s);
 int launch_h3_224_guided(const ConvArgs& a, hipStream_t s);   // image-gradient chains (guided backprop / plain gradient)
 int launch_h3_112_guided(const ConvArgs& a, hipStream_t s);
 int launch_h3_56_guided(const ConvArgs& a, hipStream_t s);

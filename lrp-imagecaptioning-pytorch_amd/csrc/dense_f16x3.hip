@@ -25,22 +25,20 @@ constexpr int DH_BN = 128;
 #ifndef LRPXB_EXP
 #define LRPXB_EXP 0       // timing experiments (wrong results): 1 no epilogue, 2 no MFMAs, 4 no staging loads / commits, 8 no B loads
 #endif
-// WM wave rows x 2 wave columns; a wave owns 64 rows x 64 columns.  WM = 2: 128-row tiles, K chunks of 64, two workgroups per CU.
-// WM = 4 (many rows): 256-row tiles, 8 waves, K chunks of 32 (the two A buffers stay at 74 KB), one workgroup per CU - every B
-// fragment streamed from L2 now serves 256 rows: the 62 720 x 512 x 512 rule moved 1.0 GB of weights from L2 to the CUs with
-// 128-row tiles (1960 workgroups x 512 KB), the dominant term of its 186 us.
-template <int WM>
+// 2 wave rows x 2 wave columns; a wave owns 64 rows x 64 columns: 128-row tiles, K chunks of 64, two workgroups per CU.
+// (256-row tiles of 8 waves, one workgroup per CU, were built and measured slower for the many-row rules: DESIGN.md,
+// "Frozen runtime switches"; the 128 x 256 kernel below is what those rules run on.)
 struct DenseCfg {
-    static constexpr int NT = WM * 128, BM = WM * 64, KC = WM == 2 ? 64 : 32, KS = KC / 16, SEGS = KC / 4;
+    static constexpr int NT = 256, BM = 128, KC = 64, KS = KC / 16, SEGS = KC / 4;
     static constexpr int RP = NT / SEGS, NU = BM / RP;              // rows per staging pass, float4 items per thread and chunk
     static constexpr int ROWB = KS * 64 + 16;                       // LDS bytes per A row: [k-step][hi | lo][lane group 2][16 B] + pad
     static constexpr int BUF = BM * ROWB, LDS = 2 * BUF;
     static constexpr int CPI = 4 / KS;                              // chunks per loop iteration (4 k-steps: static B ring indices)
 };
 
-template <int EPI, int WM>      // EPI_REL, or EPI_PLAIN: out0 = acc + bias (optional ReLU) - the (T,V) scores of a trace
-__global__ __launch_bounds__(WM * 128, WM == 2 ? 2 : 1) void dense_f16x3_kernel(ConvArgs a, int m_tiles, int n_blocks) {
-    using C = DenseCfg<WM>;
+template <int EPI>      // EPI_REL, or EPI_PLAIN: out0 = acc + bias (optional ReLU) - the (T,V) scores of a trace
+__global__ __launch_bounds__(DenseCfg::NT, 2) void dense_f16x3_kernel(ConvArgs a, int m_tiles, int n_blocks) {
+    using C = DenseCfg;
     extern __shared__ __attribute__((aligned(16))) char ldsb[];
     const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, lh = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -967,7 +965,7 @@ int launch_dense_f16x3(const ConvArgs& a, hipStream_t stream) {
     LRPX_REQUIRE(plain || (long)a.n_maps * a.pix_per_map * a.oc_split < 0x7fffffffL, "dense_f16x3: too many multiplicand elements for 32-bit offsets");
     LRPX_REQUIRE(!(a.out1 && a.out1_amax) || a.pix_per_map >= 32, "dense_f16x3: out1_amax needs at least 32 rows per map");
     // 128 x 256 tiles, waves side by side: the default for many rows and at least 256 columns with ONE output (REL: out0, or out1
-    // with its denominator); LRPX_DENSE_N256=0 or anything else: the 128 x 128 kernel
+    // with its denominator); LRPX_DENSE_N256=0 (a test seam) or anything else: the 128 x 128 kernel
     const bool one_out = plain || (a.out1 ? (!a.out0 && a.Zdiv) : true);
     auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };      // (its epilogue moves 16 bytes per lane)
     const bool aligned = al16(a.X) && al16(a.U) && al16(a.Zdiv) && al16(a.out0) && al16(a.out1) && al16(a.bias);
@@ -977,7 +975,7 @@ int launch_dense_f16x3(const ConvArgs& a, hipStream_t stream) {
         // tile height: 128 rows, or 96 where that fills the 512 resident workgroup slots in fewer (rounds x rows) - e.g. 23 040 x 512
         // columns: 360 tiles of 128 rows leave 152 slots empty while the CUs that hold two run at half speed; 480 tiles of 96 rows do not
         auto cost = [&](int rows) { return ceil_div(ceil_div(M, rows) * n_blocks, 512) * rows; };
-        const int rt = switches().dense_rt == 3 || switches().dense_rt == 4 ? switches().dense_rt : (cost(96) < cost(128) ? 3 : 4);
+        const int rt = cost(96) < cost(128) ? 3 : 4;
         const long m_tiles = ceil_div(M, 32 * rt);
         const long grid = ceil_div(m_tiles * n_blocks, 8) * 8;
         LRPX_REQUIRE(grid > 0 && grid <= 0x7fffffffL, "dense_f16x3: grid %ld out of range", grid);
@@ -996,23 +994,15 @@ int launch_dense_f16x3(const ConvArgs& a, hipStream_t stream) {
         hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), DnCfg<false>::LDS, stream, a, (int)m_tiles, n_blocks);
         return check_launch("dense_f16x3_n256");
     }
-    const bool wide = switches().dense_wide && M >= 8192;      // 256-row tiles (8 waves) for many rows: measured slower, off (A/B)
-    const long m_tiles = ceil_div(M, wide ? 256 : 128);
+    const long m_tiles = ceil_div(M, DenseCfg::BM);
     const int n_blocks = (int)ceil_div(a.n_oc, DH_BN);
     const long total = m_tiles * n_blocks;
     const long grid = ceil_div(total, 8) * 8;
     LRPX_REQUIRE(grid > 0 && grid <= 0x7fffffffL, "dense_f16x3: grid %ld out of range", grid);
-    static LdsOnce attr_once[4];
-    const int which = (plain ? 2 : 0) + (wide ? 1 : 0);
-    if (wide) {
-        auto kern = plain ? dense_f16x3_kernel<EPI_PLAIN, 4> : dense_f16x3_kernel<EPI_REL, 4>;
-        LRPX_TRY(reserve_lds_once(attr_once[which], kern, DenseCfg<4>::LDS, "dense_f16x3"));
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), DenseCfg<4>::LDS, stream, a, (int)m_tiles, n_blocks);
-    } else {
-        auto kern = plain ? dense_f16x3_kernel<EPI_PLAIN, 2> : dense_f16x3_kernel<EPI_REL, 2>;
-        LRPX_TRY(reserve_lds_once(attr_once[which], kern, DenseCfg<2>::LDS, "dense_f16x3"));
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), DenseCfg<2>::LDS, stream, a, (int)m_tiles, n_blocks);
-    }
+    static LdsOnce attr_once[2];
+    auto kern = plain ? dense_f16x3_kernel<EPI_PLAIN> : dense_f16x3_kernel<EPI_REL>;
+    LRPX_TRY(reserve_lds_once(attr_once[plain], kern, DenseCfg::LDS, "dense_f16x3"));
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(DenseCfg::NT), DenseCfg::LDS, stream, a, (int)m_tiles, n_blocks);
     return check_launch("dense_f16x3");
 }
 
@@ -1031,7 +1021,7 @@ int launch_dense_bf16x6(const ConvArgs& a, hipStream_t stream) {
     LRPX_REQUIRE(!a.out1_amax || a.pix_per_map >= 32, "dense_bf16x6: out1_amax needs at least 32 rows per map");
     const int n_blocks = (int)ceil_div(a.n_oc, DN_BN);
     auto cost = [&](int rows) { return ceil_div(ceil_div(M, rows) * n_blocks, 512) * rows; };
-    const int rt = switches().dense_rt == 3 || switches().dense_rt == 4 ? switches().dense_rt : (cost(96) < cost(128) ? 3 : 4);
+    const int rt = cost(96) < cost(128) ? 3 : 4;
     const long m_tiles = ceil_div(M, 32 * rt);
     const long grid = ceil_div(m_tiles * n_blocks, 8) * 8;
     LRPX_REQUIRE(grid > 0 && grid <= 0x7fffffffL, "dense_bf16x6: grid %ld out of range", grid);

@@ -217,8 +217,8 @@ __global__ __launch_bounds__(256, 2) void dense_slab_kernel(ConvArgs a, int m_ti
 // The plain GEMM with the K loop of a tile split over four waves (the decoders' image-gradient BPTT: 640 rows x K = 2048:
 // 137 us as 80 x 4 waves with 1024 dependent fp32 MFMAs each).  Workgroup = 16 waves = 4 column blocks x 4 K quarters over
 // the same 32 x K slab of A; the four partial tiles of a column block meet in LDS and are summed in K order
-// (deterministic).  Round 6: also the epsilon rule of the decoders' lock-steps in the exact modes (REL epilogue; LRPX_DENSE_KS_REL=0:
-// the one-wave kernel above) - 20 -> 12 us per lock-step GEMM, the one-image drop-in's decoder relevance 1.14 -> 0.97 ms.  (Rounds 3 - 5
+// (deterministic).  Round 6: also the epsilon rule of the decoders' lock-steps in the exact modes (REL epilogue) - against the
+// one-wave kernel above 20 -> 12 us per lock-step GEMM, the one-image drop-in's decoder relevance 1.14 -> 0.97 ms.  (Rounds 3 - 5
 // kept the rule on the one-wave kernel because this order moved ONE T = 20 word relevance of the LRP goldens above its 1e-5 bound; with
 // the round-6 K loop of the trace linears - lrpx_decoder.hip, linear_mfma_core - the worst row sits at 9.2e-6 in this order, 9.9e-6 in
 // the other: the row is carried by the encoder features' own 1.8e-6, tests/diag_t20_words.py.)
@@ -388,19 +388,16 @@ static int launch_dense_small_t(const ConvArgs& a, hipStream_t stream) {
     const int m_tiles = (int)ceil_div(rows, 32);
     const int n_blocks = (int)ceil_div(a.n_oc, 128);
     const int lds = 32 * ((a.cin < 1024 ? a.cin : 1024) + 4) * (int)sizeof(float);
-    const int dense_ks = switches().dense_1wave ? 0 : 1;      // (A/B switch)
-    {
-        if (dense_ks && a.cin >= 512 && (EPI == EPI_PLAIN || switches().dense_ks_rel)) {
-            // K split over four waves per column block (16-wave workgroups)
-            constexpr int RED = 16 * 32 * 33 * (int)sizeof(float);
-            const int lds_ks = lds > RED ? lds : RED;
-            constexpr int LDS_KS_MAX = 32 * (1024 + 4) * (int)sizeof(float);
-            static LdsOnce once_ks;
-            LRPX_TRY(reserve_lds_once(once_ks, dense_ks_kernel<EPI>, LDS_KS_MAX, "dense_ks"));
-            hipLaunchKernelGGL(dense_ks_kernel<EPI>, dim3((unsigned)(m_tiles * n_blocks)), dim3(1024), lds_ks, stream, a, m_tiles,
-                               n_blocks, AoaStepFuse{});
-            return check_launch("dense_ks");
-        }
+    if (a.cin >= 512) {
+        // K split over four waves per column block (16-wave workgroups)
+        constexpr int RED = 16 * 32 * 33 * (int)sizeof(float);
+        const int lds_ks = lds > RED ? lds : RED;
+        constexpr int LDS_KS_MAX = 32 * (1024 + 4) * (int)sizeof(float);
+        static LdsOnce once_ks;
+        LRPX_TRY(reserve_lds_once(once_ks, dense_ks_kernel<EPI>, LDS_KS_MAX, "dense_ks"));
+        hipLaunchKernelGGL(dense_ks_kernel<EPI>, dim3((unsigned)(m_tiles * n_blocks)), dim3(1024), lds_ks, stream, a, m_tiles,
+                           n_blocks, AoaStepFuse{});
+        return check_launch("dense_ks");
     }
     const bool slabs = a.cin > 1024;
     auto kern = slabs ? dense_slab_kernel<EPI> : dense_small_kernel<EPI>;

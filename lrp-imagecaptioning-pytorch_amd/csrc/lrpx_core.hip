@@ -58,28 +58,9 @@ int check_dev_ptrs(const char* fn, std::initializer_list<PtrArg> args) {
 const Switches& switches() {
     static const Switches sw = [] {
         auto num = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
-        auto set = [](const char* name) { return getenv(name) ? 1 : 0; };
         Switches w;
-        w.wide = num("LRPX_WIDE", 7);
-        w.fwd_ksplit14 = num("LRPX_FWD_KSPLIT", 8);
-        w.fwd_ksplit28 = num("LRPX_FWD_KSPLIT28", 1);
-        w.fwd_wide = num("LRPX_FWD_WIDE", 0);
-        w.conv11_f16 = num("LRPX_CONV11_F16", 1);
-        w.first_valu = set("LRPX_FIRST_VALU");
-        w.s21_nhwc = set("LRPX_S21_NHWC");
-        w.guided_poolbwd = set("LRPX_GUIDED_POOLBWD");
-        w.dense_wide = num("LRPX_DENSE_WIDE", 0);
-        w.dense_ks_rel = num("LRPX_DENSE_KS_REL", 1);
         w.dense_n256 = num("LRPX_DENSE_N256", 1);
-        w.dense_rt = num("LRPX_DENSE_RT", 0);
-        w.dense_1wave = set("LRPX_DENSE_1WAVE");
-        w.linear_valu = set("LRPX_LINEAR_VALU");
-        w.x6_legacy = set("LRPX_X6_LEGACY");
-        w.b6_wide = num("LRPX_B6_WIDE", 0);
-        w.b6_rel_ksplit14 = num("LRPX_B6_REL_KSPLIT14", 2);
         w.b6_wino = num("LRPX_B6_WINO", 15) & 15;
-        w.b6_fwd_ksplit28 = num("LRPX_B6_FWD_KSPLIT28", 4);
-        w.b6_fwd_ksplit56 = num("LRPX_B6_FWD_KSPLIT56", 2);
         return w;
     }();
     return sw;
@@ -1454,7 +1435,7 @@ int fwd_dual_finish(const float* part, int nsplit, const float* bias, float* act
     return check_launch("fwd_dual_finish");
 }
 // out[m][i] = x[img(m)][i] * (sum over the K splits of part[s][m][i]), pairwise in a fixed order (as fwd_dual_finish): the REL_MUL epilogue
-// of a K-split relevance conv (lrpx_vgg16_relevance_ex, LRPX_B6_REL_KSPLIT14)
+// of a K-split relevance conv (lrpx_vgg16_relevance_ex: the 14 x 14 layers of conv mode 1)
 __global__ void rel_mul_finish_kernel(const float* __restrict__ part, int nsplit, long split_stride, const float* __restrict__ x,
                                       const int* __restrict__ map2img, float* __restrict__ out, long per_map4, long total4) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;

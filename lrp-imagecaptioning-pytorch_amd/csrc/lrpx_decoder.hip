@@ -1477,8 +1477,7 @@ int lrpx_linear_small(const float* x, long ldx, const float* w, const float* bia
                       int N, int act, void* stream) {
     LRPX_CHECK_PTRS_OPT("lrpx_linear_small", {x, "x"}, {w, "w"}, {bias, "bias"}, {out, "out"});
     LRPX_REQUIRE(x && w && out && B > 0 && N > 0 && K > 0 && K % 4 == 0 && ldx % 4 == 0, "linear_small: bad arguments");
-    const int lin_valu = switches().linear_valu;     // (A/B switch)
-    if (K % 16 == 0 && B <= 64 && !lin_valu) {
+    if (K % 16 == 0 && B <= 64) {
         const dim3 grid((N + 15) / 16);
         hipStream_t st = (hipStream_t)stream;
         if (B <= 16) hipLaunchKernelGGL((linear_mfma_kernel<1>), grid, dim3(256), 0, st, x, ldx, w, bias, out, ldo, B, K, N, act);

@@ -104,7 +104,6 @@ int conv_dispatch(const lrpx_conv_desc* d, hipStream_t s, int f16_ksplit) {
         } else {
             LRPX_REQUIRE(d->blocked == 0, "conv_mfma: only the f16x3 = 2 REL_MUL kernels take the blocked layout");
         }
-        const int wide_g = switches().wide;
         if (d->f16x3 == 2 && d->epi == EPI_GUIDED && d->pool_am) {
             LRPX_REQUIRE((long)d->n_maps * (d->hw / 2) * (d->hw / 2) * d->cin < 0x7fffffffL,
                          "conv_mfma: too many (image, pooled pixel, channel) elements for the pooled-input kernel");
@@ -115,9 +114,9 @@ int conv_dispatch(const lrpx_conv_desc* d, hipStream_t s, int f16_ksplit) {
             LRPX_REQUIRE(false, "conv_mfma: no pooled-input f16+f8 GUIDED kernel built for hw=%d n_oc=%d", d->hw, d->n_oc);
         }
         if (d->f16x3 == 2 && d->epi == EPI_GUIDED) {
-            if ((wide_g & 1) && d->n_oc >= 256 && d->hw == 56) return launch_h8_56w_guided(a, s);
-            if ((wide_g & 1) && d->n_oc >= 256 && d->hw == 28) return launch_h8_28w_guided(a, s);
-            if ((wide_g & 2) && d->n_oc >= 256 && d->hw == 14) return launch_h8_14w_guided(a, s);
+            if (d->n_oc >= 256 && d->hw == 56) return launch_h8_56w_guided(a, s);
+            if (d->n_oc >= 256 && d->hw == 28) return launch_h8_28w_guided(a, s);
+            if (d->n_oc >= 256 && d->hw == 14) return launch_h8_14w_guided(a, s);
             if (d->hw == 224 && d->n_oc <= 64) return launch_h8_224_guided(a, s);
             if (d->hw == 112 && d->n_oc > 64) return launch_h8_112_guided(a, s);
             if (d->hw == 112) return launch_h8_112n_guided(a, s);
@@ -127,8 +126,8 @@ int conv_dispatch(const lrpx_conv_desc* d, hipStream_t s, int f16_ksplit) {
             LRPX_REQUIRE(false, "conv_mfma: no f16+f8 GUIDED kernel built for hw=%d n_oc=%d", d->hw, d->n_oc);
         }
         if (d->f16x3 == 2 && d->epi == EPI_PLAIN) {
-            if ((wide_g & 1) && d->n_oc >= 256 && d->hw == 28) return launch_h8_28w_plain(a, s);
-            if ((wide_g & 2) && d->n_oc >= 256 && d->hw == 14) return launch_h8_14w_plain(a, s);
+            if (d->n_oc >= 256 && d->hw == 28) return launch_h8_28w_plain(a, s);
+            if (d->n_oc >= 256 && d->hw == 14) return launch_h8_14w_plain(a, s);
             if (d->hw == 112 && d->n_oc <= 64) return launch_h8_112n_plain(a, s);
             if (d->hw == 56) return launch_h8_56_plain(a, s);
             if (d->hw == 28) return launch_h8_28_plain(a, s);
@@ -144,7 +143,6 @@ int conv_dispatch(const lrpx_conv_desc* d, hipStream_t s, int f16_ksplit) {
             LRPX_REQUIRE(false, "conv_mfma: no f16x3 GUIDED kernel built for hw=%d n_oc=%d", d->hw, d->n_oc);
         }
         if (d->epi == EPI_PLAIN) {
-            if ((switches().fwd_wide & 8) && d->hw == 14 && d->n_oc >= 256 && a.ksplit > 1) return launch_h3_14w_plain(a, s);
             if (d->hw == 112 && d->n_oc <= 64) return launch_h3_112n_plain(a, s);
             if (d->hw == 56) return launch_h3_56_plain(a, s);
             if (d->hw == 28) return launch_h3_28_plain(a, s);
@@ -152,10 +150,6 @@ int conv_dispatch(const lrpx_conv_desc* d, hipStream_t s, int f16_ksplit) {
             LRPX_REQUIRE(false, "conv_mfma: no f16x3 PLAIN kernel built for hw=%d n_oc=%d", d->hw, d->n_oc);
         }
         if (d->epi == EPI_FWD_DUAL) {
-            const int fw = switches().fwd_wide;
-            if ((fw & 1) && d->hw == 112 && d->n_oc >= 256) return launch_h3_112w_fwd(a, s);
-            if ((fw & 2) && d->hw == 56 && d->n_oc >= 256) return launch_h3_56w_fwd(a, s);
-            if ((fw & 4) && d->hw == 28 && d->n_oc >= 256) return launch_h3_28w_fwd(a, s);
             if (d->hw == 224) return launch_h3_224_fwd(a, s);
             if (d->hw == 112) return launch_h3_112_fwd(a, s);
             if (d->hw == 56) return launch_h3_56_fwd(a, s);
@@ -169,9 +163,8 @@ int conv_dispatch(const lrpx_conv_desc* d, hipStream_t s, int f16_ksplit) {
             LRPX_REQUIRE((long)d->n_maps * (d->hw / 2) * (d->hw / 2) * d->cin < 0x7fffffffL,
                          "conv_mfma: too many (image, pooled pixel, channel) elements for the pooled-input kernel");
             if (f8) {
-                const int widep = switches().wide;
-                if ((widep & 4) && d->hw == 56 && d->n_oc >= 256) return launch_h8_56w_pool(a, s);
-                if ((widep & 4) && d->hw == 28 && d->n_oc >= 256) return launch_h8_28w_pool(a, s);
+                if (d->hw == 56 && d->n_oc >= 256) return launch_h8_56w_pool(a, s);
+                if (d->hw == 28 && d->n_oc >= 256) return launch_h8_28w_pool(a, s);
                 if (d->hw == 224 && d->n_oc <= 64) return launch_h8_224_pool(a, s);
                 if (d->hw == 112 && d->n_oc > 64) return launch_h8_112_pool(a, s);
                 if (d->hw == 56) return launch_h8_56_pool(a, s);
@@ -188,11 +181,10 @@ int conv_dispatch(const lrpx_conv_desc* d, hipStream_t s, int f16_ksplit) {
             // 256 output channels and more: 8-wave workgroups (256 channels per workgroup, ONE workgroup per CU).  The chain
             // alone is as fast as with two 4-wave workgroups per CU (20.9 ms either way), but the step with batches in
             // flight is 2 % faster (12 410 -> 12 690 maps/s sustained, tools/ab_bench.sh): one double-buffered tile per CU
-            // instead of two leaves LDS for the other batches' kernels.  LRPX_WIDE=0 switches back (A/B only).
-            const int wide = switches().wide;
-            if ((wide & 1) && d->n_oc >= 256 && d->hw == 56) return launch_h8_56w_rel(a, s);
-            if ((wide & 1) && d->n_oc >= 256 && d->hw == 28) return launch_h8_28w_rel(a, s);
-            if ((wide & 2) && d->n_oc >= 256 && d->hw == 14) return launch_h8_14w_rel(a, s);
+            // instead of two leaves LDS for the other batches' kernels.
+            if (d->n_oc >= 256 && d->hw == 56) return launch_h8_56w_rel(a, s);
+            if (d->n_oc >= 256 && d->hw == 28) return launch_h8_28w_rel(a, s);
+            if (d->n_oc >= 256 && d->hw == 14) return launch_h8_14w_rel(a, s);
             if (d->hw == 224) return launch_h8_224_rel(a, s);
             if (d->hw == 112) return d->n_oc <= 64 ? launch_h8_112n_rel(a, s) : launch_h8_112_rel(a, s);
             if (d->hw == 56) return launch_h8_56_rel(a, s);
@@ -238,10 +230,6 @@ int conv_dispatch(const lrpx_conv_desc* d, hipStream_t s, int f16_ksplit) {
             // the conv sits under a 2x2 max-pool: `in` at the pool's output resolution, unpooled while staged (conv_f16x3.h, POOL + B6)
             LRPX_REQUIRE((long)d->n_maps * (d->hw / 2) * (d->hw / 2) * d->cin < 0x7fffffffL,
                          "conv_mfma: too many (image, pooled pixel, channel) elements for the pooled-input kernel");
-            const int b6w = switches().b6_wide;
-            if ((b6w & 4) && d->hw == 56 && d->n_oc >= 256) return launch_b6_56w_pool(a, s);
-            if ((b6w & 4) && d->hw == 28 && d->n_oc >= 256) return launch_b6_28w_pool(a, s);
-            if ((b6w & 8) && d->hw == 112 && d->n_oc > 64 && d->n_oc <= 128) return launch_b6_112w_pool(a, s);
             if (d->hw == 224 && d->n_oc <= 64) return launch_b6_224_pool(a, s);
             if (d->hw == 112 && d->n_oc > 64) return launch_b6_112_pool(a, s);
             if (d->hw == 56) return launch_b6_56_pool(a, s);
@@ -257,10 +245,6 @@ int conv_dispatch(const lrpx_conv_desc* d, hipStream_t s, int f16_ksplit) {
             return launch_b6_14_wino(a, s);
         }
         if (d->epi == EPI_REL_MUL) {
-            const int b6w = switches().b6_wide;
-            if ((b6w & 1) && d->n_oc >= 256 && d->hw == 56) return launch_b6_56w_rel(a, s);
-            if ((b6w & 1) && d->n_oc >= 256 && d->hw == 28) return launch_b6_28w_rel(a, s);
-            if ((b6w & 2) && d->n_oc >= 256 && d->hw == 14) return launch_b6_14w_rel(a, s);
             if (d->hw == 224 && d->n_oc <= 64) return launch_b6_224_rel(a, s);
             if (d->hw == 112) return d->n_oc <= 64 ? launch_b6_112n_rel(a, s) : launch_b6_112_rel(a, s);
             if (d->hw == 56) return launch_b6_56_rel(a, s);
@@ -275,18 +259,14 @@ int conv_dispatch(const lrpx_conv_desc* d, hipStream_t s, int f16_ksplit) {
             if (d->hw == 28) return launch_x6_28_rel(a, s);
             if (d->hw == 14) return launch_x6_14_rel(a, s);
         }
-        if (d->epi == EPI_FWD_DUAL && !switches().x6_legacy && (d->oc_split & 31) == 0) {
+        if (d->epi == EPI_FWD_DUAL) {
+            // (the act | Z+ halves of a tile's 32-channel output blocks must not straddle oc_split)
+            LRPX_REQUIRE(d->oc_split % 32 == 0, "conv_mfma: the bf16x6 FWD_DUAL kernels need oc_split %% 32 == 0 (oc_split=%d)", d->oc_split);
             if (d->hw == 224) return launch_b6_224_fwd(a, s);
             if (d->hw == 112) return launch_b6_112_fwd(a, s);
             if (d->hw == 56) return launch_b6_56_fwd(a, s);
             if (d->hw == 28) return launch_b6_28_fwd(a, s);
             if (d->hw == 14) return launch_b6_14_fwd(a, s);
-        }
-        if (d->epi == EPI_FWD_DUAL) {
-            if (d->hw == 112) return launch_x6_112_fwd(a, s);
-            if (d->hw == 56) return launch_x6_56_fwd(a, s);
-            if (d->hw == 28) return launch_x6_28_fwd(a, s);
-            if (d->hw == 14) return launch_x6_14_fwd(a, s);
         }
         LRPX_REQUIRE(false, "conv_mfma: no bf16x6 kernel built for hw=%d epi=%d", d->hw, d->epi);
     }
@@ -336,7 +316,7 @@ int conv_dispatch(const lrpx_conv_desc* d, hipStream_t s, int f16_ksplit) {
 // VGG16 geometry (cfg 'D' without the last pool)
 // ------------------------------------------------------------------------------------------------
 struct VggLayer { int conv; int hw; int cin; int cout; };   // conv: 1 conv3x3, 0 maxpool; hw = input size
-static const VggLayer kVgg[17] = {
+static constexpr VggLayer kVgg[17] = {
     {1, 224, 3, 64},   {1, 224, 64, 64},   {0, 224, 64, 64},
     {1, 112, 64, 128}, {1, 112, 128, 128}, {0, 112, 128, 128},
     {1, 56, 128, 256}, {1, 56, 256, 256},  {1, 56, 256, 256}, {0, 56, 256, 256},
@@ -344,6 +324,36 @@ static const VggLayer kVgg[17] = {
     {1, 14, 512, 512}, {1, 14, 512, 512},  {1, 14, 512, 512}};
 static const int kNL = 17;
 static inline int cin_pad(int l) { return l == 0 ? 8 : kVgg[l].cin; }   // image is kept NHWC with 8 channels
+
+// K ranges per tile of a forward-trace conv on the split-product kernels: a property of the LAYER (its map size) and of the
+// arithmetic, never of the batch size - an image gets the same activations, pool winners and maps whatever batch it sits in
+// (test_forward_features_vs_fp64_...).
+//  * 14 x 14, both arithmetics: 8.  The grid fills the chip: 16 images are 112 workgroups of 32 K-chunks each (207 -> 112 + 45 us
+//    per layer); an accumulator carries 36 k-steps instead of 288.  A chain of N MFMA accumulations rounds like a sequential
+//    fp32 sum (tools/micro/mfma_round.hip, profiles/r03_mfma_round.txt: rms 3.6e-7 of the result at N = 288, 6.5e-8 in 8
+//    blocks): f16x3 features 2.9e-6 -> 2.0e-6 of their maximum from an fp64 forward.
+//  * f16x3, 28 x 28: unsplit.  Four ranges give features 1.6e-6 from fp64, but their partial sums are 4 x 51 MB per layer and 16
+//    images: +0.3 ms per forward pass for a gain that no parity test can see (the AoA r_words rows sit at 1.0 - 1.2 of the
+//    reference's own fp64 distance either way, bound 3).
+//  * exact bf16 splits (bf16x6), 28 x 28: 4 and 56 x 56: 2.  An accumulator of this kernel is rounded six times per k-step (six
+//    MFMAs), against three on the fp16 split products: unsplit, the exact-split forward sits 2.7e-6 of the feature maximum from
+//    an fp64 evaluation where the fp16 forward sits at 2.1e-6 and oneDNN at 7.6e-7 (tools/dbg/fwd_f64_probe.py), and one
+//    well-conditioned r_words row of the T = 20 fixture left the 1e-5 bound (1.6e-5).  Partial sums over <= 72 k-steps, added
+//    pairwise by fwd_dual_finish; +0.5 ms per 16 images.
+static constexpr int fwd_ksplit(bool f16x3, bool bf16x6, int hw) {
+    if (!f16x3 && !bf16x6) return 1;
+    return hw == 14 ? 8 : (f16x3 ? 1 : (hw == 28 ? 4 : (hw == 56 ? 2 : 1)));
+}
+// every split divides the layer's K-chunks, and its partial sums fit the scratch region of the trace (xz[1]: 224 x 224 x 64 per image)
+static constexpr bool fwd_ksplit_fits() {
+    for (int l = 1; l < kNL; ++l)
+        for (int f16 = 0; f16 < 2; ++f16) {
+            const int ks = fwd_ksplit(f16, !f16, kVgg[l].hw);
+            if (kVgg[l].conv && ks > 1 && ((kVgg[l].cin / 16) % ks != 0 || (long)ks * kVgg[l].hw * kVgg[l].hw * 2 * kVgg[l].cout > 224L * 224 * 64)) return false;
+        }
+    return true;
+}
+static_assert(fwd_ksplit_fits(), "forward K split: ranges must divide cin / 16 and the partial sums must fit the trace's scratch region");
 
 int first_layer_pack(const float* w, float* w6, int cout, int plain, hipStream_t s);
 int first_layer_relevance(const float* S, const float* w6, const float* X8, const int* map2img, float* out, int n_maps,
@@ -795,63 +805,34 @@ int lrpx_vgg16_forward_ex(const void* packed, const float* img_nchw, int n_img, 
                 // (the maximum of act[1] is recorded by conv1_1's epilogue below: l == 0)
                 d.f16x3 = 1; d.wpacked = pk + p.fwdh[l];
                 d.in_amax = fam + (size_t)in_l * n_img; d.out0_amax = fam + (size_t)(l + 1) * n_img;
-                // The 14x14 layers run K-SPLIT: blockIdx.y takes one of 8 contiguous K ranges per tile through the PLAIN epilogue
-                // (partial sums behind each other in the xz[1] region of the trace - SCRATCH during the forward pass:
-                // lrpx_vgg16_trace_derive below rewrites it after the last layer), then one pass adds the splits pairwise in a
-                // fixed order, applies bias / ReLU and records the per-image maximum: what the FWD_DUAL epilogue does.
-                //  * the grid fills the chip: 16 images are 112 workgroups of 32 K-chunks each (207 -> 112 + 45 us per layer);
-                //  * accuracy: an accumulator carries 36 k-steps instead of 288.  A chain of N MFMA accumulations rounds like a
-                //    sequential fp32 sum (tools/micro/mfma_round.hip, profiles/r03_mfma_round.txt: rms 3.6e-7 of the result at
-                //    N = 288, 6.5e-8 in 8 blocks): features 2.9e-6 -> 2.0e-6 of their maximum from an fp64 forward;
-                //  * the decision depends on the LAYER only, never on the batch size: an image gets the same activations,
-                //    pool winners and maps whatever batch it sits in (test_forward_features_vs_fp64_...).
-                // The 28x28 layers can split too (LRPX_FWD_KSPLIT28=4: features 1.6e-6 from fp64), but their partial sums are 4 x
-                // 51 MB per layer and 16 images: +0.3 ms per forward pass for a gain that no parity test can see (the AoA
-                // r_words rows sit at 1.0 - 1.2 of the reference's own fp64 distance either way, bound 3) - off by default.
-                const int fwd_ks = L.hw == 14 ? switches().fwd_ksplit14 : (L.hw == 28 ? switches().fwd_ksplit28 : 1);
-                if (fwd_ks > 1 && (fwd_ks & (fwd_ks - 1)) == 0 && fwd_ks <= 16 && (L.cin / 16) % fwd_ks == 0 &&
-                    (size_t)fwd_ks * L.hw * L.hw * 2 * L.cout <= (size_t)224 * 224 * 64) {
-                    float* part = tr + t.xz[1];
-                    d.epi = EPI_PLAIN; d.bias = nullptr; d.oc_split = 2 * L.cout;
-                    d.out0 = part; d.out1 = nullptr; d.out0_amax = nullptr;
-                    LRPX_TRY(conv_dispatch(&d, (hipStream_t)stream, fwd_ks));
-                    LRPX_TRY(fwd_dual_finish(part, fwd_ks, pk + p.bias[l], tr + t.act[l + 1], tr + t.zpos[l], n_img,
-                                             (long)L.hw * L.hw, L.cout, fam + (size_t)(l + 1) * n_img, (hipStream_t)stream));
-                    continue;
-                }
-            } else if (use_bf16x6 && (L.hw <= 112 || (l > 0 && !switches().x6_legacy))) {
-                // mode 1: exact bf16 splits (round 6: conv1_2 too, and the 14 x 14 layers K-split as in the f16x3 forward - the decision
-                // depends on the layer only, never on the batch)
+            } else if (use_bf16x6 && l > 0) {
+                // mode 1: exact bf16 splits (round 6: conv1_2 too)
                 d.bf16x6 = 1; d.wpacked = pk + p.fwd6[l];
-                // K ranges per tile (a property of the LAYER, never of the batch).  An accumulator of this kernel is rounded six times per
-                // k-step (six MFMAs), against three on the fp16 split products: unsplit, the exact-split forward sits 2.7e-6 of the feature
-                // maximum from an fp64 evaluation where the fp16 forward sits at 2.1e-6 and oneDNN at 7.6e-7 (tools/dbg/fwd_f64_probe.py), and one
-                // well-conditioned r_words row of the T = 20 fixture left the 1e-5 bound (1.6e-5).  Partial sums over <= 72 k-steps, added
-                // pairwise by lrpx fwd_dual_finish: LRPX_B6_FWD_KSPLIT28 (4) / 56 (2); +0.5 ms per 16 images.
-                const int fwd_ks = switches().x6_legacy ? 1 : (L.hw == 14 ? switches().fwd_ksplit14 : (L.hw == 28 ? switches().b6_fwd_ksplit28 : (L.hw == 56 ? switches().b6_fwd_ksplit56 : 1)));
-                if (fwd_ks > 1 && (fwd_ks & (fwd_ks - 1)) == 0 && fwd_ks <= 16 && (L.cin / 16) % fwd_ks == 0 &&
-                    (size_t)fwd_ks * L.hw * L.hw * 2 * L.cout <= (size_t)224 * 224 * 64) {
-                    float* part = tr + t.xz[1];
-                    d.epi = EPI_PLAIN; d.bias = nullptr; d.oc_split = 2 * L.cout;
-                    d.out0 = part; d.out1 = nullptr;
-                    LRPX_TRY(conv_dispatch(&d, (hipStream_t)stream, fwd_ks));
-                    LRPX_TRY(fwd_dual_finish(part, fwd_ks, pk + p.bias[l], tr + t.act[l + 1], tr + t.zpos[l], n_img,
-                                             (long)L.hw * L.hw, L.cout, nullptr, (hipStream_t)stream));
-                    continue;
-                }
-            }
-            if (fwd_f16 && mode >= 2 && l == 0) {
+            } else if (fwd_f16 && mode >= 2) {
+                // conv1_1 on the fp16 matrix cores too (the fp32 MFMA kernel: 0.67 ms per 16 images for 15 GFLOP and 0.4 GB -
+                // neither its matrix nor its memory time): the signed image [x+ | x- | 0] padded to one 16-channel
+                // K-chunk (51 MB per 16 images, in the scratch region of the trace), scale = max|pixel| per image
                 unsigned* fam = reinterpret_cast<unsigned*>(tr + t.famax);
+                float* img16 = tr + t.xz[1];
+                LRPX_TRY(lrpx_nchw_to_nhwc_posneg(img_nchw, img16, n_img, 3, 224 * 224, 16, stream));
+                LRPX_TRY(lrpx_amax_maps(img16, n_img, (long)224 * 224 * 16, fam, stream));
+                d.in = img16; d.cin = 16; d.f16x3 = 1; d.wpacked = pk + p.fwdh0; d.in_amax = fam;
                 d.out0_amax = fam + (size_t)1 * n_img;       // per-image maximum of the activations: conv1_2's fp16 scale
-                if (switches().conv11_f16) {
-                    // conv1_1 on the fp16 matrix cores too (the fp32 MFMA kernel: 0.67 ms per 16 images for 15 GFLOP and 0.4 GB -
-                    // neither its matrix nor its memory time): the signed image [x+ | x- | 0] padded to one 16-channel
-                    // K-chunk (51 MB per 16 images, in the scratch region of the trace), scale = max|pixel| per image
-                    float* img16 = tr + t.xz[1];
-                    LRPX_TRY(lrpx_nchw_to_nhwc_posneg(img_nchw, img16, n_img, 3, 224 * 224, 16, stream));
-                    LRPX_TRY(lrpx_amax_maps(img16, n_img, (long)224 * 224 * 16, fam, stream));
-                    d.in = img16; d.cin = 16; d.f16x3 = 1; d.wpacked = pk + p.fwdh0; d.in_amax = fam;
-                }
+            }
+            const int fwd_ks = fwd_ksplit(d.f16x3, d.bf16x6, L.hw);
+            if (fwd_ks > 1) {
+                // K-SPLIT: blockIdx.y takes one of fwd_ks contiguous K ranges per tile through the PLAIN epilogue (partial sums behind
+                // each other in the xz[1] region of the trace - SCRATCH during the forward pass: lrpx_vgg16_trace_derive below
+                // rewrites it after the last layer), then one pass adds the splits pairwise in a fixed order, applies bias / ReLU
+                // and (f16x3) records the per-image maximum: what the FWD_DUAL epilogue does.
+                float* part = tr + t.xz[1];
+                unsigned* act_amax = d.out0_amax;
+                d.epi = EPI_PLAIN; d.bias = nullptr; d.oc_split = 2 * L.cout;
+                d.out0 = part; d.out1 = nullptr; d.out0_amax = nullptr;
+                LRPX_TRY(conv_dispatch(&d, (hipStream_t)stream, fwd_ks));
+                LRPX_TRY(fwd_dual_finish(part, fwd_ks, pk + p.bias[l], tr + t.act[l + 1], tr + t.zpos[l], n_img,
+                                         (long)L.hw * L.hw, L.cout, act_amax, (hipStream_t)stream));
+                continue;
             }
             LRPX_TRY(conv_dispatch(&d, (hipStream_t)stream));
         } else if (l >= 2 && l + 1 < kNL && t.xz[l + 1] && kVgg[l - 1].conv && L.cin % 16 == 0) {
@@ -924,7 +905,6 @@ int lrpx_vgg16_relevance_ex(const void* packed, const void* trace, int n_img, co
                  "vgg16_relevance: bad arguments");
     const VggCtx cx = resolve_ctx(opts);
     const int mode = cx.mode;
-    const bool use_bf16x6 = cx.bf16x6();
     LayerTimer timer;
     LRPX_REQUIRE(map2img || n_maps == n_img, "vgg16_relevance: map2img is required when n_maps != n_img");
     const VggPacked p = vgg_packed_layout();
@@ -941,8 +921,8 @@ int lrpx_vgg16_relevance_ex(const void* packed, const void* trace, int n_img, co
     const bool h3 = mode >= 2;
     // mode 1 (round 6): the same FUSED flow - REL_MUL epilogues on the precomputed multiplicands, convs under a pool unpool while they stage,
     // no pool kernels, no unpooled tensors - on the exact bf16 splits (conv_f16x3.h, B6): no operand scales, hence no amax words.
-    // LRPX_X6_LEGACY=1 keeps round 1's flow (EPI_REL with the division in the epilogue + maxpool_relevance kernels) for A/B.
-    const bool b6 = mode == 1 && !switches().x6_legacy;
+    // Mode 0 alone keeps round 1's flow: EPI_REL with the division in the epilogue + maxpool_relevance kernels.
+    const bool b6 = mode == 1;
     const bool fused = h3 || b6;
     unsigned* amax = h3 ? reinterpret_cast<unsigned*>(R + (size_t)112 * 112 * 64 * n_maps) : nullptr;
     if (h3) LRPX_TRY(clear_async(amax, (size_t)kNL * n_maps * sizeof(unsigned), (hipStream_t)stream));
@@ -975,9 +955,8 @@ int lrpx_vgg16_relevance_ex(const void* packed, const void* trace, int n_img, co
         if (l == 0) {
             // 3 output channels (first_layer.hip): 16x16x32 MFMAs on the split halves of S in the split-product modes (S
             // comes with its per-map maximum, in 32-channel chunks), the direct fp32 VALU conv otherwise
-            const int fl_mfma = (blk || !switches().first_valu) ? 1 : 0;
             if (timing) (void)hipEventRecord(timer.ev[0][0], (hipStream_t)stream);
-            if (h3 && fl_mfma)
+            if (h3)
                 LRPX_TRY(first_layer_relevance_mfma(S[cur], pk + p.first16, tr + t.act[0], map2img, amax, out_nchw, n_maps,
                                                     0, 1, (hipStream_t)stream));
             else
@@ -1005,11 +984,11 @@ int lrpx_vgg16_relevance_ex(const void* packed, const void* trace, int n_img, co
             // blocked: in (1), x (2), out (4); conv1_2 (l == 1): blocked input only (see conv_f16x3.h, TR)
             if (blk) d.blocked = l == 1 ? 1 : 7;
         }
-        else if (use_bf16x6) { d.bf16x6 = 1; d.wpacked = pk + p.bwd6[l]; }   // round 1's flow (LRPX_X6_LEGACY): EPI_REL, pool kernels
         // (14 x 14 on the Winograd kernel: one launch of 8 x ceil(49 n_maps / 64) workgroups, no K split)
-        const int rel_ks = (b6 && L.hw == 14 && !(d.wpacked_wino && (b6_wino_bits() & 4))) ? switches().b6_rel_ksplit14 : 1;
-        if (rel_ks > 1 && (rel_ks & (rel_ks - 1)) == 0 && rel_ks <= 4 && (L.cout / 16) % rel_ks == 0) {
-            // the 14 x 14 relevance layers K-split in two (LRPX_B6_REL_KSPLIT14): partial sums into the R buffer (unused in the fused flow), then
+        constexpr int rel_ks = 2;
+        static_assert((512 / 16) % rel_ks == 0, "the K ranges must divide the K-chunks of the 14 x 14 layers");
+        if (b6 && L.hw == 14 && !(d.wpacked_wino && (b6_wino_bits() & 4))) {
+            // the 14 x 14 relevance layers of mode 1 K-split in two: partial sums into the R buffer (unused in the fused flow), then
             // out = multiplicand * (pairwise sum) in rel_mul_finish.  At 320 maps the layers cost the same (1 120 -> 2 240 workgroups on 512 slots:
             // the shorter tail pays for the extra pass: 3.67 -> 3.64 ms over the three layers); a chain of 20 maps - the drop-in's one image - ran
             // them on 72 workgroups with 288-step K loops: 319 -> 190 us each, 4.24 -> 3.86 ms per chain.  A LAYER property, never the batch's:
@@ -1028,13 +1007,12 @@ int lrpx_vgg16_relevance_ex(const void* packed, const void* trace, int n_img, co
             d.out1 = S[cur ^ 1];
             if (fused) { d.x = tr + ((blk && l != 1) ? t.xzp[l] : t.xz[l]); if (h3) d.out1_amax = amax + (size_t)(l - 1) * n_maps; }   // x / safe(Z+) precomputed
             // the first-layer kernel walks S in channel chunks (MFMA version: 32 = whole 128-byte lines per pixel; VALU: 16)
-            const int fl_chunk = (b6 || (!blk && switches().first_valu)) ? 16 : 32;
+            const int fl_chunk = b6 ? 16 : 32;
             if (fused && l == 1) d.out_chunk = fl_chunk;
             else if (!blk && !b6) { d.zdiv = tr + t.zpos[l - 1]; d.stab = STAB_SAFE; }
             // mode 2, conv2_2 -> conv2_1: S in 16-channel chunks, the K-chunk of the consumer (64-byte slices of 512-byte NHWC pixels
             // drag every 128-byte line through the fabric twice: FETCH 3.1x the tensor; chunked: conv2_1 1.44 -> 1.37 ms)
-            const int s21_chunk = switches().s21_nhwc ? 0 : 16;
-            if (fused && !blk && l == 4 && s21_chunk) { d.out_chunk = s21_chunk; cur_chunked = 1; }
+            if (fused && !blk && l == 4) { d.out_chunk = 16; cur_chunked = 1; }
             LRPX_TIMED_DISPATCH(l, &d);
         } else {
             if (fused) {
@@ -1045,16 +1023,15 @@ int lrpx_vgg16_relevance_ex(const void* packed, const void* trace, int n_img, co
                 cur ^= 1;
                 continue;
             }
-            // a pool lies below: R at the pool output, then the Pool2d rule + division by Z+ of the conv under it
+            // mode 0, a pool lies below: R at the pool output, then the Pool2d rule + division by Z+ of the conv under it
             d.out0 = R;
             LRPX_TIMED_DISPATCH(l, &d);
             // wide maps: hand the conv below its input in K-chunks (32-byte pixel slices would drag every 128-byte
             // line through the fabric four times: measured L2 hit 36 %, 3x the unique bytes on conv1_2)
             const int below_hw = 2 * L.hw;
-            const int chunk = below_hw < 112 ? 0 : (use_bf16x6 ? 16 : lrpx_conv_kc(below_hw, 9, L.cin));
+            const int chunk = below_hw < 112 ? 0 : lrpx_conv_kc(below_hw, 9, L.cin);
             LRPX_TRY(maxpool_relevance_amax(tr + t.act[l - 1], R, tr + t.zpos[l - 2], map2img, nullptr, S[cur ^ 1],
-                                            n_maps, L.hw, L.hw, L.cin, chunk,
-                                            h3 ? amax + (size_t)(l - 2) * n_maps : nullptr, (hipStream_t)stream));
+                                            n_maps, L.hw, L.hw, L.cin, chunk, nullptr, (hipStream_t)stream));
             cur_chunked = chunk ? 1 : 0;
         }
         cur ^= 1;
@@ -1103,7 +1080,7 @@ static int vgg16_backprop(const void* packed, const void* trace, int n_img, cons
     // pool backward kernel); only the first tensor costs a streaming read of its own
     const bool h3 = mode >= 2;
     // mode 1 (round 6): exact bf16 splits on the conv_f16x3.h tiling (B6), GUIDED hooks fused, pools folded into the staging as in mode 3
-    const bool b6 = mode == 1 && !switches().x6_legacy && !switches().guided_poolbwd;
+    const bool b6 = mode == 1;
     unsigned* gam = reinterpret_cast<unsigned*>(R + (size_t)112 * 112 * 64 * n_maps);
     if (h3) {
         LRPX_TRY(clear_async(gam, (size_t)kNL * n_maps * sizeof(unsigned), st));
@@ -1113,8 +1090,7 @@ static int vgg16_backprop(const void* packed, const void* trace, int n_img, cons
         const VggLayer& L = kVgg[l];
         if (!L.conv) continue;
         if (l == 0) {
-            const int fl_mfma = switches().first_valu ? 0 : 1;
-            if (h3 && fl_mfma)
+            if (h3)
                 LRPX_TRY(first_layer_relevance_mfma(G[cur], pk + p.first16p, tr + t.act[0], map2img, gam, out_nchw, n_maps, 1, 0, st));
             else
                 LRPX_TRY(first_layer_relevance(G[cur], pk + p.first6p, tr + t.act[0], map2img, out_nchw, n_maps, L.cout, 1, 0, st));
@@ -1134,15 +1110,14 @@ static int vgg16_backprop(const void* packed, const void* trace, int n_img, cons
         }
         // mode 3: a conv under a pool receives the gradient at the pool's OUTPUT resolution and routes it to the windows'
         // arg-max while staging (the winner bytes of the trace, as the relevance chain): no pool-backward kernel, no 4x tensor
-        const int gpool = switches().guided_poolbwd ? 0 : 1;
-        const bool lowres_in = gpool && (mode == 3 || b6) && l + 1 < kNL && !kVgg[l + 1].conv && l + 2 < kNL;
+        const bool lowres_in = (mode == 3 || b6) && l + 1 < kNL && !kVgg[l + 1].conv && l + 2 < kNL;
         if (lowres_in) d.pool_am = (const uint8_t*)(tr + t.am[l + 1]);
         if (kVgg[l - 1].conv) {
             d.epi = EPI_GUIDED; d.x = tr + t.act[l]; d.out0 = G[cur ^ 1];      // ReLU hook of conv l-1 fused
             d.relu = plain ? 2 : 0;
             if (h3) d.out0_amax = gam + (size_t)(l - 1) * n_maps;
             LRPX_TRY(conv_dispatch(&d, st));
-        } else if (gpool && (mode == 3 || b6) && l >= 2) {
+        } else if ((mode == 3 || b6) && l >= 2) {
             // a pool lies below: the pool backward's gate [max > 0] (and the guided clamp) is the GUIDED hook on the pool's
             // OUTPUT (= this conv's input, act[l]); the conv under the pool unpools while staging
             d.epi = EPI_GUIDED; d.x = tr + t.act[l]; d.out0 = G[cur ^ 1];

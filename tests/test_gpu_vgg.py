@@ -776,6 +776,24 @@ def test_b6_kernels_never_write_past_the_last_map(ops, hw, n_maps, epi):
         ops.conv_mfma(s, wb, n_maps, hw, cout, cin, 9, _lib.EPI_REL_MUL, oc_split=cin, x=x, out0=out, out1=out, bf16x6=1, **kw)
 
 
+def test_bf16x6_fwd_dual_refuses_an_oc_split_off_the_32_channel_blocks(ops):
+    """the exact-split FWD_DUAL kernels hand whole 32-channel column blocks to out0 or out1: oc_split = 48 of n_oc = 96 is
+    EINVAL with a message that names oc_split, and nothing is launched"""
+    from lrp_amd import _lib
+    hw, cin, cout = 14, 16, 48
+    x = torch.rand(1, hw * hw, cin, device="cuda")
+    w = torch.randn(2 * cout, cin, 3, 3, device="cuda") * 0.05
+    wb = ops.pack_weights_bf16x3(w, 2 * cout, cin, _lib.PACK_FWD)
+    act = torch.full((1, hw * hw, cout), 12345.0, device="cuda")
+    zpos = torch.full((1, hw * hw, cout), 12345.0, device="cuda")
+    with pytest.raises(ValueError, match="oc_split"):
+        ops.conv_mfma(x, wb, 1, hw, cin, 2 * cout, 9, _lib.EPI_FWD_DUAL, oc_split=cout, bias=torch.zeros(cout, device="cuda"),
+                      out0=act, out1=zpos, bf16x6=1)
+    assert b"oc_split" in _lib.load().lrpx_last_error_string()
+    torch.cuda.synchronize()
+    assert (act == 12345.0).all() and (zpos == 12345.0).all()
+
+
 def test_per_context_conv_mode_in_flight_on_two_streams(ops, gridtd_case):
     """the conv mode travels per call (lrpx_vgg16_opts): two contexts over the same weights with DIFFERENT modes run
     interleaved on two streams and each reproduces, bit for bit, what a process-wide setter run of its mode gives - while

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """distance of the GPU forward trace's features from an fp64 evaluation of the same VGG16 (1 image, CPU double), per forward variant:
-python tools/dbg/fwd_f64_probe.py   (LRPX_FWD_KSPLIT28=4 etc. in the environment select the switches)"""
+python tools/dbg/fwd_f64_probe.py"""
 import os, sys
 import torch
 import torch.nn.functional as F
@@ -32,5 +32,4 @@ for name, mode, f16 in (("mode 0 fp32 MFMA", 0, 0), ("mode 1 exact bf16 splits",
     vgg.conv_mode, vgg.forward_f16 = mode, f16
     f = vgg.forward(img.cuda())[0].double().cpu()
     e = (f - f64).abs()
-    print(f"{name}: max {(e.max() / f64.abs().max()).item():.2e}, rms {(e.pow(2).mean().sqrt() / f64.abs().max()).item():.2e} of the feature maximum (switches: "
-          f"KSPLIT14={os.environ.get('LRPX_FWD_KSPLIT', '8')} KSPLIT28={os.environ.get('LRPX_FWD_KSPLIT28', '1')})", flush=True)
+    print(f"{name}: max {(e.max() / f64.abs().max()).item():.2e}, rms {(e.pow(2).mean().sqrt() / f64.abs().max()).item():.2e} of the feature maximum", flush=True)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Latency of the many-row dense f16x3 GEMM (REL epilogue) for the shapes of configs 2 and 5; LRPX_DENSE_WIDE=1 -> 256-row tiles."""
+"""Latency of the many-row dense f16x3 GEMM (REL epilogue) for the shapes of configs 2 and 5."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """ReLU-mask and pool-winner flips of the GPU forward trace, per layer, against (a) the fp32 CPU forward of the oracle (oneDNN:
 what the reference runs) and (b) an fp64 forward of the same weights.  A flip = a discrete decision (ReLU sign, 2x2 arg-max) taken
-differently: every one moves relevance / gradient by a finite amount, so this is what the end-to-end deviations are made of.
-Run once per forward variant (the switches latch per process):  LRPX_FWD_KSPLIT28=1 python tools/flip_probe.py"""
+differently: every one moves relevance / gradient by a finite amount, so this is what the end-to-end deviations are made of."""
 import os, sys
 import torch
 import torch.nn.functional as F
