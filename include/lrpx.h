@@ -652,6 +652,34 @@ int lrpx_adaatt_rel_glob(const lrpx_adaatt_trace* tr, const lrpx_adaatt_relstate
 int lrpx_adaatt_rel_pix_rows(const lrpx_adaatt_trace* tr, const lrpx_adaatt_relstate* rs, const float* Vp, const float* proj_nb,
                              float* a_proj, const int32_t* rows, int n_rows, void* stream);
 
+/* ---- single-LSTM adaptive-attention decoder: gradient explainers (ExplainAdaptiveGradient.explain_caption_wordt,
+ *      models/adaptiveattention.py:965-1021; the guided class's decoder part, :1100-1157, is the same function and Grad-CAM inherits it).
+ *      The trace is an lrpx_adaatt_trace WITH o and sgate.  Only d_h = G_i W_hh is serial: r_words[i] = G_i . wsum with
+ *      wsum[k] = sum_{e < E} W_ih[k][e], and d_glob = (sum_i G_i) W_ih[:, E:] - the caller's GEMM on gsum (csrc/lrpx_adaatt_grad.hip). -- */
+typedef struct lrpx_adaptive_gradstate {
+    const int32_t* lens;                /* [B] words per image (null: T) */
+    float *d_ctx, *d_c;                 /* [B*T][H]: (1 - beta_t) d_h (:989); the running cell gradient */
+    float *g0, *g1;                     /* [B*T][4H]: the gate gradients G_i (order i f g o) of even / odd lock-steps */
+    float* gsum;                        /* [B*T][4H]: sum_i G_i */
+    float* wpart;                       /* [B*T][T][H / 16]: per-workgroup partials of G_i . wsum */
+    float* r_words;                     /* [B*T][T] (not normalised: lrpx_rel_words_norm) */
+} lrpx_adaptive_gradstate;
+/* :987-992 and the cell back-step of lock-step 0 (time index i = t): d_ctx, d_c, G_t into g0, gsum = G_t, the partials of r_words[t]; g1 is
+ * cleared.  Rows behind an image's last word: exact zeros in d_ctx, d_c, g0, g1, gsum.  wsum: [4H].  tok_ld >= T + 1. */
+int lrpx_adaptive_grad_init(const lrpx_adaatt_trace* tr, const lrpx_adaptive_gradstate* gs, const float* fcw, const long long* tok,
+                            int tok_ld, const float* wsum, void* stream);
+/* lock-steps 1 <= s < n_steps in one call, one launch each (row b*T + t works on time index i = t - s while s <= t < lens[b]):
+ * d_h = G_{i+1} w_hh_t^T on the fp32 matrix cores (w_hh_t (H, 4H): row j = column j of W_hh) with the cell back-step (:996-1006) of the
+ * workgroup's 16 hidden units in the epilogue - G_i into the other G buffer, d_c, gsum += G_i, its partial of G_i . wsum -; then one launch
+ * that adds the partials in workgroup order into r_words (zeros behind word t and in inactive rows).  1 <= n_steps <= T. */
+int lrpx_adaptive_grad_steps(const lrpx_adaatt_trace* tr, const lrpx_adaptive_gradstate* gs, int n_steps, const float* w_hh_t,
+                             const float* wsum, void* stream);
+/* d_feat[x][k][:] = alpha[b][t][k] v1[row][:] + d_avg[row][:] / P for row = rows[x] (null: x, n_rows must be B*T), written compactly
+ * [n_rows][P][C] (:1013-1015; v1 = d_ctx W_proj [B*T][C], d_avg = d_glob W_gp [B*T][C]); zeros for a row behind its image's last word.
+ * C % 4 == 0. */
+int lrpx_adaptive_grad_pix_rows(const lrpx_adaatt_trace* tr, const lrpx_adaptive_gradstate* gs, const float* v1, const float* d_avg,
+                                float* d_feat, int C, const int32_t* rows, int n_rows, void* stream);
+
 /* ---- AoA decoder: trace (get_hidden_parameters, models/aoamodel.py:990-1062) -------------------------- */
 typedef struct lrpx_aoa_trace {
     int B, T, H, E, P, NH;

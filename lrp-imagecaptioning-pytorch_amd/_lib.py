@@ -74,6 +74,11 @@ class AdaRelState(C.Structure):
     _fields_ = [(k, _f) for k in ("lens", "r_h", "r_c", "r_ctx", "r_glob", "A", "rx", "r_words")]
 
 
+class AdaGradState(C.Structure):
+    """lrpx_adaptive_gradstate"""
+    _fields_ = [(k, _f) for k in ("lens", "d_ctx", "d_c", "g0", "g1", "gsum", "wpart", "r_words")]
+
+
 class AoaGradState(C.Structure):
     _fields_ = [(k, _f) for k in ("lens", "d_h", "d_c", "dA", "dB", "gates", "dx", "d_glob", "r_words")]
 
@@ -224,6 +229,9 @@ SIGNATURES = {
     "lrpx_adaatt_rel_steps": (_i, [C.POINTER(AdaTrace), C.POINTER(AdaRelState), _i, C.POINTER(ConvDesc), _f, _i, _i, _f]),
     "lrpx_adaatt_rel_glob": (_i, [C.POINTER(AdaTrace), C.POINTER(AdaRelState), _f, _f, _f]),
     "lrpx_adaatt_rel_pix_rows": (_i, [C.POINTER(AdaTrace), C.POINTER(AdaRelState), _f, _f, _f, _f, _i, _f]),
+    "lrpx_adaptive_grad_init": (_i, [C.POINTER(AdaTrace), C.POINTER(AdaGradState), _f, _f, _i, _f, _f]),
+    "lrpx_adaptive_grad_steps": (_i, [C.POINTER(AdaTrace), C.POINTER(AdaGradState), _i, _f, _f, _f]),
+    "lrpx_adaptive_grad_pix_rows": (_i, [C.POINTER(AdaTrace), C.POINTER(AdaGradState), _f, _f, _f, _i, _f, _i, _f]),
     "lrpx_gridtd_grad_init": (_i, [C.POINTER(GridTrace), C.POINTER(GridGradState), _f, _f, _i, _f]),
     "lrpx_gridtd_grad_step": (_i, [C.POINTER(GridTrace), C.POINTER(GridGradState), _i, _i, _f]),
     "lrpx_spread_pixels": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _f]),

@@ -53,7 +53,8 @@ class AdaAttEngine(EngineBase):
 
     ENCODER_CONV_MODES = EngineBase._ENCODER_CONV_MODES
     GRADIENT_FOLLOW_UP = ("the gradient explainers of this model (ExplainAdaptiveAttentionGradient / GuidedGradient / GradCam / GuidedGradCam, "
-                          "models/adaptiveattention.py:851-1320) are a follow-up: AdaAttEngine has the LRP explainer only")
+                          "models/adaptiveattention.py:851-1320) live in the follow-up to this engine, AdaAttGradEngine "
+                          "(explainers/adaatt_grad.py): AdaAttEngine has the LRP explainer only")
     NO_LRP_INFERENCE = "models/adaptiveattention.py defines no sample_lrp / forwardlrp_context for this model"
 
     def __init__(self, state, device="cuda", encoder=None, encoder_conv_mode=1):
@@ -120,6 +121,9 @@ class AdaAttEngine(EngineBase):
         names = ["xh", "h", "c", "g", "i", "f", "s", "ctx", "ctx_hat", "hc", "alpha", "beta"]
         for k in names[3:10]:
             shapes[k] = (B, T, H)
+        if grad:                                           # the gradient explainers' trace: output gate and sentinel gate kept
+            names += ["o", "sgate"]
+            shapes["o"] = shapes["sgate"] = (B, T, H)
         tr = dict(B=B, T=T)
         tr.update(ops.zeros_arena(dev, shapes))            # one allocation, one fill (h[0] = c[0] = 0: init_hidden_state, :123-126)
         c = AdaTrace()
@@ -214,11 +218,15 @@ class AdaAttEngine(EngineBase):
         (`model_bias`: accepted for the drop-in base; this explainer's forward IS the model's, :557.)"""
         if grad:
             raise NotImplementedError("AdaAttEngine.trace(grad=True): " + self.GRADIENT_FOLLOW_UP)
+        return self._teacher_forced(enc, captions, predictions, False)
+
+    def _teacher_forced(self, enc, captions, predictions, grad):
+        """the body of `trace`; grad=True keeps the output gate and the sentinel gate (explainers/adaatt_grad.py)"""
         lib, st = _lib.load(), stream_ptr()
         B, T = captions.shape[0], captions.shape[1] - 1
         H, E, P, dev, sd = self.H, self.E, self.P, self.device, self.sd
         captions = captions.to(dev, torch.int64).contiguous()      # (token ids index the embedding table: never another width)
-        tr = self._alloc_trace(B, T)
+        tr = self._alloc_trace(B, T, grad)
         c = C.byref(tr["_c"])
         if self.decoupled and T > 0:
             W, R, NR, aa = H + 2 * E, B * T, self.NR, "AdaAttention."
@@ -401,11 +409,12 @@ class ExplainAdaptiveAttention(ExplainerBase):
     reference explains is `beam_search(beam_size=3, max_cap_length=20)` (:628).  `t_list` selects what the reference draws
     (`visualize_explanations`); nothing is drawn here, every word is explained.  A ResNet encoder is handed over as for
     `ExplainGridTDAttention`."""
+    _ENGINE, _ENGINE_KIND = AdaAttEngine, "adaatt"          # the engine class and its engine-cache kind (the gradient family has its own)
 
     def _engine_key(self):
         from . import engine_cache
         mode = getattr(self.args, "encoder_conv_mode", 1)
-        return engine_cache.fingerprint("adaatt", self.args.weight if self.model is None else self.model,
+        return engine_cache.fingerprint(self._ENGINE_KIND, self.args.weight if self.model is None else self.model,
                                         extra=() if mode == 1 else (("encoder_conv_mode", mode),))
 
     def _build_engine(self, state):
@@ -415,7 +424,7 @@ class ExplainAdaptiveAttention(ExplainerBase):
             if resnet_encoder_keys(state) and isinstance(enc, torch.nn.Module) and all(
                     t.device.type == "cuda" for t in list(enc.parameters()) + list(enc.buffers())):
                 encoder = enc                  # the model's own module (else: rebuilt from the same tensors by the engine)
-        return AdaAttEngine(state, encoder=encoder, encoder_conv_mode=getattr(self.args, "encoder_conv_mode", 1))
+        return self._ENGINE(state, encoder=encoder, encoder_conv_mode=getattr(self.args, "encoder_conv_mode", 1))
 
     def get_hidden_parameters(self, img, caption_encode=None, max_cap_length=20):
         """Forward trace (:626-677).  `img`: file path or a (1,3,H,W) tensor of the encoder's image size."""
