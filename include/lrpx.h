@@ -167,8 +167,17 @@ typedef struct lrpx_conv_desc {
 } lrpx_conv_desc;
 /* 3x3/pad-1 convolution (taps=9, square hw x hw maps) or dense GEMM (taps=1) on the fp32 MFMA with
  * the fused epilogues of the relevance rules.  Replaces F.conv2d / conv backward inside
- * LRPtools/utils.py:21-31 `lrp_backward` and torch.matmul/sum inside `lrp_linear_eps`. */
+ * LRPtools/utils.py:21-31 `lrp_backward` and torch.matmul/sum inside `lrp_linear_eps`.
+ * taps = 9 is built for hw = 224, 112, 56, 28 and 14 only: any other hw is LRPX_EINVAL, in every arithmetic (before the kernel list of
+ * csrc/conv_kernels.def, bf16x6 PLAIN and Winograd descriptors with another hw <= 56 ran a kernel compiled for 14 x 14 maps). */
 int lrpx_conv_mfma(const lrpx_conv_desc* d, void* stream);
+/* Which kernel lrpx_conv_mfma would run for *d: exactly its validation and selection, pure host code - nothing is launched or cleared, no
+ * pointer is dereferenced or queried (pointers only need to be non-null where the descriptor needs them).  Writes
+ * "<name> ks=<K split> tg=<tile group>" into buf (len bytes, truncated), <name> = the row of csrc/conv_kernels.def (the launcher launch_<name>; b6_<hw>_wino_share = the Winograd kernel
+ * with column-sharing staging, lrpx_set_b6_wino bit 8 clear) or one of dense_bf16x6,
+ * dense_f16x3, dense_small_f16x3, dense_small; the selection reads lrpx_set_b6_wino.  LRPX_EINVAL + lrpx_last_error_string() where
+ * lrpx_conv_mfma refuses the descriptor. */
+int lrpx_conv_kernel_name(const lrpx_conv_desc* d, char* buf, int len);
 
 /* ---- the contraction engine at any conv geometry (csrc/conv_geom_kernel.h, fp32 entries in csrc/conv_geom.hip; the ResNet encoders' 7x7 s2, 1x1, 1x1 s2, 3x3 s2) ------ */
 enum { LRPX_GEOM_FWD = 0,   /* out[n,oh,ow,co] = sum in[n, oh*sh-ph+r, ow*sw-pw+s, ci] * w[co,ci,r,s] (+ bias[co]) */

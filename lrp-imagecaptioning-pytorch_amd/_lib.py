@@ -147,6 +147,7 @@ SIGNATURES = {
     "lrpx_set_b6_wino": (_i, [_i]),
     "lrpx_conv_kc": (_i, [_i, _i, _i]),
     "lrpx_conv_mfma": (_i, [C.POINTER(ConvDesc), _f]),
+    "lrpx_conv_kernel_name": (_i, [C.POINTER(ConvDesc), C.c_char_p, _i]),
     "lrpx_nchw_to_nhwc": (_i, [_f, _f, _i, _i, _i, _i, _f]),
     "lrpx_nhwc_to_nchw": (_i, [_f, _f, _i, _i, _i, _i, _f]),
     "lrpx_nchw_to_nhwc_posneg": (_i, [_f, _f, _i, _i, _i, _i, _f]),
@@ -363,7 +364,7 @@ class Recording(object):
 
 
 # int-valued entry points that are QUERIES / setters, not launches with a status: never part of a recorded step
-_QUERIES = {"lrpx_version", "lrpx_conv_kc", "lrpx_set_bf16x6", "lrpx_set_conv_mode", "lrpx_set_forward_f16"}
+_QUERIES = {"lrpx_version", "lrpx_conv_kc", "lrpx_conv_kernel_name", "lrpx_set_bf16x6", "lrpx_set_conv_mode", "lrpx_set_forward_f16"}
 
 
 def _recordable(fn):

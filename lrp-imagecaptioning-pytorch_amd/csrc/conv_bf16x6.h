@@ -41,8 +41,15 @@ __device__ __forceinline__ void split3(float x, unsigned short& p0, unsigned sho
 static __device__ unsigned long long g_stamp[8];
 #define LRPX_T(v) unsigned long long v; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory"); \
                   __builtin_amdgcn_sched_barrier(0)
+#define LRPX_STAMP_READER_X6                                                                                                            \
+    extern "C" int lrpx_debug_stamps(unsigned long long* out8, int reset) {                                                             \
+        if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(lrpx::g_stamp), 64) != hipSuccess) return 1;                                           \
+        if (reset) { unsigned long long z[8] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(lrpx::g_stamp), z, 64) != hipSuccess) return 1; }   \
+        return 0;                                                                                                                       \
+    }
 #else
 #define LRPX_T(v)
+#define LRPX_STAMP_READER_X6
 #endif
 
 // DB: double-buffered A tile (one barrier per chunk).  DB = false (tiles whose two buffers would not leave room for two

@@ -105,8 +105,16 @@ __device__ __forceinline__ void amax_update(unsigned* p, float m) {
 static __device__ unsigned long long g_stamp_h3[12];
 #define LRPXH_T(v) unsigned long long v; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory"); \
                    __builtin_amdgcn_sched_barrier(0)
+// the reader of a translation unit's clocks (g_stamp_h3 is one array per unit): conv_kernels.def names the units that export one
+#define LRPX_STAMP_READER(unit)                                                                                                           \
+    extern "C" int lrpx_debug_stamps_##unit(unsigned long long* out12, int reset) {                                                       \
+        if (hipMemcpyFromSymbol(out12, HIP_SYMBOL(lrpx::g_stamp_h3), 96) != hipSuccess) return 1;                                         \
+        if (reset) { unsigned long long z[12] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(lrpx::g_stamp_h3), z, 96) != hipSuccess) return 1; } \
+        return 0;                                                                                                                         \
+    }
 #else
 #define LRPXH_T(v)
+#define LRPX_STAMP_READER(unit)
 #endif
 
 // REL_MUL epilogue with 16-byte accesses ("wide"): out = x * acc for the wave's 7 accumulator tiles of 32 pixels x 32

@@ -1,4 +1,4 @@
-// Launch helpers for the conv_mfma kernel family (instantiated in conv_inst_*.hip).
+// Launch helpers for the conv_mfma kernel family and the row type of the kernel list (conv_kernels.def).
 #pragma once
 #include "common.h"
 #include "conv_mfma.h"
@@ -25,130 +25,16 @@ int launch_conv_cfg(const ConvArgs& a, hipStream_t stream) {
     return check_launch("conv_mfma");
 }
 
-// one function per instantiation, defined in conv_inst_*.hip
-int launch_conv_224_8_1_4_9_fwd_dual(const ConvArgs& a, hipStream_t s);
-int launch_conv_224_8_2_2_9_rel(const ConvArgs& a, hipStream_t s);
-int launch_conv_112_8_1_4_9_fwd_dual(const ConvArgs& a, hipStream_t s);
-int launch_conv_112_8_1_4_9_rel(const ConvArgs& a, hipStream_t s);
-int launch_conv_112_8_2_2_9_rel(const ConvArgs& a, hipStream_t s);
-int launch_conv_56_16_1_4_9_fwd_dual(const ConvArgs& a, hipStream_t s);
-int launch_conv_56_16_1_4_9_rel(const ConvArgs& a, hipStream_t s);
-int launch_conv_28_16_1_4_9_fwd_dual(const ConvArgs& a, hipStream_t s);
-int launch_conv_28_16_1_4_9_rel(const ConvArgs& a, hipStream_t s);
-int launch_conv_14_16_1_4_9_fwd_dual(const ConvArgs& a, hipStream_t s);
-int launch_conv_14_16_1_4_9_rel(const ConvArgs& a, hipStream_t s);
-int launch_conv_224_8_2_2_9_guided(const ConvArgs& a, hipStream_t s);
-int launch_conv_14_32_1_4_1_rel(const ConvArgs& a, hipStream_t s);
-int launch_conv_14_32_1_4_1_plain(const ConvArgs& a, hipStream_t s);
-int launch_conv_112_8_1_4_9_guided(const ConvArgs& a, hipStream_t s);
-int launch_conv_112_8_2_2_9_plain(const ConvArgs& a, hipStream_t s);
-int launch_conv_56_16_1_4_9_guided(const ConvArgs& a, hipStream_t s);
-int launch_conv_56_16_1_4_9_plain(const ConvArgs& a, hipStream_t s);
-int launch_conv_28_16_1_4_9_guided(const ConvArgs& a, hipStream_t s);
-int launch_conv_28_16_1_4_9_plain(const ConvArgs& a, hipStream_t s);
-int launch_conv_14_16_1_4_9_guided(const ConvArgs& a, hipStream_t s);
-int launch_conv_14_16_1_4_9_plain(const ConvArgs& a, hipStream_t s);
-int launch_conv_224_8_1_4_9_plain(const ConvArgs& a, hipStream_t s);       // Z+ / Z- of the alpha-beta rule at 224 x 224
-
-// round 1's exact-split kernels (conv_bf16x6.h): the EPI_REL relevance passes only; every other bf16x6 descriptor runs on the B6 kernels below
-int launch_x6_56_rel(const ConvArgs& a, hipStream_t s);
-int launch_x6_28_rel(const ConvArgs& a, hipStream_t s);
-int launch_x6_14_rel(const ConvArgs& a, hipStream_t s);
-int launch_x6_112_rel(const ConvArgs& a, hipStream_t s);
-int launch_x6_224_rel(const ConvArgs& a, hipStream_t s);
-int launch_x6_112n_rel(const ConvArgs& a, hipStream_t s);
-
-// conv mode 1 on the conv_f16x3.h tiling (B6: exact bf16 splits, six products) with the fused multiplicand (REL_MUL) and pooled-input staging
-int launch_b6_224_rel(const ConvArgs& a, hipStream_t s);
-int launch_b6_112_rel(const ConvArgs& a, hipStream_t s);
-int launch_b6_112n_rel(const ConvArgs& a, hipStream_t s);
-int launch_b6_56_rel(const ConvArgs& a, hipStream_t s);
-int launch_b6_28_rel(const ConvArgs& a, hipStream_t s);
-int launch_b6_14_rel(const ConvArgs& a, hipStream_t s);
-int launch_b6_224_pool(const ConvArgs& a, hipStream_t s);
-int launch_b6_112_pool(const ConvArgs& a, hipStream_t s);
-int launch_b6_56_pool(const ConvArgs& a, hipStream_t s);
-int launch_b6_28_pool(const ConvArgs& a, hipStream_t s);
-int launch_b6_112n_guided(const ConvArgs& a, hipStream_t s);   // ... image-gradient chains (GUIDED: guided backprop / plain gradient)
-int launch_b6_56_guided(const ConvArgs& a, hipStream_t s);
-int launch_b6_28_guided(const ConvArgs& a, hipStream_t s);
-int launch_b6_14_guided(const ConvArgs& a, hipStream_t s);
-int launch_b6_224_pool_guided(const ConvArgs& a, hipStream_t s);
-int launch_b6_112_pool_guided(const ConvArgs& a, hipStream_t s);
-int launch_b6_56_pool_guided(const ConvArgs& a, hipStream_t s);
-int launch_b6_28_pool_guided(const ConvArgs& a, hipStream_t s);
-int launch_b6_224_fwd(const ConvArgs& a, hipStream_t s);       // ... forward trace (FWD_DUAL; 14 x 14: K-split PLAIN)
-int launch_b6_112_fwd(const ConvArgs& a, hipStream_t s);
-int launch_b6_56_fwd(const ConvArgs& a, hipStream_t s);
-int launch_b6_28_fwd(const ConvArgs& a, hipStream_t s);
-int launch_b6_14_fwd(const ConvArgs& a, hipStream_t s);
-int launch_b6_14_plain(const ConvArgs& a, hipStream_t s);
-int launch_b6_28_plain(const ConvArgs& a, hipStream_t s);
-int launch_b6_56_plain(const ConvArgs& a, hipStream_t s);
-
-int launch_b6_56_wino(const ConvArgs& a, hipStream_t s);      // ... Winograd F(2x2,3x3) on the exact splits (conv_wino_b6.h; a.wp = lrpx_pack_weights_wino_b6)
-int launch_b6_28_wino(const ConvArgs& a, hipStream_t s);
-int launch_b6_14_wino(const ConvArgs& a, hipStream_t s);
-
-int launch_h3_224_rel(const ConvArgs& a, hipStream_t s);
-int launch_h3_112_rel(const ConvArgs& a, hipStream_t s);
-int launch_h3_112n_rel(const ConvArgs& a, hipStream_t s);
-int launch_h3_56_rel(const ConvArgs& a, hipStream_t s);
-int launch_h3_28_rel(const ConvArgs& a, hipStream_t s);
-int launch_h3_14_rel(const ConvArgs& a, hipStream_t s);
-// f16+f8 relevance kernels (conv_f16x3.h, F8 = true): hi.hi on the fp16 matrix cores, the two cross products on fp8
-int launch_h8_56_rel(const ConvArgs& a, hipStream_t s);
-int launch_h8_28_rel(const ConvArgs& a, hipStream_t s);
-int launch_h8_14_rel(const ConvArgs& a, hipStream_t s);
-int launch_h8_56w_rel(const ConvArgs& a, hipStream_t s);      // 8-wave workgroups (256 output channels)
-int launch_h8_28w_rel(const ConvArgs& a, hipStream_t s);
-int launch_h8_14w_rel(const ConvArgs& a, hipStream_t s);
-int launch_h8_56w_pool(const ConvArgs& a, hipStream_t s);
-int launch_h8_28w_pool(const ConvArgs& a, hipStream_t s);
-int launch_h8_112_rel(const ConvArgs& a, hipStream_t s);
-int launch_h8_112n_rel(const ConvArgs& a, hipStream_t s);
-int launch_h8_224_rel(const ConvArgs& a, hipStream_t s);
-int launch_h8_224_pool(const ConvArgs& a, hipStream_t s);
-int launch_h8_112_pool(const ConvArgs& a, hipStream_t s);
-int launch_h8_56_pool(const ConvArgs& a, hipStream_t s);
-int launch_h8_28_pool(const ConvArgs& a, hipStream_t s);
-int launch_h8_224_guided(const ConvArgs& a, hipStream_t s);   // image-gradient chains on the f16+f8 kernels
-int launch_h8_112_guided(const ConvArgs& a, hipStream_t s);
-int launch_h8_56_guided(const ConvArgs& a, hipStream_t s);
-int launch_h8_28_guided(const ConvArgs& a, hipStream_t s);
-int launch_h8_14_guided(const ConvArgs& a, hipStream_t s);
-int launch_h8_112n_plain(const ConvArgs& a, hipStream_t s);
-int launch_h8_56_plain(const ConvArgs& a, hipStream_t s);
-int launch_h8_28_plain(const ConvArgs& a, hipStream_t s);
-int launch_h8_14_plain(const ConvArgs& a, hipStream_t s);
-int launch_h8_56w_guided(const ConvArgs& a, hipStream_t s);   // ... >= 256 output channels: 8-wave workgroups
-int launch_h8_28w_guided(const ConvArgs& a, hipStream_t s);
-int launch_h8_14w_guided(const ConvArgs& a, hipStream_t s);
-int launch_h8_28w_plain(const ConvArgs& a, hipStream_t s);
-int launch_h8_14w_plain(const ConvArgs& a, hipStream_t s);
-int launch_h8_112n_guided(const ConvArgs& a, hipStream_t s);
-int launch_h8_224_pool_guided(const ConvArgs& a, hipStream_t s);   // ... under a pool: pooled-input staging
-int launch_h8_112_pool_guided(const ConvArgs& a, hipStream_t s);
-int launch_h8_56w_pool_guided(const ConvArgs& a, hipStream_t s);
-int launch_h8_28w_pool_guided(const ConvArgs& a, hipStream_t s);
-int launch_h3_224_fwd(const ConvArgs& a, hipStream_t s);    // forward trace (ReLU(conv+b) and Z+) on the fp16 matrix cores
-int launch_h3_112_fwd(const ConvArgs& a, hipStream_t s);
-int launch_h3_56_fwd(const ConvArgs& a, hipStream_t s);
-int launch_h3_28_fwd(const ConvArgs& a, hipStream_t s);
-int launch_h3_14_fwd(const ConvArgs& a, hipStream_t s);
-int launch_h3_224_guided(const ConvArgs& a, hipStream_t s);   // image-gradient chains (guided backprop / plain gradient)
-int launch_h3_112_guided(const ConvArgs& a, hipStream_t s);
-int launch_h3_56_guided(const ConvArgs& a, hipStream_t s);
-int launch_h3_28_guided(const ConvArgs& a, hipStream_t s);
-int launch_h3_14_guided(const ConvArgs& a, hipStream_t s);
-int launch_h3_112n_plain(const ConvArgs& a, hipStream_t s);
-int launch_h3_56_plain(const ConvArgs& a, hipStream_t s);
-int launch_h3_28_plain(const ConvArgs& a, hipStream_t s);
-int launch_h3_14_plain(const ConvArgs& a, hipStream_t s);
-int launch_h3_224_pool(const ConvArgs& a, hipStream_t s);   // operand unpooled while staged (a.pool_am)
-int launch_h3_112_pool(const ConvArgs& a, hipStream_t s);
-int launch_h3_56_pool(const ConvArgs& a, hipStream_t s);
-int launch_h3_28_pool(const ConvArgs& a, hipStream_t s);
+// one row of conv_kernels.def: a fixed-geometry conv kernel (launch_<name> = an instantiation of launch_conv_cfg / launch_conv_bf16x6 /
+// launch_conv_f16x3 / launch_conv_wino_b6, defined in the generated conv_inst_<unit>.hip) and the descriptors that run on it
+enum ConvFamily : int { FAM_FP32, FAM_B6, FAM_H3, FAM_H8 };
+enum ConvVariant : int { VAR_DIRECT, VAR_POOL, VAR_WINO_OWN, VAR_WINO_SHARE };
+constexpr int OC_ANY = 0x7fffffff;
+struct ConvKernel {
+    const char* name;
+    int (*launch)(const ConvArgs&, hipStream_t);
+    int family, hw, epi, variant, oc_min, oc_max;
+};
 
 // dense relevance GEMMs with many rows on the fp16 matrix cores (dense_f16x3.hip)
 int launch_dense_f16x3(const ConvArgs& a, hipStream_t s);
@@ -170,7 +56,7 @@ int launch_dense_ks_aoa_step(const ConvArgs& a, const AoaStepFuse& fz, hipStream
 bool dense_small_fits(const ConvArgs& a);
 int launch_dense_small(const ConvArgs& a, hipStream_t s);
 
-// host-side entry used by the C ABI and by the VGG16 / decoder chains
+// host-side entry used by the C ABI and by the VGG16 / decoder chains (conv_dispatch.hip): conv_select, then the launch
 int conv_dispatch(const lrpx_conv_desc* d, hipStream_t stream, int f16_ksplit = 1);
 
 }  // namespace lrpx

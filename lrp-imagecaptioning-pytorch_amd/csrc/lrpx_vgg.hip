@@ -1,4 +1,4 @@
-// Conv dispatch + the VGG16 encoder chains (forward trace, LRP relevance) of liblrpx.
+// The VGG16 encoder chains (forward trace, LRP relevance, image gradients) of liblrpx; their convs go through conv_dispatch.hip.
 //
 // Reference behaviour reproduced (paths relative to the reference repo):
 //   forward  : models/gridTDmodel.py:40-43 Encoder.forward over vgg16.features[0:-1] (models/vgg.py:62-81)
@@ -13,304 +13,6 @@
 #include "blocked.h"
 
 namespace lrpx {
-
-int conv_dispatch(const lrpx_conv_desc* d, hipStream_t s, int f16_ksplit) {
-    LRPX_REQUIRE(d && d->in && d->wpacked && (d->out0 || d->out1), "conv_mfma: null pointer");
-    LRPX_REQUIRE(d->taps == 9 || d->taps == 1, "conv_mfma: taps must be 9 or 1");
-    LRPX_REQUIRE(d->n_maps > 0 && d->cin > 0 && d->n_oc > 0 && d->n_oc % 32 == 0, "conv_mfma: bad sizes (n_oc %% 32)");
-    const int kc = (d->bf16x6 || d->f16x3) ? 16 : lrpx_conv_kc(d->hw, d->taps, d->cin);
-    LRPX_REQUIRE(kc > 0 && d->cin % kc == 0, "conv_mfma: cin=%d is not a multiple of the K-chunk %d", d->cin, kc);
-    ConvArgs a;
-    a.in = d->in; a.wp = d->wpacked; a.n_maps = d->n_maps; a.cin = d->cin; a.n_oc = d->n_oc;
-    a.pix_per_map = d->taps == 9 ? d->hw * d->hw : d->pix_per_map;
-    a.in_chunk_stride = d->in_chunked ? (long)d->n_maps * a.pix_per_map * kc : 0;
-    a.epi = d->epi; a.stab = d->stab; a.oc_split = d->oc_split; a.relu = d->relu;
-    a.bias = d->bias; a.X = d->x; a.U = d->u; a.Zdiv = d->zdiv; a.map2img = d->map2img;
-    a.out0 = d->out0; a.out1 = d->out1;
-    a.in_amax = d->in_amax; a.out1_amax = d->out1_amax; a.pool_am = d->pool_am; a.out0_amax = d->out0_amax;
-    a.out_chunk = d->epi == EPI_REL_MUL ? d->out_chunk : 0;
-    a.tile_group = ((d->f16x3 || (d->bf16x6 && (d->epi == EPI_REL_MUL || d->epi == EPI_GUIDED))) && d->tile_group > 1 && d->n_maps % d->tile_group == 0) ? d->tile_group : 0;
-    a.ksplit = 1;
-    // many rows (the (word, pixel) rules of the decoders): split products on the fp16 matrix cores (dense_f16x3.hip);
-    // `wpacked` is then an lrpx_pack_weights_f16x2 blob (taps = 1) and `in_amax` holds max|in| per map
-    // ... or, with operands split EXACTLY into three bf16 parts (the default arithmetic of the path: nothing narrower than fp32), on the
-    // bf16 matrix cores: `wpacked` from lrpx_pack_weights_bf16x3 (taps = 1), no in_amax, any number of rows
-    if (d->taps == 1 && d->bf16x6) {
-        LRPX_REQUIRE(!d->f16x3 && d->epi == EPI_REL && d->x && d->pix_per_map > 0, "conv_mfma: the dense bf16x6 GEMM is built for the REL epilogue (x, pix_per_map)");
-        return launch_dense_bf16x6(a, s);
-    }
-    if (d->taps == 1 && d->f16x3 && d->epi == EPI_PLAIN) {
-        // out0 = in W^T + bias on the fp16 matrix cores (the (T,V) scores of a trace): weights from lrpx_pack_weights_f16x2(PACK_FWD,
-        // taps = 1), in_amax = max|in| per map (rows of a map share one operand scale; pix_per_map = 1: per row)
-        LRPX_REQUIRE(d->f16x3 == 1 && d->in_amax && d->pix_per_map > 0 && d->out0 && !d->out1,
-                     "conv_mfma: the dense f16x3 PLAIN GEMM needs in_amax, pix_per_map and out0");
-        return launch_dense_f16x3(a, s);
-    }
-    if (d->taps == 1 && d->f16x3) {
-        LRPX_REQUIRE(d->f16x3 == 1 && d->epi == EPI_REL && d->x && d->pix_per_map > 0,
-                     "conv_mfma: the dense f16x3 GEMMs are built for the REL / PLAIN epilogues (REL needs x, pix_per_map)");
-        // few rows (the lock-step gate rules): whole K per workgroup, per-row operand scales found while staging
-        if ((long)d->n_maps * d->pix_per_map <= 4096 && d->cin <= 1024 && !d->out1) return launch_dense_small_f16x3(a, s);
-        LRPX_REQUIRE(d->in_amax, "conv_mfma: the many-row dense f16x3 GEMM needs in_amax (max|in| per map)");
-        LRPX_REQUIRE(!d->out1 || d->zdiv || d->stab == STAB_NONE, "conv_mfma: REL out1 needs zdiv");
-        return launch_dense_f16x3(a, s);
-    }
-    // few rows (the decoder's lock-step rules): 32-row tiles, whole K per workgroup (dense_small.hip)
-    if (d->taps == 1 && !d->bf16x6 && !d->f16x3 && dense_small_fits(a)) {
-        LRPX_REQUIRE(d->epi != EPI_REL || d->x, "conv_mfma: REL needs x");
-        return launch_dense_small(a, s);
-    }
-    // dense GEMMs with few rows are latency-bound by one wave's serial MFMA chain over K: split K over blockIdx.y and
-    // add the partial results atomically (outputs zeroed first).  Only where the epilogue is linear in the accumulator.
-    a.ksplit = 1;
-    if (d->taps == 1 && (long)d->n_maps * a.pix_per_map <= 2048 && d->cin >= 4 * kc && !d->out1 &&
-        ((d->epi == EPI_REL) || (d->epi == EPI_PLAIN && !d->relu))) {
-        a.ksplit = d->cin / kc >= 16 ? 4 : 2;
-        const int ncol = d->oc_split;
-        LRPX_TRY(clear_async(d->out0, (size_t)d->n_maps * a.pix_per_map * ncol * sizeof(float), s));
-    }
-    LRPX_REQUIRE(a.pix_per_map > 0, "conv_mfma: pix_per_map must be positive");
-    LRPX_REQUIRE((long)a.n_maps * a.pix_per_map < 0x7fffffffL, "conv_mfma: too many pixels for 32-bit indexing");
-    switch (d->epi) {
-        case EPI_FWD_DUAL: LRPX_REQUIRE(d->out0 && d->out1 && 2 * d->oc_split <= d->n_oc, "conv_mfma: FWD_DUAL needs out0,out1"); break;
-        case EPI_REL: LRPX_REQUIRE(d->x && (d->out0 || d->out1) && (!d->out1 || d->zdiv || d->stab == STAB_NONE), "conv_mfma: REL needs x and (out0|out1,zdiv)"); break;
-        case EPI_FIRST: LRPX_REQUIRE(d->x && d->out0, "conv_mfma: FIRST needs x,out0"); break;
-        case EPI_PLAIN: LRPX_REQUIRE(d->out0, "conv_mfma: PLAIN needs out0"); break;
-        case EPI_GUIDED: LRPX_REQUIRE(d->out0 && d->x, "conv_mfma: GUIDED needs x,out0"); break;
-        case EPI_REL_MUL: LRPX_REQUIRE(d->x && (d->f16x3 || d->bf16x6) && (!d->out0 != !d->out1), "conv_mfma: REL_MUL is the epilogue of the split-product kernels (f16x3 / bf16x6; needs x and exactly one of out0 / out1)"); break;
-        default: LRPX_REQUIRE(false, "conv_mfma: epilogue %d not built", d->epi);
-    }
-    if (d->f16x3) {
-        // (internal: K split of the PLAIN epilogue, partial sums per split behind each other in out0)
-        a.ksplit = (d->epi == EPI_PLAIN && f16_ksplit > 1 && (d->cin / 16) % f16_ksplit == 0) ? f16_ksplit : 1;
-        LRPX_REQUIRE(d->taps == 9 && d->cin % 16 == 0 && d->in_amax && !d->bf16x6 &&
-                         ((d->epi == EPI_REL_MUL && d->x) || (d->epi == EPI_GUIDED && d->f16x3 == 2 && d->x) ||
-                          ((d->epi == EPI_FWD_DUAL || d->epi == EPI_GUIDED || (d->epi == EPI_PLAIN && !d->relu && !d->bias)) &&
-                           !d->pool_am)),
-                     "conv_mfma: f16x3 needs a 3x3 conv, cin %% 16 == 0, in_amax and the REL_MUL (with x), FWD_DUAL, GUIDED "
-                     "or bias-free PLAIN epilogue");
-        LRPX_REQUIRE(d->f16x3 != 2 || d->epi == EPI_REL_MUL || d->epi == EPI_GUIDED || d->epi == EPI_PLAIN,
-                     "conv_mfma: the f16+f8 kernels (f16x3 = 2) are built for the REL_MUL, GUIDED and PLAIN epilogues");
-        // the mode-3 relevance kernels (f16x3 = 2, REL_MUL) are built for the BLOCKED layout of in / x / out only (blocked.h,
-        // lrpx_nhwc_to_blocked); everything else takes NHWC
-        // the mode-3 relevance kernels (f16x3 = 2, REL_MUL) take `in` in the BLOCKED layout (blocked.h, lrpx_nhwc_to_blocked) and, except the
-        // 224 x 224 one (conv1_2: NHWC multiplicand, NHWC / channel-chunked output for the first-layer kernel), x and the output too
-        if (d->f16x3 == 2 && d->epi == EPI_REL_MUL) {
-            if (d->hw == 224)
-                LRPX_REQUIRE(d->blocked == 1 && !d->in_chunked, "conv_mfma: the 224x224 f16x3 = 2 REL_MUL kernel takes `in` blocked (blocked = 1), x / out NHWC");
-            else
-                LRPX_REQUIRE(d->blocked == 7 && d->oc_split % 16 == 0 && !d->in_chunked && !d->out_chunk,
-                             "conv_mfma: f16x3 = 2 with REL_MUL takes in / x / out in the blocked layout (blocked = 7, oc_split %% 16 == 0, no chunk options)");
-        } else {
-            LRPX_REQUIRE(d->blocked == 0, "conv_mfma: only the f16x3 = 2 REL_MUL kernels take the blocked layout");
-        }
-        if (d->f16x3 == 2 && d->epi == EPI_GUIDED && d->pool_am) {
-            LRPX_REQUIRE((long)d->n_maps * (d->hw / 2) * (d->hw / 2) * d->cin < 0x7fffffffL,
-                         "conv_mfma: too many (image, pooled pixel, channel) elements for the pooled-input kernel");
-            if (d->hw == 224 && d->n_oc <= 64) return launch_h8_224_pool_guided(a, s);
-            if (d->hw == 112 && d->n_oc > 64 && d->n_oc <= 128) return launch_h8_112_pool_guided(a, s);
-            if (d->hw == 56 && d->n_oc >= 256) return launch_h8_56w_pool_guided(a, s);
-            if (d->hw == 28 && d->n_oc >= 256) return launch_h8_28w_pool_guided(a, s);
-            LRPX_REQUIRE(false, "conv_mfma: no pooled-input f16+f8 GUIDED kernel built for hw=%d n_oc=%d", d->hw, d->n_oc);
-        }
-        if (d->f16x3 == 2 && d->epi == EPI_GUIDED) {
-            if (d->n_oc >= 256 && d->hw == 56) return launch_h8_56w_guided(a, s);
-            if (d->n_oc >= 256 && d->hw == 28) return launch_h8_28w_guided(a, s);
-            if (d->n_oc >= 256 && d->hw == 14) return launch_h8_14w_guided(a, s);
-            if (d->hw == 224 && d->n_oc <= 64) return launch_h8_224_guided(a, s);
-            if (d->hw == 112 && d->n_oc > 64) return launch_h8_112_guided(a, s);
-            if (d->hw == 112) return launch_h8_112n_guided(a, s);
-            if (d->hw == 56) return launch_h8_56_guided(a, s);
-            if (d->hw == 28) return launch_h8_28_guided(a, s);
-            if (d->hw == 14) return launch_h8_14_guided(a, s);
-            LRPX_REQUIRE(false, "conv_mfma: no f16+f8 GUIDED kernel built for hw=%d n_oc=%d", d->hw, d->n_oc);
-        }
-        if (d->f16x3 == 2 && d->epi == EPI_PLAIN) {
-            if (d->n_oc >= 256 && d->hw == 28) return launch_h8_28w_plain(a, s);
-            if (d->n_oc >= 256 && d->hw == 14) return launch_h8_14w_plain(a, s);
-            if (d->hw == 112 && d->n_oc <= 64) return launch_h8_112n_plain(a, s);
-            if (d->hw == 56) return launch_h8_56_plain(a, s);
-            if (d->hw == 28) return launch_h8_28_plain(a, s);
-            if (d->hw == 14) return launch_h8_14_plain(a, s);
-            LRPX_REQUIRE(false, "conv_mfma: no f16+f8 PLAIN kernel built for hw=%d n_oc=%d", d->hw, d->n_oc);
-        }
-        if (d->epi == EPI_GUIDED) {
-            if (d->hw == 224 && d->n_oc <= 64) return launch_h3_224_guided(a, s);
-            if (d->hw == 112 && d->n_oc > 64) return launch_h3_112_guided(a, s);
-            if (d->hw == 56) return launch_h3_56_guided(a, s);
-            if (d->hw == 28) return launch_h3_28_guided(a, s);
-            if (d->hw == 14) return launch_h3_14_guided(a, s);
-            LRPX_REQUIRE(false, "conv_mfma: no f16x3 GUIDED kernel built for hw=%d n_oc=%d", d->hw, d->n_oc);
-        }
-        if (d->epi == EPI_PLAIN) {
-            if (d->hw == 112 && d->n_oc <= 64) return launch_h3_112n_plain(a, s);
-            if (d->hw == 56) return launch_h3_56_plain(a, s);
-            if (d->hw == 28) return launch_h3_28_plain(a, s);
-            if (d->hw == 14) return launch_h3_14_plain(a, s);
-            LRPX_REQUIRE(false, "conv_mfma: no f16x3 PLAIN kernel built for hw=%d n_oc=%d", d->hw, d->n_oc);
-        }
-        if (d->epi == EPI_FWD_DUAL) {
-            if (d->hw == 224) return launch_h3_224_fwd(a, s);
-            if (d->hw == 112) return launch_h3_112_fwd(a, s);
-            if (d->hw == 56) return launch_h3_56_fwd(a, s);
-            if (d->hw == 28) return launch_h3_28_fwd(a, s);
-            if (d->hw == 14) return launch_h3_14_fwd(a, s);
-            LRPX_REQUIRE(false, "conv_mfma: no f16x3 forward kernel built for hw=%d", d->hw);
-        }
-        const bool f8 = d->f16x3 == 2;
-        if (d->pool_am) {
-            // the kernels index pool_am with 32-bit element offsets (image * pooled pixels * channels)
-            LRPX_REQUIRE((long)d->n_maps * (d->hw / 2) * (d->hw / 2) * d->cin < 0x7fffffffL,
-                         "conv_mfma: too many (image, pooled pixel, channel) elements for the pooled-input kernel");
-            if (f8) {
-                if (d->hw == 56 && d->n_oc >= 256) return launch_h8_56w_pool(a, s);
-                if (d->hw == 28 && d->n_oc >= 256) return launch_h8_28w_pool(a, s);
-                if (d->hw == 224 && d->n_oc <= 64) return launch_h8_224_pool(a, s);
-                if (d->hw == 112 && d->n_oc > 64) return launch_h8_112_pool(a, s);
-                if (d->hw == 56) return launch_h8_56_pool(a, s);
-                if (d->hw == 28) return launch_h8_28_pool(a, s);
-                LRPX_REQUIRE(false, "conv_mfma: no pooled-input f16+f8 kernel built for hw=%d n_oc=%d", d->hw, d->n_oc);
-            }
-            if (d->hw == 224 && d->n_oc <= 64) return launch_h3_224_pool(a, s);
-            if (d->hw == 112 && d->n_oc > 64) return launch_h3_112_pool(a, s);
-            if (d->hw == 56) return launch_h3_56_pool(a, s);
-            if (d->hw == 28) return launch_h3_28_pool(a, s);
-            LRPX_REQUIRE(false, "conv_mfma: no pooled-input f16x3 kernel built for hw=%d n_oc=%d", d->hw, d->n_oc);
-        }
-        if (f8) {
-            // 256 output channels and more: 8-wave workgroups (256 channels per workgroup, ONE workgroup per CU).  The chain
-            // alone is as fast as with two 4-wave workgroups per CU (20.9 ms either way), but the step with batches in
-            // flight is 2 % faster (12 410 -> 12 690 maps/s sustained, tools/ab_bench.sh): one double-buffered tile per CU
-            // instead of two leaves LDS for the other batches' kernels.
-            if (d->n_oc >= 256 && d->hw == 56) return launch_h8_56w_rel(a, s);
-            if (d->n_oc >= 256 && d->hw == 28) return launch_h8_28w_rel(a, s);
-            if (d->n_oc >= 256 && d->hw == 14) return launch_h8_14w_rel(a, s);
-            if (d->hw == 224) return launch_h8_224_rel(a, s);
-            if (d->hw == 112) return d->n_oc <= 64 ? launch_h8_112n_rel(a, s) : launch_h8_112_rel(a, s);
-            if (d->hw == 56) return launch_h8_56_rel(a, s);
-            if (d->hw == 28) return launch_h8_28_rel(a, s);
-            if (d->hw == 14) return launch_h8_14_rel(a, s);
-            LRPX_REQUIRE(false, "conv_mfma: no f16+f8 kernel built for hw=%d", d->hw);
-        }
-        if (d->hw == 224) return launch_h3_224_rel(a, s);
-        if (d->hw == 112) return d->n_oc <= 64 ? launch_h3_112n_rel(a, s) : launch_h3_112_rel(a, s);
-        if (d->hw == 56) return launch_h3_56_rel(a, s);
-        if (d->hw == 28) return launch_h3_28_rel(a, s);
-        if (d->hw == 14) return launch_h3_14_rel(a, s);
-        LRPX_REQUIRE(false, "conv_mfma: no f16x3 kernel built for hw=%d", d->hw);
-    }
-    if (d->bf16x6) {
-        LRPX_REQUIRE(d->taps == 9 && d->cin % 16 == 0, "conv_mfma: bf16x6 needs a 3x3 conv, cin %% 16 == 0");
-        LRPX_REQUIRE(d->blocked == 0 && (!d->pool_am || d->epi == EPI_REL_MUL || d->epi == EPI_GUIDED),
-                     "conv_mfma: bf16x6 takes NHWC tensors; pool_am needs the REL_MUL or GUIDED epilogue");
-        a.ksplit = (d->epi == EPI_PLAIN && f16_ksplit > 1 && (d->cin / 16) % f16_ksplit == 0) ? f16_ksplit : 1;
-        if (d->epi == EPI_GUIDED && d->pool_am) {
-            LRPX_REQUIRE((long)d->n_maps * (d->hw / 2) * (d->hw / 2) * d->cin < 0x7fffffffL,
-                         "conv_mfma: too many (image, pooled pixel, channel) elements for the pooled-input kernel");
-            if (d->hw == 224 && d->n_oc <= 64) return launch_b6_224_pool_guided(a, s);
-            if (d->hw == 112 && d->n_oc > 64) return launch_b6_112_pool_guided(a, s);
-            if (d->hw == 56) return launch_b6_56_pool_guided(a, s);
-            if (d->hw == 28) return launch_b6_28_pool_guided(a, s);
-            LRPX_REQUIRE(false, "conv_mfma: no pooled-input bf16x6 GUIDED kernel built for hw=%d n_oc=%d", d->hw, d->n_oc);
-        }
-        if (d->epi == EPI_GUIDED) {
-            if (d->hw == 112 && d->n_oc <= 64) return launch_b6_112n_guided(a, s);
-            if (d->hw == 56) return launch_b6_56_guided(a, s);
-            if (d->hw == 28) return launch_b6_28_guided(a, s);
-            if (d->hw == 14) return launch_b6_14_guided(a, s);
-            LRPX_REQUIRE(false, "conv_mfma: no bf16x6 GUIDED kernel built for hw=%d n_oc=%d", d->hw, d->n_oc);
-        }
-        if (d->epi == EPI_PLAIN) {
-            LRPX_REQUIRE(d->hw <= 56 && !d->relu && !d->bias, "conv_mfma: the bf16x6 PLAIN kernels are built for 56 / 28 / 14-pixel maps, no bias / ReLU (the K-split forward)");
-            if (d->hw == 56) return launch_b6_56_plain(a, s);
-            if (d->hw == 28) return launch_b6_28_plain(a, s);
-            return launch_b6_14_plain(a, s);
-        }
-        if (d->epi == EPI_REL_MUL && d->pool_am) {
-            // the conv sits under a 2x2 max-pool: `in` at the pool's output resolution, unpooled while staged (conv_f16x3.h, POOL + B6)
-            LRPX_REQUIRE((long)d->n_maps * (d->hw / 2) * (d->hw / 2) * d->cin < 0x7fffffffL,
-                         "conv_mfma: too many (image, pooled pixel, channel) elements for the pooled-input kernel");
-            if (d->hw == 224 && d->n_oc <= 64) return launch_b6_224_pool(a, s);
-            if (d->hw == 112 && d->n_oc > 64) return launch_b6_112_pool(a, s);
-            if (d->hw == 56) return launch_b6_56_pool(a, s);
-            if (d->hw == 28) return launch_b6_28_pool(a, s);
-            LRPX_REQUIRE(false, "conv_mfma: no pooled-input bf16x6 kernel built for hw=%d n_oc=%d", d->hw, d->n_oc);
-        }
-        if (d->epi == EPI_REL_MUL && d->wpacked_wino && !d->in_chunked && d->n_oc % 64 == 0 && d->hw <= 56 &&
-            (b6_wino_bits() & (d->hw == 56 ? 1 : (d->hw == 28 ? 2 : 4)))) {
-            // Winograd F(2x2,3x3) on the same exact splits (conv_wino_b6.h): chosen by the layer's map size, never by the batch
-            a.wp = reinterpret_cast<const float*>(d->wpacked_wino);
-            if (d->hw == 56) return launch_b6_56_wino(a, s);
-            if (d->hw == 28) return launch_b6_28_wino(a, s);
-            return launch_b6_14_wino(a, s);
-        }
-        if (d->epi == EPI_REL_MUL) {
-            if (d->hw == 224 && d->n_oc <= 64) return launch_b6_224_rel(a, s);
-            if (d->hw == 112) return d->n_oc <= 64 ? launch_b6_112n_rel(a, s) : launch_b6_112_rel(a, s);
-            if (d->hw == 56) return launch_b6_56_rel(a, s);
-            if (d->hw == 28) return launch_b6_28_rel(a, s);
-            if (d->hw == 14) return launch_b6_14_rel(a, s);
-            LRPX_REQUIRE(false, "conv_mfma: no bf16x6 REL_MUL kernel built for hw=%d n_oc=%d", d->hw, d->n_oc);
-        }
-        if (d->epi == EPI_REL) {
-            if (d->hw == 224) return launch_x6_224_rel(a, s);
-            if (d->hw == 112) return d->n_oc <= 64 ? launch_x6_112n_rel(a, s) : launch_x6_112_rel(a, s);
-            if (d->hw == 56) return launch_x6_56_rel(a, s);
-            if (d->hw == 28) return launch_x6_28_rel(a, s);
-            if (d->hw == 14) return launch_x6_14_rel(a, s);
-        }
-        if (d->epi == EPI_FWD_DUAL) {
-            // (the act | Z+ halves of a tile's 32-channel output blocks must not straddle oc_split)
-            LRPX_REQUIRE(d->oc_split % 32 == 0, "conv_mfma: the bf16x6 FWD_DUAL kernels need oc_split %% 32 == 0 (oc_split=%d)", d->oc_split);
-            if (d->hw == 224) return launch_b6_224_fwd(a, s);
-            if (d->hw == 112) return launch_b6_112_fwd(a, s);
-            if (d->hw == 56) return launch_b6_56_fwd(a, s);
-            if (d->hw == 28) return launch_b6_28_fwd(a, s);
-            if (d->hw == 14) return launch_b6_14_fwd(a, s);
-        }
-        LRPX_REQUIRE(false, "conv_mfma: no bf16x6 kernel built for hw=%d epi=%d", d->hw, d->epi);
-    }
-    if (d->taps == 1) {
-        if (d->epi == EPI_REL) return launch_conv_14_32_1_4_1_rel(a, s);
-        if (d->epi == EPI_PLAIN) return launch_conv_14_32_1_4_1_plain(a, s);
-        LRPX_REQUIRE(false, "conv_mfma: dense supports REL / PLAIN epilogues only");
-    }
-    const int e = d->epi;
-    switch (d->hw) {
-        case 224:
-            if (e == EPI_FWD_DUAL) return launch_conv_224_8_1_4_9_fwd_dual(a, s);
-            if (e == EPI_REL) return launch_conv_224_8_2_2_9_rel(a, s);
-            if (e == EPI_GUIDED) return launch_conv_224_8_2_2_9_guided(a, s);
-            if (e == EPI_PLAIN) return launch_conv_224_8_1_4_9_plain(a, s);
-            break;
-        case 112:
-            if (e == EPI_FWD_DUAL) return launch_conv_112_8_1_4_9_fwd_dual(a, s);
-            if (e == EPI_REL) return d->n_oc <= 64 ? launch_conv_112_8_2_2_9_rel(a, s) : launch_conv_112_8_1_4_9_rel(a, s);
-            if (e == EPI_GUIDED) return launch_conv_112_8_1_4_9_guided(a, s);
-            if (e == EPI_PLAIN) return launch_conv_112_8_2_2_9_plain(a, s);
-            break;
-        case 56:
-            if (e == EPI_FWD_DUAL) return launch_conv_56_16_1_4_9_fwd_dual(a, s);
-            if (e == EPI_REL) return launch_conv_56_16_1_4_9_rel(a, s);
-            if (e == EPI_GUIDED) return launch_conv_56_16_1_4_9_guided(a, s);
-            if (e == EPI_PLAIN) return launch_conv_56_16_1_4_9_plain(a, s);
-            break;
-        case 28:
-            if (e == EPI_FWD_DUAL) return launch_conv_28_16_1_4_9_fwd_dual(a, s);
-            if (e == EPI_REL) return launch_conv_28_16_1_4_9_rel(a, s);
-            if (e == EPI_GUIDED) return launch_conv_28_16_1_4_9_guided(a, s);
-            if (e == EPI_PLAIN) return launch_conv_28_16_1_4_9_plain(a, s);
-            break;
-        case 14:
-            if (e == EPI_FWD_DUAL) return launch_conv_14_16_1_4_9_fwd_dual(a, s);
-            if (e == EPI_REL) return launch_conv_14_16_1_4_9_rel(a, s);
-            if (e == EPI_GUIDED) return launch_conv_14_16_1_4_9_guided(a, s);
-            if (e == EPI_PLAIN) return launch_conv_14_16_1_4_9_plain(a, s);
-            break;
-    }
-    set_error("conv_mfma: no kernel built for hw=%d epi=%d", d->hw, d->epi);
-    return LRPX_EINVAL;
-}
 
 // ------------------------------------------------------------------------------------------------
 // VGG16 geometry (cfg 'D' without the last pool)
@@ -609,21 +311,6 @@ static VggTrace vgg_trace_layout(int n_img) {
 using namespace lrpx;
 
 extern "C" {
-
-int lrpx_conv_kc(int hw, int taps, int cin) {
-    if (taps == 1) return 32;
-    (void)cin;
-    if (hw >= 112) return 8;    // two LDS buffers of (rows+halo) x (W+2) pixels must fit: narrower chunks on wide maps
-    return 16;
-}
-
-int lrpx_conv_mfma(const lrpx_conv_desc* d, void* stream) {
-    LRPX_REQUIRE(d, "conv_mfma: null descriptor");
-    LRPX_CHECK_PTRS("lrpx_conv_mfma", {d->in, "in"}, {d->wpacked, "wpacked"}, {d->bias, "bias"}, {d->x, "x"}, {d->u, "u"}, {d->zdiv, "zdiv"},
-                    {d->map2img, "map2img"}, {d->out0, "out0"}, {d->out1, "out1"}, {d->in_amax, "in_amax"}, {d->out1_amax, "out1_amax"},
-                    {d->out0_amax, "out0_amax"}, {d->pool_am, "pool_am"});
-    return conv_dispatch(d, (hipStream_t)stream);
-}
 
 int lrpx_set_bf16x6(int enable) {
     if (enable >= 0) return g_default_mode.exchange(enable ? 1 : 0) >= 1;

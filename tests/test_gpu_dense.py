@@ -65,6 +65,33 @@ def test_dense_plain_few_rows(ops, rows, k, n, relu):
     assert rel_err(out.cpu(), want) < 2e-6
 
 
+def test_dense_plain_atomic_k_split_clears_its_output(ops):
+    """64 rows, K = 16384 (beyond dense_small.hip's 8192), fp32, PLAIN without ReLU: the one shape class that still takes the atomic
+    K split of the fp32 conv_mfma kernel (lrpx_conv_kernel_name: conv_14_32_1_4_1_plain ks=4) - four K ranges added atomically
+    into out0, which conv_dispatch zeroes first (between selection and launch).  out0 arrives filled with 7.25; against the fp64
+    product with test_dense_plain_few_rows's bound (2e-6 of the maximum; fp32 accumulation over 4096 terms per range; measured
+    1.42e-6, and the order of the four atomic additions moves that by an ulp of the result, 6e-8, at most)."""
+    import ctypes as C
+    from lrp_amd import _lib
+    rows, k, n = 64, 16384, 32
+    g = torch.Generator().manual_seed(rows * 3 + k)
+    a = torch.randn(rows, k, generator=g)
+    w = torch.randn(n, k, generator=g) * 0.05
+    b = torch.randn(n, generator=g)
+    ad, bd = a.cuda(), b.cuda()
+    wp = ops.pack_weights(w.cuda(), n, k, 1, _lib.PACK_DENSE, 32)
+    out = torch.full((rows, n), 7.25, device="cuda")
+    kw = dict(pix_per_map=1, oc_split=n, bias=bd, out0=out)
+    buf = C.create_string_buffer(96)
+    assert _lib.load().lrpx_conv_kernel_name(C.byref(ops.conv_desc(ad, wp, rows, 0, k, n, 1, _lib.EPI_PLAIN, **kw)), buf, len(buf)) == _lib.OK
+    assert buf.value == b"conv_14_32_1_4_1_plain ks=4 tg=0"
+    ops.conv_mfma(ad, wp, rows, 0, k, n, 1, _lib.EPI_PLAIN, **kw)
+    torch.cuda.synchronize()
+    err = rel_err(out.cpu(), a.double() @ w.double().t() + b.double())
+    print(f"dense PLAIN, atomic K split ({rows} x {k} -> {n}): {err:.2e} of the maximum")
+    assert err < 2e-6
+
+
 @pytest.mark.parametrize("n_maps,P,k,n,n_img", [(40, 196, 512, 512, 4), (23, 36, 512, 2048, 5), (3, 36, 64, 96, 2), (320, 196, 512, 512, 16)])
 def test_dense_f16x3_rel_many_rows(ops, n_maps, P, k, n, n_img):
     """The (word, pixel) epsilon rules of the decoders on the fp16 matrix cores (csrc/dense_f16x3.hip):

@@ -1,7 +1,8 @@
 #!/bin/bash
-# VGPRs / spills / scratch of every kernel in the given instantiation files (csrc/conv_inst_<name>.hip ...)
+# VGPRs / spills / scratch of every kernel in the given units of csrc/conv_kernels.def (csrc/conv_inst_<unit>.hip, written by make)
 # usage: tools/kernel_regs.sh h8 h8w ...   [EXTRA="-D..."]
 cd "$(dirname "$0")/../lrp-imagecaptioning-pytorch_amd/csrc"
+make -s $(printf 'conv_inst_%s.hip ' "$@")
 for f in "$@"; do
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-function $EXTRA -c conv_inst_$f.hip -o /tmp/kr_$$.o \
       -Rpass-analysis=kernel-resource-usage 2>&1 | python3 -c '

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Phase breakdown of the bf16x6 conv kernels of conv_inst_x6.hip (56/28/14 relevance) from s_memtime stamps.
+"""Phase breakdown of the bf16x6 conv kernels of unit x6 of csrc/conv_kernels.def (56/28/14 relevance) from s_memtime stamps.
 Needs a profiling build: make -C lrp-imagecaptioning-pytorch_amd/csrc clean && make ... STAMP=1"""
 import ctypes as C
 import os

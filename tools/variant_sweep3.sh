@@ -1,5 +1,5 @@
 #!/bin/bash
-# On the GPU box: rebuild the f16+f8 instantiation files (conv_inst_h8*) with different -D flags and print the chain's
+# On the GPU box: rebuild the f16+f8 kernel units (build/conv_inst_h8*.o, units of csrc/conv_kernels.def) with different -D flags and print the chain's
 # per-layer conv times (bench.py --conv-mode 3, HIP events around every launch).
 # usage: tools/variant_sweep3.sh "<flags1>" "<flags2>" ...
 cd $(dirname $0)/..
