@@ -1,17 +1,39 @@
-// What the decoder files (lrpx_decoder.hip: gridTD and AoA; lrpx_adaatt.hip: the single-LSTM adaptive-attention model) share on the
-// device: the point-wise helpers, the wave / block reductions, the K loop of the skinny linears on the fp32 matrix cores, and the body of
-// `AdaptiveAttention.forward` (models/gridTDmodel.py:71-103 and models/adaptiveattention.py:56-98 are the same module).  One text, so the
-// decoders round alike: a kernel that calls one of these forms the same sums in the same order as every other caller.
+// What the decoder files (decoder_blocks.hip: the model-agnostic kernels; decoder_gridtd.hip, decoder_aoa.hip, lrpx_adaatt.hip: one model
+// each) share: the point-wise helpers, the LSTM cell, the wave / block reductions, the K loop of the skinny linears on the fp32 matrix cores
+// with the sum of its four K-slices, the body of `AdaptiveAttention.forward` (models/gridTDmodel.py:71-103 and
+// models/adaptiveattention.py:56-98 are the same module), and on the host the choice of the row tile.  One text, so the decoders round
+// alike: a kernel that calls one of these forms the same sums in the same order as every other caller.
 #pragma once
 #include <math.h>
+
+#include <type_traits>
 
 #include "common.h"
 #include "conv_mfma.h"
 
 namespace lrpx {
 
+// host: the row tile RT (16 rows each) of the matrix-core kernels for B <= 64 rows; calls f(std::integral_constant<int, RT>{})
+template <class F>
+auto with_row_tiles(int B, F&& f) {
+    if (B <= 16) return f(std::integral_constant<int, 1>{});
+    if (B <= 32) return f(std::integral_constant<int, 2>{});
+    if (B <= 48) return f(std::integral_constant<int, 3>{});
+    return f(std::integral_constant<int, 4>{});
+}
+
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 __device__ __forceinline__ float eps_id(float r, float x, float z) { return (x / stab_eps(z)) * r; }   // weight=eye rule
+
+// The LSTM cell of every decoder (models/gridTDmodel.py:777-784, models/aoamodel.py:1030-1033, models/adaptiveattention.py:554-565) from the
+// four pre-activations of one hidden unit and its old cell state: the gates and the new cell state; the caller forms h = o tanh(cn) and
+// keeps what its trace wants (the g gate is traced as the pre-activation zg itself).
+struct LstmCell { float i, f, o, cn; };
+__device__ __forceinline__ LstmCell lstm_cell(float zi, float zf, float zg, float zo, float c_old) {
+    const float i = sigmoidf_(zi), f = sigmoidf_(zf), o = sigmoidf_(zo);
+    const float cn = f * c_old + i * tanhf(zg);
+    return {i, f, o, cn};
+}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -95,6 +117,12 @@ __device__ __forceinline__ void linear_mfma_core(const float* __restrict__ x, lo
 #pragma unroll
         for (int i = 0; i < 4; ++i) red[wv_][r][4 * kq + i][nl] = (acc[r][0][i] + acc[r][1][i]) + (acc[r][2][i] + acc[r][3][i]);
     __syncthreads();
+}
+
+// ... and what every caller reads back: element (row tile r, row, col) of the product, the four K-slices summed in wave order
+template <int RT>
+__device__ __forceinline__ float red4(const float (&red)[4][RT][16][17], int r, int row, int col) {
+    return (red[0][r][row][col] + red[1][r][row][col]) + (red[2][r][row][col] + red[3][r][row][col]);
 }
 
 // AdaptiveAttention.forward (models/gridTDmodel.py:71-103 = models/adaptiveattention.py:56-98), two kernels so that the rows fill the chip:

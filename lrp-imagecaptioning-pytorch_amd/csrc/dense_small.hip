@@ -220,7 +220,7 @@ __global__ __launch_bounds__(256, 2) void dense_slab_kernel(ConvArgs a, int m_ti
 // (deterministic).  Round 6: also the epsilon rule of the decoders' lock-steps in the exact modes (REL epilogue) - against the
 // one-wave kernel above 20 -> 12 us per lock-step GEMM, the one-image drop-in's decoder relevance 1.14 -> 0.97 ms.  (Rounds 3 - 5
 // kept the rule on the one-wave kernel because this order moved ONE T = 20 word relevance of the LRP goldens above its 1e-5 bound; with
-// the round-6 K loop of the trace linears - lrpx_decoder.hip, linear_mfma_core - the worst row sits at 9.2e-6 in this order, 9.9e-6 in
+// the round-6 K loop of the trace linears - decoder_shared.h, linear_mfma_core - the worst row sits at 9.2e-6 in this order, 9.9e-6 in
 // the other: the row is carried by the encoder features' own 1.8e-6, tests/diag_t20_words.py.)
 // FUSE (round 6): lock-step s of the AoA decoder relevance (models/aoamodel.py:1114-1134) in this kernel's epilogue - what FUSE of
 // dense_small_f16x3_kernel (dense_f16x3.hip) is for the fp16 split products, here in the exact arithmetic of the default mode: the product

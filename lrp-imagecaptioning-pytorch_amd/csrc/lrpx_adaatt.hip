@@ -53,14 +53,14 @@ __global__ void adaatt_fwd_inputs_kernel(AdaFwd g, int t, const float* __restric
 __device__ __forceinline__ void adaatt_cell(const AdaFwd& g, int b, int t, int c, const float (&z)[5]) {
     const int H = g.H;
     const long st0 = ((long)b * (g.T + 1) + t) * H, st1 = st0 + H, tr = ((long)b * g.T + t) * H;
-    const float i = sigmoidf_(z[0]), f = sigmoidf_(z[1]), zg = z[2], o = sigmoidf_(z[3]), sg = sigmoidf_(z[4]);
-    const float cn = f * g.c[st0 + c] + i * tanhf(zg);
-    const float tc = tanhf(cn);
-    const float hn = o * tc;
-    g.c[st1 + c] = cn; g.h[st1 + c] = hn;
-    g.g[tr + c] = zg; g.i[tr + c] = i; g.f[tr + c] = f;
+    const LstmCell l = lstm_cell(z[0], z[1], z[2], z[3], g.c[st0 + c]);
+    const float sg = sigmoidf_(z[4]);
+    const float tc = tanhf(l.cn);
+    const float hn = l.o * tc;
+    g.c[st1 + c] = l.cn; g.h[st1 + c] = hn;
+    g.g[tr + c] = z[2]; g.i[tr + c] = l.i; g.f[tr + c] = l.f;
     g.s[tr + c] = sg * tc;
-    if (g.o) g.o[tr + c] = o;
+    if (g.o) g.o[tr + c] = l.o;
     if (g.sgate) g.sgate[tr + c] = sg;
     if (t + 1 < g.T) g.xh[((long)b * g.T + t + 1) * (H + 2 * g.E) + c] = hn;         // the next step's h columns
 }
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void adaatt_rec_kernel(AdaFwd g, int t, const 
 #pragma unroll
         for (int q = 0; q < 5; ++q) {
             const int col = 5 * u + q;
-            z[q] = ((red[0][r][row][col] + red[1][r][row][col]) + (red[2][r][row][col] + red[3][r][row][col])) + zi[col];
+            z[q] = red4<RT>(red, r, row, col) + zi[col];
         }
         adaatt_cell(g, b, t, c, z);
     }
@@ -335,10 +335,7 @@ int lrpx_adaatt_fwd_recurrence(const lrpx_adaatt_trace* tr, const float* w_hh_il
         const AdaFwd g = to_fwd(&sub);
         const float* z = zin + (long)b0 * tr->T * 16 * NG;
         for (int t = 0; t < tr->T; ++t) {
-            if (sub.B <= 16) hipLaunchKernelGGL((adaatt_rec_kernel<1>), dim3(NG), dim3(256), 0, st, g, t, w_hh_il, z);
-            else if (sub.B <= 32) hipLaunchKernelGGL((adaatt_rec_kernel<2>), dim3(NG), dim3(256), 0, st, g, t, w_hh_il, z);
-            else if (sub.B <= 48) hipLaunchKernelGGL((adaatt_rec_kernel<3>), dim3(NG), dim3(256), 0, st, g, t, w_hh_il, z);
-            else hipLaunchKernelGGL((adaatt_rec_kernel<4>), dim3(NG), dim3(256), 0, st, g, t, w_hh_il, z);
+            with_row_tiles(sub.B, [&](auto rt) { hipLaunchKernelGGL((adaatt_rec_kernel<decltype(rt)::value>), dim3(NG), dim3(256), 0, st, g, t, w_hh_il, z); });
             LRPX_TRY(check_launch("adaatt_rec"));
         }
     }

@@ -2,7 +2,7 @@
 
 Reference: models/gridTDmodel.py:705-1211 (`ExplainGridTDAttention`).  The reference explains one
 image at a time with ~50k tiny tensor ops per image; here a batch of B images x T words is traced
-and explained in lock-step by HIP kernels behind the lrpx C ABI (see csrc/lrpx_decoder.hip).
+and explained in lock-step by HIP kernels behind the lrpx C ABI (see csrc/decoder_gridtd.hip; the model-agnostic kernels: csrc/decoder_blocks.hip).
 The host logic below only sequences kernel launches; torch is used for device memory."""
 import ctypes as C
 
@@ -477,7 +477,7 @@ class GridTDBUEngine(GridTDEngine):
     The decoder is `GridTDEngine`'s.  The image side differs (:1912-1915): the global feature is
     relu(global_img_feature_proj(mean_k relu(img_projector(F))[k])) - the mean of the PROJECTED regions -, so its relevance returns under
     the projector rule: r_avg = eps(r_glob, avg, glob_pre, W_gp), r_vp[k] = r_proj[k] + eps(r_avg, Vp[k] / P, avg, eye),
-    r_feat[k] = eps(r_vp[k], F[k], proj_pre[k], W_proj) (`_rel_tail`; csrc/lrpx_decoder.hip: lrpx_gridtd_rel_pix_rows_avg).  The
+    r_feat[k] = eps(r_vp[k], F[k], proj_pre[k], W_proj) (`_rel_tail`; csrc/decoder_gridtd.hip: lrpx_gridtd_rel_pix_rows_avg).  The
     region relevance (B, T, P, C) is the result: there is no CNN stage, no running sum, and no gradient explainer (the reference
     defines none for this model).  DESIGN.md 5.14."""
 

@@ -1,4 +1,4 @@
-"""The decoder FORWARD traces of csrc/lrpx_decoder.hip and csrc/lrpx_adaatt.hip restated time step by time step in plain torch, from the formulae
+"""The decoder FORWARD traces of csrc/decoder_gridtd.hip, csrc/decoder_aoa.hip and csrc/lrpx_adaatt.hip restated time step by time step in plain torch, from the formulae
 of the reference (models/gridTDmodel.py, models/aoamodel.py, models/adaptiveattention.py: line numbers at each step, as in the .hip comments and
 oracle/lrp_oracle.py), from ANY initial state - and the planted models and drawn inputs the kernel tests run them on.  A helper module, not a
 conftest.

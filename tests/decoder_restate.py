@@ -1,4 +1,4 @@
-"""The four decoder back-passes of csrc/lrpx_decoder.hip restated row by row in plain torch, from the formulae of the reference
+"""The four decoder back-passes of csrc/decoder_gridtd.hip and csrc/decoder_aoa.hip restated row by row in plain torch, from the formulae of the reference
 (models/gridTDmodel.py, models/aoamodel.py: line numbers at each step, as in the .hip comments and oracle/lrp_oracle.py), on trace
 tensors of ANY values - and the drawn traces the kernel tests run them on.  A helper module, not a conftest.
 

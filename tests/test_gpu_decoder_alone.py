@@ -1,4 +1,4 @@
-"""The four decoder back-passes of csrc/lrpx_decoder.hip ALONE, through the C ABI, on traces of drawn values (tests/decoder_restate.py:
+"""The four decoder back-passes of csrc/decoder_gridtd.hip and csrc/decoder_aoa.hip ALONE, through the C ABI, on traces of drawn values (tests/decoder_restate.py:
 planted exact zeros of both signs and +-0.004 under every stabiliser, a zero logit, an all-zero row), against the fp64 restatement of the
 same file: gridTD relevance (`gridtd_rel_*`), AoA relevance (`aoa_rel_*`, the fused lock-steps of csrc/dense_small.hip and
 csrc/dense_f16x3.hip, `rel_words_norm_parts`), gridTD gradient / guided (`gridtd_grad_*`, `lstm_cell_bwd`, `spread_pixels`) and AoA

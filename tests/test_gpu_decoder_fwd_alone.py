@@ -1,4 +1,4 @@
-"""The decoder FORWARD kernels of csrc/lrpx_decoder.hip and csrc/lrpx_adaatt.hip ALONE, through the C ABI, against the fp64 restatements of
+"""The decoder FORWARD kernels of csrc/decoder_blocks.hip, csrc/decoder_gridtd.hip, csrc/decoder_aoa.hip and csrc/lrpx_adaatt.hip ALONE, through the C ABI, against the fp64 restatements of
 tests/decoder_fwd_restate.py: the building blocks (`lrpx_linear_small` at every row tile and on both kernels, `lrpx_mean_pixels`, `lrpx_relu`,
 `lrpx_target_logit`, the two arg-max kernels), one decoder step of each model from a drawn state, whole traces through every path (per-step,
 fused, decoupled), the recorded row maxima, the engines' `trace`, and the LRP-inference re-weighting.  The kernels receive the engine's OWN packed

@@ -24,8 +24,10 @@ for o in "${objs[@]}"; do
     grep -o '[A-Za-z_][A-Za-z0-9_]*\.kd$' "$tmp/notes.txt" | sed 's/\.kd$//' | sort -u > "$tmp/kernels.txt"
     # (blank lines and the "..." of zero fill between symbols depend on what follows a kernel in its object, not on the kernel)
     "$bin/llvm-objdump" -d --no-leading-addr --no-show-raw-insn "$tmp/x.co" | sed 's,[[:space:]]*//.*$,,' | grep -v '^[[:space:]]*\(\.\.\.\)\?$' > "$tmp/dis.txt"
+    # (nor does the run of s_nop / s_code_end padding behind a section's last kernel belong to that kernel: which kernel is last depends on the object)
     while read -r k; do
-      h=$(awk -v s="<$k>:" '$NF == s { on = 1; next } /^[0-9a-f]* *<.*>:$/ { on = 0 } on' "$tmp/dis.txt" | sha256sum | cut -c1-16)
+      h=$(awk -v s="<$k>:" '$NF == s { on = 1; next } /^[0-9a-f]* *<.*>:$/ { on = 0 } on { a[++n] = $0 }
+                            END { while (n > 0 && a[n] ~ /^[[:space:]]*(s_nop 0|s_code_end)$/) --n; for (i = 1; i <= n; ++i) print a[i] }' "$tmp/dis.txt" | sha256sum | cut -c1-16)
       printf '%-24s %s %s\n' "$o" "$h" "$k"
     done < "$tmp/kernels.txt"
     continue
