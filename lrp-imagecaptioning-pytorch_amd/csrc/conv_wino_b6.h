@@ -16,6 +16,8 @@
 // out = x * Y as in epi_finish<EPI_REL_MUL> (NHWC or channel-chunked output, map2img for the multiplicand).
 // B fragments stream from L2: 32 B/clk/CU, sustainable only while the CUs of an XCD walk the same 64-channel slice
 // (16 xi x K x 64 x 6 B = 3.1 MB at K = 512): workgroups are ordered XCD-contiguous in bands of 32 row blocks.
+// Patch and B loads are buffer loads without control flow around them, so that every s_waitcnt counts them: the patch loads of the
+// next chunk go out between the chunk's two xi steps and are waited for by the commit alone (profiles/wino_wait_isa.txt).
 #pragma once
 #include "conv_bf16x6.h"
 
@@ -26,6 +28,7 @@ constexpr int WINO_XI = 4 * WINO_KQ;       // bytes per xi
 constexpr int WINO_BUF = 16 * WINO_XI;     // bytes per V buffer
 constexpr int WINO_LDS = 2 * WINO_BUF;     // 139 264 B: one workgroup per CU
 constexpr int WINO_MROW = 33;              // floats per (xi, tile) row of the M exchange
+constexpr unsigned WINO_OOB = 0x7fff0000u; // patch-load offset of what is not fetched: beyond the end of every workgroup's buffer resource
 
 // 8 fp32 -> three bf16x8 planes, v == p0 + p1 + p2 exactly
 __device__ __forceinline__ void wino_split8(const f32x4 q0, const f32x4 q1, bf16x8& p0, bf16x8& p1, bf16x8& p2) {
@@ -90,8 +93,14 @@ __global__ __launch_bounds__(512) void conv_wino_b6_kernel(ConvArgs a, int total
     const float sgn = half ? -1.f : 1.f;
     unsigned smask = 0;
     bool take_l = false, take_r = false;     // SHARE: patch column 0 / 3 comes from lane - 4 / lane + 4
-    long sbase;
     int srow[3];                             // patch row of slot a, b, c (wave-uniform)
+    // The patch loads are raw buffer loads through a resource that starts at the workgroup's first map and ends with the tensor
+    // (at most WINO_OOB bytes: the launcher checks that a workgroup's maps fit): a thread issues all twelve of them, every chunk, with
+    // no branch around them, so that the compiler counts them in its vmcnt waits.  What a thread must not fetch (zero padding,
+    // ragged tail, SHARE: the columns it is given) has the offset WINO_OOB: the range check answers with the exact zero, forms no
+    // address and touches no memory.  Every other offset is that of an element of `in`.
+    const int n0 = row0 / TPM;
+    unsigned voff[3][4];
     {
         const int T = row0 + stile;
         const int n = T / TPM, t = T - n * TPM;
@@ -115,19 +124,22 @@ __global__ __launch_bounds__(512) void conv_wino_b6_kernel(ConvArgs a, int total
                 if (take_r) smask &= ~0x888u;
             }
         }
-        sbase = (((long)n * HW + y0) * HW + x0) * a.cin + seg * 4;
+        // under smask the pixel lies in map n >= n0 of the tensor: the offset is >= 0 and below WINO_OOB
+        const int sbase = (((n - n0) * HW + y0) * HW + x0) * a.cin + seg * 4;
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                voff[r][c] = (smask & (1u << (r * 4 + c))) ? (unsigned)(sbase + (srow[r] * HW + c) * a.cin) * 4u : WINO_OOB;
     }
-    // smask never changes: what a thread does not fetch stays the zero it starts as (SHARE: or is overwritten by the exchange)
+    const long left = (long)(a.n_maps - n0) * P * a.cin * 4;
+    const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(a.in) + (long)n0 * P * a.cin, 0, (int)(left < (long)WINO_OOB ? left : (long)WINO_OOB), 0x00020000);
+    // SHARE: the exchange overwrites columns 0 / 3 of the lanes that are given them; the next chunk's loads put their zeros back
     f32x4 rv[3][4];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) rv[r][c] = f32x4{0, 0, 0, 0};
 #define LRPXW_ISSUE(CHUNK)                                                                                          \
-    _Pragma("unroll") for (int r = 0; r < 3; ++r) _Pragma("unroll") for (int c = 0; c < 4; ++c) {                    \
-        if (smask & (1u << (r * 4 + c)))                                                                            \
-            rv[r][c] = *reinterpret_cast<const f32x4*>(a.in + sbase + (long)(srow[r] * HW + c) * a.cin + (CHUNK) * 16); \
-    }
+    _Pragma("unroll") for (int r = 0; r < 3; ++r) _Pragma("unroll") for (int c = 0; c < 4; ++c)                      \
+        rv[r][c] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srsrc, voff[r][c], (CHUNK) * 64, 0));
     // ds_bpermute moves a dword between lanes without a VALU slot (DPP row shifts stop at 16 lanes = 4 tiles); one select per dword.
     // (the element goes through a scalar: __builtin_bit_cast straight on rv[r][c][e] reads element 0 of the vector)
     const int lane_l = ((lane - 4) & 63) * 4, lane_r = ((lane + 4) & 63) * 4;
@@ -171,62 +183,81 @@ __global__ __launch_bounds__(512) void conv_wino_b6_kernel(ConvArgs a, int total
 
     // B fragments [ocb][xi][k-step][plane][64 lanes][16 B]: the fragments of channel block nb are re-loaded for the next
     // (xi, k-step) as soon as its MFMAs are issued, i.e. half a step ahead
-    const u32x4* wp = reinterpret_cast<const u32x4*>(a.wp) + lane;
-    const long ocb_stride = (long)16 * nchunk * 192;
+    // (buffer loads as well: the lane's 16 B in the one address register, fragment and plane in the scalar offset - flat loads
+    // keep four 64-bit addresses in registers that the kernel does not have; the launcher checks that the packed weights stay below 2 GiB)
+    const int ocb_stride = 16 * nchunk * 192;
     const int last_step = 2 * nchunk - 1;
-    auto bptr = [&](int step, int nb) -> const u32x4* {
+    const __amdgpu_buffer_rsrc_t wrsrc =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.wp), 0, n_blocks * 2 * ocb_stride * 16, 0x00020000);
+    const unsigned wlane = lane * 16;
+    auto boff = [&](int step, int nb) -> unsigned {
         const int s = min(step, last_step);
         const int xi = 2 * wave + (s & 1), ks = s >> 1;
-        return wp + (long)(nblk * 2 + nb) * ocb_stride + ((long)xi * nchunk + ks) * 192;
+        return (unsigned)((nblk * 2 + nb) * ocb_stride + (xi * nchunk + ks) * 192) * 16u;
     };
+#define LRPXW_BLOAD(STEP, NB)                                                                                       \
+    _Pragma("unroll") for (int p = 0; p < 3; ++p)                                                                   \
+        bq[NB][p] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wlane, boff(STEP, NB) + p * 1024, 0));
     u32x4 bq[2][3];
 #pragma unroll
-    for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-        for (int p = 0; p < 3; ++p) bq[nb][p] = bptr(0, nb)[p * 64];
+    for (int nb = 0; nb < 2; ++nb) LRPXW_BLOAD(0, nb)
 
     LRPXW_COMMIT(0)
     __syncthreads();
 
-    for (int chunk = 0; chunk < nchunk; ++chunk) {
-        const bool more = chunk + 1 < nchunk;
-        if (more) { LRPXW_ISSUE(chunk + 1) }
+    // one xi step of a chunk: read and split the wave's A fragments, 24 MFMAs; the B fragments of a channel block are re-loaded for
+    // the next step as soon as its MFMAs are issued
+#define LRPXW_STEP(CHUNK, X, VBUF)                                                                                  \
+    {                                                                                                               \
+        const char* vx = (VBUF) + (2 * wave + (X)) * WINO_XI + (2 * lh) * WINO_KQ + li * 16;                        \
+        bf16x8 ap[2][3];                                                                                            \
+        _Pragma("unroll") for (int rt = 0; rt < 2; ++rt) {                                                          \
+            const f32x4 q0 = *reinterpret_cast<const f32x4*>(vx + rt * 512);                                        \
+            const f32x4 q1 = *reinterpret_cast<const f32x4*>(vx + rt * 512 + WINO_KQ);                              \
+            wino_split8(q0, q1, ap[rt][0], ap[rt][1], ap[rt][2]);                                                   \
+        }                                                                                                           \
+        _Pragma("unroll") for (int nb = 0; nb < 2; ++nb) {                                                          \
+            const bf16x8 b0 = __builtin_bit_cast(bf16x8, bq[nb][0]);                                                \
+            const bf16x8 b1 = __builtin_bit_cast(bf16x8, bq[nb][1]);                                                \
+            const bf16x8 b2 = __builtin_bit_cast(bf16x8, bq[nb][2]);                                                \
+            _Pragma("unroll") for (int rt = 0; rt < 2; ++rt) {                                                      \
+                f32x16 c = acc[X][rt][nb];                                                                          \
+                /* smallest terms first */                                                                          \
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[rt][2], b0, c, 0, 0, 0);                             \
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[rt][1], b1, c, 0, 0, 0);                             \
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[rt][0], b2, c, 0, 0, 0);                             \
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[rt][1], b0, c, 0, 0, 0);                             \
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[rt][0], b1, c, 0, 0, 0);                             \
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[rt][0], b0, c, 0, 0, 0);                             \
+                acc[X][rt][nb] = c;                                                                                 \
+            }                                                                                                       \
+            LRPXW_BLOAD(2 * (CHUNK) + (X) + 1, nb)                                                                  \
+            __builtin_amdgcn_sched_barrier(0); /* the reload stays here in the queue of loads */                    \
+        }                                                                                                           \
+    }
+
+    // Steady state.  The loads retire in the order of their issue, which the scheduling barriers pin:
+    //   B of the second step (6, issued during the first step), the 12 patch loads of chunk + 1, B of the next chunk's first step (6).
+    // So no wait in front of MFMAs retires a patch load of its own chunk (the second step's waits end at vmcnt(15), the next chunk's
+    // first step finds the patch loads retired by the commit), and the patch loads have the second step's 24 MFMAs to come back.  rv is
+    // dead during the first step.  The last chunk, which stages nothing, is peeled off, so that the loop has no branch in it.
+    for (int chunk = 0; chunk + 1 < nchunk; ++chunk) {
         const char* vbuf = ldsw + (chunk & 1) * WINO_BUF;
-#pragma unroll
-        for (int x = 0; x < 2; ++x) {
-            const char* vx = vbuf + (2 * wave + x) * WINO_XI + (2 * lh) * WINO_KQ + li * 16;
-            bf16x8 ap[2][3];
-#pragma unroll
-            for (int rt = 0; rt < 2; ++rt) {
-                const f32x4 q0 = *reinterpret_cast<const f32x4*>(vx + rt * 512);
-                const f32x4 q1 = *reinterpret_cast<const f32x4*>(vx + rt * 512 + WINO_KQ);
-                wino_split8(q0, q1, ap[rt][0], ap[rt][1], ap[rt][2]);
-            }
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb) {
-                const bf16x8 b0 = __builtin_bit_cast(bf16x8, bq[nb][0]);
-                const bf16x8 b1 = __builtin_bit_cast(bf16x8, bq[nb][1]);
-                const bf16x8 b2 = __builtin_bit_cast(bf16x8, bq[nb][2]);
-#pragma unroll
-                for (int rt = 0; rt < 2; ++rt) {
-                    f32x16 c = acc[x][rt][nb];
-                    // smallest terms first
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[rt][2], b0, c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[rt][1], b1, c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[rt][0], b2, c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[rt][1], b0, c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[rt][0], b1, c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[rt][0], b0, c, 0, 0, 0);
-                    acc[x][rt][nb] = c;
-                }
-                const u32x4* nx = bptr(2 * chunk + x + 1, nb);
-#pragma unroll
-                for (int p = 0; p < 3; ++p) bq[nb][p] = nx[p * 64];
-            }
-        }
-        if (more) { LRPXW_COMMIT((chunk + 1) & 1) }
+        LRPXW_STEP(chunk, 0, vbuf)
+        LRPXW_ISSUE(chunk + 1)
+        __builtin_amdgcn_sched_barrier(0);
+        LRPXW_STEP(chunk, 1, vbuf)      // (ends with a scheduling barrier: the transform and its waits stay behind the MFMAs)
+        LRPXW_COMMIT((chunk + 1) & 1)
         __syncthreads();
     }
+    {
+        const char* vbuf = ldsw + ((nchunk - 1) & 1) * WINO_BUF;
+        LRPXW_STEP(nchunk - 1, 0, vbuf)
+        LRPXW_STEP(nchunk - 1, 1, vbuf)
+        __syncthreads();
+    }
+#undef LRPXW_STEP
+#undef LRPXW_BLOAD
 #undef LRPXW_ISSUE
 #undef LRPXW_SHARE
 #undef LRPXW_COMMIT
@@ -294,6 +325,12 @@ int launch_conv_wino_b6(const ConvArgs& a, hipStream_t stream) {
     const long grid = ceil_div(m_blocks, 8) * 8 * n_blocks;
     if (grid <= 0 || grid > 0x7fffffffL || a.n_oc % 64 != 0) {
         set_error("conv_wino_b6: grid %ld out of range or n_oc %d not a multiple of 64", grid, a.n_oc);
+        return LRPX_EINVAL;
+    }
+    // the kernel's 32-bit buffer offsets: the maps that a workgroup's 64 tiles touch (at most 64 / TPM + 2), and the packed weights
+    const long span = (long)(64 / TPM + 2) * HW * HW * a.cin * 4, wbytes = (long)n_blocks * 2 * 16 * (a.cin / 16) * 192 * 16;
+    if (span >= (long)WINO_OOB || wbytes > 0x7fffffffL) {
+        set_error("conv_wino_b6: %ld B of maps per workgroup or %ld B of packed weights are beyond the kernel's 32-bit offsets", span, wbytes);
         return LRPX_EINVAL;
     }
     auto kern = conv_wino_b6_kernel<HW, SHARE>;
