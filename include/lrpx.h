@@ -38,7 +38,8 @@ enum {
  * The same holds for the batched ResNet engine's entries (lrpx_conv_geom_ex, lrpx_resnet_*) and their conv mode 1 siblings
  * (lrpx_conv_geom_packed_bf16x3_bytes, lrpx_conv_geom_pack_bf16x3, lrpx_conv_geom_ex_b6), and for the general alpha-beta rule on
  * that engine (lrpx_conv_geom_ab, lrpx_conv_geom_ab_b6, lrpx_resnet_coef_neg), and for its gradient chain (lrpx_conv_geom_grad,
- * lrpx_conv_geom_grad_b6, lrpx_resnet_relu_grad, lrpx_resnet_maxpool_grad).
+ * lrpx_conv_geom_grad_b6, lrpx_resnet_relu_grad, lrpx_resnet_maxpool_grad), and for the alpha-beta rule under a 2x2 max-pool
+ * (lrpx_conv_geom_ab_pool, lrpx_conv_geom_ab_pool_b6, lrpx_vgg16_ab_coef, lrpx_conv_geom_ex_b6_blocked).
  * 101: the alpha-beta Conv2d rule (LRPX_PACK_*_PN*, lrpx_divide_alpha_beta, lrpx_maxpool2x2_relevance_ab); 100 before it */
 int lrpx_version(void);
 const char* lrpx_last_error_string(void);
@@ -239,6 +240,12 @@ int lrpx_conv_geom_pack_bf16x3(const float* w, int cout, int cin, int kh, int kw
 /* lrpx_conv_geom_ex with `wpacked` the bf16x3 image of the same direction: same descriptor, same refusals, same tiling and masking,
  * no atomics.  An in * q that overflows to +-inf comes out NaN here (the lower planes of inf are NaN), inf there. */
 int lrpx_conv_geom_ex_b6(const lrpx_conv_geom_ex_desc* d, void* stream);
+/* The forward direction of lrpx_conv_geom_ex_b6 (dir = LRPX_GEOM_FWD only, else LRPX_EINVAL) with its sums in a BLOCKED order: the cross
+ * products of the split collect in an accumulator of their own and the main accumulator is flushed into a second level every 8
+ * (tap, chunk) stages.  Z+ of a conv is a sum of terms of one sign: the plain forward rounds 12 times per stage at the running sum's
+ * full size, this one (stages / 8) + 16 times per output.  Same descriptor, packs, tiling and refusals; other bits than the plain
+ * forward's.  What lrpx_vgg16_ab_coef's input is made with. */
+int lrpx_conv_geom_ex_b6_blocked(const lrpx_conv_geom_ex_desc* d, void* stream);
 
 /* ---- the transposed direction of both engines with TWO coefficients: the general alpha-beta rule without bias on the batched engine
  * (LRPtools/lrp_modules.py:124-150; ops.ResNetEncoder.relevance_alpha_beta).  For a conv with a non-negative input
@@ -261,6 +268,28 @@ int lrpx_conv_geom_ab(const lrpx_conv_geom_ab_desc* d, void* stream);      /* fp
 /* exact bf16 split (split3 after both multiplications); the cross products collect in an accumulator of their own, joined to the
  * a0 b0 sums once per output: W+ against W- cancels, and fewer roundings at the running sum's size keep the result fp32 grade */
 int lrpx_conv_geom_ab_b6(const lrpx_conv_geom_ab_desc* d, void* stream);
+
+/* ---- the same two entries for a conv that sits directly under a 2x2 / stride-2 max-pool (VGG16's conv1_2, 2_2, 3_3, 4_3;
+ * ops.Vgg16.relevance_alpha_beta(conv_mode=1)).  The Pool2d rule (lrp_modules.py:182-195) hands a window's relevance to
+ * its first maximum, R where that maximum is non-zero and 0 where the whole window is zero: a per-image 0 / 1 factor, folded into q / q2
+ * by lrpx_vgg16_ab_coef.  `in` is the relevance BEHIND the pool,
+ *   in [n * (oh / 2) * (ow / 2)][kr],   A(kappa) = (in[m, oh' >> 1, ow' >> 1, c] * qh[img, oh', ow', c]) * sh,
+ * read inside the pooled map's bounds: a last odd row / column of the conv's output lies under no window and contributes zero.  The
+ * relevance at the conv's own resolution never exists.  Everything else - stacked K, scale / scale2, x, addend, map2img, k = kr with q2
+ * NULL, arithmetic, tiling, refusals - is lrpx_conv_geom_ab's / _ab_b6's; no atomics, no workspace. */
+typedef struct lrpx_conv_geom_ab_pool_desc {
+    lrpx_conv_geom_ab_desc ab;   /* as above, but ab.base.in at the pooled resolution */
+    int pool;                    /* 2: kernel = stride = 2, no padding, floor mode.  Anything else is LRPX_EINVAL */
+} lrpx_conv_geom_ab_pool_desc;
+int lrpx_conv_geom_ab_pool(const lrpx_conv_geom_ab_pool_desc* d, void* stream);     /* fp32 MFMA */
+int lrpx_conv_geom_ab_pool_b6(const lrpx_conv_geom_ab_pool_desc* d, void* stream);  /* exact bf16 split */
+/* The per-image coefficients of those entries on VGG16 (once per forward, independent of alpha and beta).  zz [n_img*oh*ow][2c] =
+ * [Z+ | Z-], the rows of one stacked forward contraction;  qp, qn [n_img*oh*ow][c]:
+ *   qp = win / safe(Z+),  qn = win / safe(Z-),  safe(z) = z + 1e-7 (z == 0)  (LRPtools/utils.py:28), IEEE division of 1.
+ * xpool NULL: win = 1.  xpool [n_img*oh*ow][c], the input of the 2x2 max-pool above the conv (the conv's ReLU output): win = 1 at the
+ * FIRST maximum of the pixel's window (row-major, strict >) if that maximum != 0, else 0; 0 for pixels no window covers (odd oh / ow).
+ * c % 4 == 0, all pointers 16-byte aligned; 64-bit indices, no atomics. */
+int lrpx_vgg16_ab_coef(const float* zz, const float* xpool, float* qp, float* qn, int n_img, int oh, int ow, int c, void* stream);
 
 /* ---- the transposed direction of both engines for the GRADIENT chain through conv -> BatchNorm (eval) -> ReLU
  * (ops.ResNetEncoder.gradient / guided_backprop): plain autograd (ExplainGridTDGradient.explain_cnn,

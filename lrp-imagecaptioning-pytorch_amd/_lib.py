@@ -116,6 +116,11 @@ class ConvGeomAbDesc(C.Structure):
     _fields_ = [("base", ConvGeomExDesc), ("q2", _f), ("scale", C.c_float), ("scale2", C.c_float), ("kr", _i)]
 
 
+class ConvGeomAbPoolDesc(C.Structure):
+    """lrpx_conv_geom_ab_pool_desc: the same with the relevance operand behind a 2x2 max-pool"""
+    _fields_ = [("ab", ConvGeomAbDesc), ("pool", _i)]
+
+
 class ConvGeomGradDesc(C.Structure):
     """lrpx_conv_geom_grad_desc: the transposed direction of the gradient chain (raw weights; clamp, mask, scale in the gather)"""
     _fields_ = [("base", ConvGeomExDesc), ("mask", _f), ("scale", _f), ("clamp", _i)]
@@ -278,6 +283,10 @@ SIGNATURES = {
     "lrpx_conv_geom_ex_b6": (_i, [C.POINTER(ConvGeomExDesc), _f]),
     "lrpx_conv_geom_ab": (_i, [C.POINTER(ConvGeomAbDesc), _f]),
     "lrpx_conv_geom_ab_b6": (_i, [C.POINTER(ConvGeomAbDesc), _f]),
+    "lrpx_conv_geom_ex_b6_blocked": (_i, [C.POINTER(ConvGeomExDesc), _f]),
+    "lrpx_conv_geom_ab_pool": (_i, [C.POINTER(ConvGeomAbPoolDesc), _f]),
+    "lrpx_conv_geom_ab_pool_b6": (_i, [C.POINTER(ConvGeomAbPoolDesc), _f]),
+    "lrpx_vgg16_ab_coef": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _f]),
     "lrpx_conv_geom_grad": (_i, [C.POINTER(ConvGeomGradDesc), _f]),
     "lrpx_conv_geom_grad_b6": (_i, [C.POINTER(ConvGeomGradDesc), _f]),
     "lrpx_resnet_relu_grad": (_i, [_f, _f, _f, _f, _i, _i, _l, _i, _f]),

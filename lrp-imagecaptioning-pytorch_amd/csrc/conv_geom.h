@@ -72,6 +72,16 @@ inline int conv_geom_ab_check(const lrpx_conv_geom_ab_desc* a, const char* fn) {
     return LRPX_OK;
 }
 
+// What the pooled-operand entries (lrpx_conv_geom_ab_pool, lrpx_conv_geom_ab_pool_b6) check before conv_geom_check sees their ab part:
+// the one pool the gather is written for, and a pooled map that is not empty.
+inline int conv_geom_pool_check(const lrpx_conv_geom_ab_pool_desc* a, const char* fn) {
+    LRPX_REQUIRE(a, "%s: null descriptor", fn);
+    LRPX_REQUIRE(a->pool == 2, "%s: pool must be 2 (kernel = stride = 2, no padding, floor mode), got %d", fn, a->pool);
+    LRPX_REQUIRE(a->ab.base.oh >= 2 && a->ab.base.ow >= 2, "%s: the conv's output %dx%d leaves the pool no window", fn, a->ab.base.oh,
+                 a->ab.base.ow);
+    return LRPX_OK;
+}
+
 // What the gradient entries (lrpx_conv_geom_grad, lrpx_conv_geom_grad_b6) add to conv_geom_check: the transposed direction alone, no
 // multiplicand, coefficient or bias, and the refusals of mask / scale / clamp.
 inline int conv_geom_grad_check(const lrpx_conv_geom_grad_desc* g, const char* fn) {

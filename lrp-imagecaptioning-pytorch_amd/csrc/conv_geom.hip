@@ -71,6 +71,11 @@ int lrpx_conv_geom_ab(const lrpx_conv_geom_ab_desc* a, void* stream) {
     return conv_geom_run<CgF32, 1>(&a->base, a, stream, "lrpx_conv_geom_ab");
 }
 
+int lrpx_conv_geom_ab_pool(const lrpx_conv_geom_ab_pool_desc* a, void* stream) {
+    LRPX_TRY(conv_geom_pool_check(a, "lrpx_conv_geom_ab_pool"));
+    return conv_geom_run<CgF32, 1, true>(&a->ab.base, &a->ab, stream, "lrpx_conv_geom_ab_pool");
+}
+
 int lrpx_conv_geom_grad(const lrpx_conv_geom_grad_desc* g, void* stream) {
     LRPX_REQUIRE(g, "lrpx_conv_geom_grad: null descriptor");
     return conv_geom_run<CgF32, 3>(&g->base, nullptr, stream, "lrpx_conv_geom_grad", g);

@@ -87,10 +87,22 @@ int lrpx_conv_geom_pack_bf16x3(const float* w, int cout, int cin, int kh, int kw
 
 int lrpx_conv_geom_ex_b6(const lrpx_conv_geom_ex_desc* d, void* stream) { return conv_geom_run<CgB6, 0>(d, nullptr, stream, "lrpx_conv_geom_ex_b6"); }
 
+// the forward direction alone, its sums in the blocked order (conv_geom_kernel.h): the Z+ / Z- of the alpha-beta coefficients
+int lrpx_conv_geom_ex_b6_blocked(const lrpx_conv_geom_ex_desc* d, void* stream) {
+    LRPX_REQUIRE(d && d->dir == LRPX_GEOM_FWD, "lrpx_conv_geom_ex_b6_blocked: the forward direction only");
+    return conv_geom_run<CgB6, 0, false, true>(d, nullptr, stream, "lrpx_conv_geom_ex_b6_blocked");
+}
+
 // the W+ half alone sums in lrpx_conv_geom_ex_b6's order, so that scale 1 gives its bytes
 int lrpx_conv_geom_ab_b6(const lrpx_conv_geom_ab_desc* a, void* stream) {
     LRPX_REQUIRE(a, "lrpx_conv_geom_ab_b6: null descriptor");
     return a->q2 ? conv_geom_run<CgB6, 2>(&a->base, a, stream, "lrpx_conv_geom_ab_b6") : conv_geom_run<CgB6, 1>(&a->base, a, stream, "lrpx_conv_geom_ab_b6");
+}
+
+int lrpx_conv_geom_ab_pool_b6(const lrpx_conv_geom_ab_pool_desc* a, void* stream) {
+    LRPX_TRY(conv_geom_pool_check(a, "lrpx_conv_geom_ab_pool_b6"));
+    return a->ab.q2 ? conv_geom_run<CgB6, 2, true>(&a->ab.base, &a->ab, stream, "lrpx_conv_geom_ab_pool_b6")
+                    : conv_geom_run<CgB6, 1, true>(&a->ab.base, &a->ab, stream, "lrpx_conv_geom_ab_pool_b6");
 }
 
 // clamp, mask and scale are applied in fp32 before the split: the operand is lrpx_conv_geom_grad's

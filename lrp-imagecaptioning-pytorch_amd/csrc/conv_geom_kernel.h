@@ -17,6 +17,13 @@
 // The gradient chain (AB = 3) is the transposed kernel with the raw weights and an operand shaped while it is gathered:
 // A = scale[c] * (mask[img] > 0 ? (clamp ? max(in, 0) : in) : 0), each of the three optional, and the epilogue out = acc + addend: no
 // multiplicand, p.x is never read.
+// The blocked forward (BLOCKED, forward direction only): the sums of the plain forward in a blocked order.  Z+ is a sum of
+// terms of one sign, so every add into the running sum rounds at the sum's full size; the policy's cross products collect in an
+// accumulator of their own and the main one is flushed into a second level every CG_FLUSH stages, which leaves (stages / CG_FLUSH) + 2
+// CG_FLUSH roundings of full size per output where the plain forward has 12 per stage.
+// POOL (the dual-coefficient gather only): the conv sits directly under a 2x2 / stride-2 max-pool and `in` is the relevance
+// BEHIND that pool, (n maps, (OH / 2) (OW / 2), kr): the staged element reads it at (sy >> 1, sx >> 1), inside the pooled map's bounds, and
+// q / q2 - which carry the pool's winner factor - at (sy, sx).  The relevance at the conv's own resolution never exists.
 #pragma once
 #include "conv_geom.h"
 
@@ -45,15 +52,36 @@ struct CgParams {
     int clamp;
 };
 
+// The second level of the blocked forward: present in the BLOCKED instantiation alone, an empty object in every other
+template <bool ON>
+struct CgSecondLevel {
+    f32x16 hi;
+    __device__ __forceinline__ CgSecondLevel() {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) hi[e] = 0.f;
+    }
+    __device__ __forceinline__ void flush(f32x16& acc) {
+        hi = hi + acc;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+    }
+    __device__ __forceinline__ void join(f32x16& acc, const f32x16& lo) const { acc = hi + (acc + lo); }
+};
+template <>
+struct CgSecondLevel<false> {};
+
 // DIR = LRPX_GEOM_FWD: output pixels are the (OH, OW) map, sources the (H, W) map.
 // DIR = LRPX_GEOM_BWD: output pixels are the (H, W) map in sub-pixel classes (blockIdx.z), sources the (OH, OW) map.
 // AB (transposed direction only) 1: the dual-coefficient gather;  2: the same, with the policy's cross products in an accumulator of their
-// own (CgB6 over both halves, K = 2 kr);  3: the gradient chain's gather and epilogue.
-template <typename Arith, int DIR, int AB>
+// own (CgB6 over both halves, K = 2 kr);  3: the gradient chain's gather and epilogue.  POOL, BLOCKED: above.
+template <typename Arith, int DIR, int AB, bool POOL = false, bool BLOCKED = false>
 __global__ __launch_bounds__(256) void conv_geom_kernel(const CgParams p) {
+    static_assert(!POOL || (DIR == LRPX_GEOM_BWD && (AB == 1 || AB == 2)), "the pooled operand belongs to the dual-coefficient gather");
     typedef typename Arith::BFrag BFrag;
     constexpr int NB = Arith::NB;
     constexpr bool DUAL = AB == 1 || AB == 2, GRAD = AB == 3;
+    constexpr int CG_FLUSH = 8;                     // BLOCKED: stages per block of the main accumulator
+    static_assert(!BLOCKED || (DIR == LRPX_GEOM_FWD && AB == 0), "the blocked order belongs to the forward direction");
     __shared__ __attribute__((aligned(16))) char a_lds[CG_TM * Arith::ROWB];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave & 1, wn = wave >> 1;
@@ -63,6 +91,10 @@ __global__ __launch_bounds__(256) void conv_geom_kernel(const CgParams p) {
     const int cs_h = DIR == LRPX_GEOM_BWD ? p.sh : 1, cs_w = DIR == LRPX_GEOM_BWD ? p.sw : 1;
     const int OY = DIR == LRPX_GEOM_BWD ? p.H : p.OH, OX = DIR == LRPX_GEOM_BWD ? p.W : p.OW;     // output map
     const int SY = DIR == LRPX_GEOM_BWD ? p.OH : p.H, SX = DIR == LRPX_GEOM_BWD ? p.OW : p.W;     // source map
+    // POOL: the map `in` is stored at, and the part of the source map its windows cover - a last odd row / column lies under no window,
+    // its operand is zero (the winner factor in q / q2 is) and nothing of it is read
+    const int PY = SY >> 1, PX = SX >> 1;
+    const int SYg = POOL ? SY & ~1 : SY, SXg = POOL ? SX & ~1 : SX;
     const int Hc = ch < OY ? (OY - ch + cs_h - 1) / cs_h : 0, Wc = cw < OX ? (OX - cw + cs_w - 1) / cs_w : 0;
     const long npix = (long)p.n * Hc * Wc;
     const long pix0 = (long)blockIdx.x * CG_TM;
@@ -106,7 +138,8 @@ __global__ __launch_bounds__(256) void conv_geom_kernel(const CgParams p) {
     f32x16 acc, acc_lo;
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] = acc_lo[e] = 0.f;
-    f32x16& lo = AB == 2 ? acc_lo : acc;            // where the policy's cross products collect (CgB6)
+    f32x16& lo = AB == 2 || BLOCKED ? acc_lo : acc;  // where the policy's cross products collect (CgB6)
+    CgSecondLevel<BLOCKED> second;
 #pragma unroll
     for (int g = 0; g < NB; ++g) bcur[g] = bnext[g] = BFrag{0, 0, 0, 0};
 
@@ -119,11 +152,14 @@ __global__ __launch_bounds__(256) void conv_geom_kernel(const CgParams p) {
             const int sy = DIR == LRPX_GEOM_BWD ? phi[u] + yb - i : phi[u] * p.sh - p.ph + i;
             const int sx = DIR == LRPX_GEOM_BWD ? pwi[u] + xb - j : pwi[u] * p.sw - p.pw + j;
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (pn[u] >= 0 && sy >= 0 && sy < SY && sx >= 0 && sx < SX && kc < p.K) {
+            if (pn[u] >= 0 && sy >= 0 && sy < SYg && sx >= 0 && sx < SXg && kc < p.K) {
                 const long pix = (long)sy * SX + sx;
                 const bool neg = DUAL && kc >= p.kr;                 // the W- half of the stacked contraction
                 const int c = neg ? kc - p.kr : kc, ld = DUAL ? p.kr : p.K;
-                v = *reinterpret_cast<const f32x4*>(p.in + ((long)pn[u] * SY * SX + pix) * ld + c);
+                if (!POOL)
+                    v = *reinterpret_cast<const f32x4*>(p.in + ((long)pn[u] * SY * SX + pix) * ld + c);
+                else        // sy < SY & ~1 and sx < SX & ~1 here: (sy >> 1, sx >> 1) lies inside the pooled map
+                    v = *reinterpret_cast<const f32x4*>(p.in + ((long)pn[u] * PY * PX + (long)(sy >> 1) * PX + (sx >> 1)) * ld + c);
                 if (DIR == LRPX_GEOM_BWD && !GRAD && p.q) {
                     const f32x4 qv = *reinterpret_cast<const f32x4*>((neg ? p.q2 : p.q) + ((long)pim[u] * SY * SX + pix) * ld + c);
                     v = v * qv;
@@ -161,9 +197,12 @@ __global__ __launch_bounds__(256) void conv_geom_kernel(const CgParams p) {
         if (active) Arith::mma(a_lds + (wm * 32 + (lane & 31)) * Arith::ROWB + 16 * (lane >> 5), bcur, acc, lo);
 #pragma unroll
         for (int g = 0; g < NB; ++g) bcur[g] = bnext[g];
+        if constexpr (BLOCKED)
+            if (st % CG_FLUSH == CG_FLUSH - 1) second.flush(acc);
     }
 
     if (AB == 2) acc = acc + acc_lo;
+    if constexpr (BLOCKED) second.join(acc, acc_lo);
     // epilogue: accumulator register e of lane l is tile row (e & 3) + 8 (e >> 2) + 4 (l >> 5), column l & 31
     const int oc = ocb * 32 + (lane & 31);
     if (oc >= p.n_oc) return;
@@ -193,8 +232,8 @@ __global__ __launch_bounds__(256) void conv_geom_kernel(const CgParams p) {
 }
 
 // Check the descriptor (`ab`: the dual-coefficient entries, d = &ab->base; `gr`: the gradient entries, d = &gr->base, AB = 3) and launch its direction: conv_geom_kernel<Arith, FWD, 0> on
-// ceil(output pixels / CG_TM) tiles, or <Arith, BWD, AB> on the tiles of the largest class, (0, 0), for each of the sh * sw classes.
-template <typename Arith, int AB>
+// ceil(output pixels / CG_TM) tiles, or <Arith, BWD, AB, POOL> on the tiles of the largest class, (0, 0), for each of the sh * sw classes.
+template <typename Arith, int AB, bool POOL = false, bool BLOCKED = false>
 int conv_geom_run(const lrpx_conv_geom_ex_desc* d, const lrpx_conv_geom_ab_desc* ab, void* stream, const char* fn,
                   const lrpx_conv_geom_grad_desc* gr = nullptr) {
     LRPX_TRY(conv_geom_check(d, fn, ab, gr));
@@ -205,11 +244,11 @@ int conv_geom_run(const lrpx_conv_geom_ex_desc* d, const lrpx_conv_geom_ab_desc*
     const unsigned gy = (unsigned)ceil_div(d->n_oc, CG_TN);
     if (d->dir == LRPX_GEOM_FWD) {
         const long pix_out = (long)d->n * d->oh * d->ow;
-        hipLaunchKernelGGL((conv_geom_kernel<Arith, LRPX_GEOM_FWD, 0>), dim3((unsigned)ceil_div(pix_out, CG_TM), gy, 1), dim3(256), 0,
+        hipLaunchKernelGGL((conv_geom_kernel<Arith, LRPX_GEOM_FWD, 0, false, BLOCKED>), dim3((unsigned)ceil_div(pix_out, CG_TM), gy, 1), dim3(256), 0,
                            (hipStream_t)stream, p);
     } else {
         const long pc = (long)d->n * ceil_div(d->h, d->sh) * ceil_div(d->w, d->sw);
-        hipLaunchKernelGGL((conv_geom_kernel<Arith, LRPX_GEOM_BWD, AB>), dim3((unsigned)ceil_div(pc, CG_TM), gy, (unsigned)(d->sh * d->sw)),
+        hipLaunchKernelGGL((conv_geom_kernel<Arith, LRPX_GEOM_BWD, AB, POOL>), dim3((unsigned)ceil_div(pc, CG_TM), gy, (unsigned)(d->sh * d->sw)),
                            dim3(256), 0, (hipStream_t)stream, p);
     }
     return check_launch(fn);

@@ -829,6 +829,50 @@ __global__ void maxpool_relevance_ab_kernel(const float* __restrict__ x, const f
     o[c4] = ab_quot(ri, zn, nbeta);
 }
 
+// The per-image coefficients of the general rule on the exact splits: qp = win / safe(Z+), qn = win / safe(Z-) from the
+// rows [Z+ | Z-] of one stacked forward contraction.  win is the Pool2d rule of the pool above the conv as a 0 / 1 factor - the winner
+// logic of maxpool_relevance_ab_kernel, with m * (R / safe(m)) taken as R where m != 0 and 0 where the window is all zero - or 1 without
+// a pool (x NULL).  Pixels of a last odd row / column lie under no window: 0.  One thread = one pixel x 4 channels, 64-bit indices.
+__global__ void vgg16_ab_coef_kernel(const float* __restrict__ zz, const float* __restrict__ x, float* __restrict__ qp, float* __restrict__ qn,
+                                     int h, int w, int c4, long total) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;   // over n_img * h * w * c4
+    if (idx >= total) return;
+    const int cc = (int)(idx % c4);
+    const long row = idx / c4;
+    const f32x4 zp = reinterpret_cast<const f32x4*>(zz)[row * (2 * c4) + cc], zn = reinterpret_cast<const f32x4*>(zz)[row * (2 * c4) + c4 + cc];
+    bool win[4] = {true, true, true, true};
+    if (x) {
+        long t = row;
+        const int xi = (int)(t % w); t /= w;
+        const int yi = (int)(t % h);
+        const long img = t / h;
+        if ((yi >> 1) < (h >> 1) && (xi >> 1) < (w >> 1)) {
+            const int pos = (yi & 1) * 2 + (xi & 1);   // position of this pixel inside its window, row-major
+            const f32x4* xb = reinterpret_cast<const f32x4*>(x) + ((img * h + (yi & ~1)) * w + (xi & ~1)) * c4 + cc;
+            const f32x4 w4[4] = {xb[0], xb[c4], xb[(long)w * c4], xb[(long)w * c4 + c4]};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float m = w4[0][e];
+                int am = 0;
+                if (w4[1][e] > m) { m = w4[1][e]; am = 1; }
+                if (w4[2][e] > m) { m = w4[2][e]; am = 2; }
+                if (w4[3][e] > m) { m = w4[3][e]; am = 3; }
+                win[e] = am == pos && m != 0.f;
+            }
+        } else {
+            win[0] = win[1] = win[2] = win[3] = false;
+        }
+    }
+    f32x4 op, on;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        op[e] = win[e] ? 1.f / stab_safe(zp[e]) : 0.f;
+        on[e] = win[e] ? 1.f / stab_safe(zn[e]) : 0.f;
+    }
+    reinterpret_cast<f32x4*>(qp)[idx] = op;
+    reinterpret_cast<f32x4*>(qn)[idx] = on;
+}
+
 // S = R / safe(Z+) at the top of the mode-3 chain, written BLOCKED (blocked.h) with the per-map maxima.
 // r: [n_maps][P][C] NHWC, z: [n_img][P][C].  A wave moves 8 pixels x 32 channels per step: 8 lanes read one pixel's 128 contiguous
 // bytes (whole lines in), and write per (16-channel chunk, 4-channel part) 8 pixels x 16 bytes = one 128-byte run (whole lines out).
@@ -1260,6 +1304,18 @@ int lrpx_maxpool2x2_relevance_ab(const float* x, const float* r_out, const float
     hipLaunchKernelGGL(maxpool_relevance_ab_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, r_out, zpos, zneg,
                        map2img, s2, h_out, w_out, c / 4, alpha, -beta, total);
     return check_launch("maxpool2x2_relevance_ab");
+}
+
+int lrpx_vgg16_ab_coef(const float* zz, const float* xpool, float* qp, float* qn, int n_img, int oh, int ow, int c, void* stream) {
+    LRPX_REQUIRE(zz && qp && qn, "vgg16_ab_coef: null pointer");
+    LRPX_REQUIRE(n_img > 0 && oh > 0 && ow > 0 && c > 0 && c % 4 == 0, "vgg16_ab_coef: bad sizes (n_img=%d oh=%d ow=%d c=%d, c %% 4 == 0)",
+                 n_img, oh, ow, c);
+    LRPX_REQUIRE((((uintptr_t)zz | (uintptr_t)xpool | (uintptr_t)qp | (uintptr_t)qn) & 15) == 0, "vgg16_ab_coef: pointers must be 16-byte aligned");
+    LRPX_CHECK_PTRS("lrpx_vgg16_ab_coef", {zz, "zz"}, {xpool, "xpool"}, {qp, "qp"}, {qn, "qn"});
+    const long total = (long)n_img * oh * ow * (c / 4);
+    LRPX_REQUIRE(ceil_div(total, 256) < 0x7fffffffL, "vgg16_ab_coef: too many elements for one launch");
+    hipLaunchKernelGGL(vgg16_ab_coef_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, zz, xpool, qp, qn, oh, ow, c / 4, total);
+    return check_launch("vgg16_ab_coef");
 }
 
 size_t lrpx_blocked_floats(long n_pix, int c) { return (size_t)blk_floats(n_pix, c); }

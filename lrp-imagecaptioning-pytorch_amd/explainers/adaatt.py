@@ -333,7 +333,8 @@ class AdaAttEngine(EngineBase):
     def explain_features(self, features, captions, lens=None, predictions=False):
         """Every word of B captions explained on (B, P, C) features in place of the encoder's; captions (B, T+1) int64, column 0 =
         <start>.  Returns r_feat (B, T, P, C) - zero in rows behind an image's last word (`lens`) - and r_words (B, T, T) (row t holds
-        t + 1 valid entries); then the (B, T, V) scores with predictions=True."""
+        t + 1 valid entries); then the (B, T, V) scores with predictions=True.  No encoder stage: `lrp_params` must be None."""
+        self._features_stage("explain_features")
         enc = self.encode(features=features)
         captions = captions.to(self.device, torch.int64).contiguous()
         B, T = captions.shape[0], captions.shape[1] - 1
@@ -345,7 +346,9 @@ class AdaAttEngine(EngineBase):
     def explain_batch(self, images, captions, lens=None, accumulate=False, return_features=False, predictions=False):
         """Batched `explain_caption` (:779-794): images (B,3,H,W) of the encoder's size, captions (B,T+1) int64.  Returns maps
         (B,T,3,H,W) and r_words (B,T,T); accumulate=True: the running sums the reference returns (lrp_wrapper.py:64-82 quirk);
-        predictions=True: then the (B,T,V) scores; return_features=True: then r_feat (B,T,P,C), the trace and `encode`'s dict."""
+        predictions=True: then the (B,T,V) scores; return_features=True: then r_feat (B,T,P,C), the trace and `encode`'s dict.
+        The instance attribute `lrp_params` selects the encoder's Conv2d rule (explainers/engine_base.py: `_maps_stage`)."""
+        maps_of = self._maps_stage("explain_batch")
         self._check_sizes(images=images)
         images = images.to(self.device, torch.float32).contiguous()
         captions = captions.to(self.device, torch.int64).contiguous()
@@ -354,14 +357,16 @@ class AdaAttEngine(EngineBase):
         tr = self.trace(enc, captions, predictions=predictions)
         rg = ragged(lens, B, T, self.device)
         r_feat, r_words, row2img = self.relevance(enc, tr, rg)
-        return self._finish(rg, B, T, r_feat, r_words, row2img, self.cnn.relevance, tuple(images.shape[1:]), accumulate=accumulate,
+        return self._finish(rg, B, T, r_feat, r_words, row2img, maps_of, tuple(images.shape[1:]), accumulate=accumulate,
                             extra=(tr["pred"],) if predictions else (), features=(tr, enc) if return_features else None)
 
     def explain_stream(self, batches, depth=3, accumulate=False):
         """`explain_batch` over an iterable of (images, captions[, lens]) batches, `depth` in flight (explainers/engine_base.py); an
         engine without an encoder streams `explain_features` over (features, captions[, lens]) batches."""
         if self.cnn is None:
+            self._features_stage("explain_stream")
             return self._explain_stream(batches, depth, lambda eng, f, c, lens: eng.explain_features(f, c, lens=lens))
+        self._maps_stage("explain_stream")                # a refusal here, not inside the generator's first step
         return self._explain_stream(batches, depth, lambda eng, i, c, lens: eng.explain_batch(i, c, lens=lens, accumulate=accumulate))
 
     def _static(self, graph, src, captions, accumulate, predictions, *key):
@@ -376,11 +381,13 @@ class AdaAttEngine(EngineBase):
     def explain_batch_graph(self, images, captions, accumulate=False, predictions=False):
         """`explain_batch` (images) or `explain_features` ((B, P, C) features) replayed from a captured HIP graph, one per input shape
         (explainers/engine_base.py: `_static_step`)."""
+        self._preset_only("explain_batch_graph", self._NO_STATIC_AB)
         self._refuse_resnet("explain_batch_graph", self._NO_GRAPH)
         return self._static(True, images, captions, accumulate, predictions)
 
     def explain_batch_replay(self, images, captions, accumulate=False, predictions=False):
         """the same as a RECORDED step, one per input shape and stream (explainers/engine_base.py: `_static_step`)."""
+        self._preset_only("explain_batch_replay", self._NO_STATIC_AB)
         self._refuse_resnet("explain_batch_replay", self._NO_RECORDING)
         return self._static(False, images, captions, accumulate, predictions, _lib.stream_ptr().value,
                             self.vgg.conv_mode if self.vgg is not None else None)

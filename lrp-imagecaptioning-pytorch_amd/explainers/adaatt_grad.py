@@ -112,6 +112,7 @@ class AdaAttGradEngine(AdaAttEngine):
         """Batched `ExplainAdaptiveGradient.explain_caption` (:1038-1052): the decoder gradient + the gradient through the encoder
         (`explain_cnn`, :1023-1036) -> maps (B,T,3,H,W), word scores (B,T,T).  cam=True: `ExplainAdaptiveGradCam` (:1218-1236) - the
         per-word result is the Grad-CAM heat map (B,T,P).  (No running sums: the reference takes a fresh gradient per word.)"""
+        self._preset_only("explain_batch_gradient", self._NO_GRAD_AB)
         self._check_sizes(images=images)                                  # before any launch
         if cam and self.P > GRADCAM_MAX_PIXELS:
             raise ValueError("{}: a feature map of {} pixels; Grad-CAM heat maps are built for at most {} (lrpx_gradcam)".format(
@@ -125,6 +126,7 @@ class AdaAttGradEngine(AdaAttEngine):
     def explain_batch_guided(self, images, captions, lens=None, return_features=False, gradcam=False):
         """Batched `ExplainiAdaptiveGuidedGradient.explain_caption`: the same decoder gradient, guided backprop through the encoder
         (`explain_cnn`, :1175-1189) -> maps (B,T,3,H,W), word scores (B,T,T).  gradcam=True (`ExplainAdaptiveGuidedGradCam`) is refused."""
+        self._preset_only("explain_batch_guided", self._NO_GRAD_AB)
         if gradcam:
             raise NotImplementedError("{}.explain_batch_guided(gradcam=True): {}".format(type(self).__name__, GUIDED_GRADCAM_MISSING))
         self._check_sizes(images=images)                                  # before any launch
@@ -137,6 +139,7 @@ class AdaAttGradEngine(AdaAttEngine):
     def explain_features_gradient(self, features, captions, lens=None):
         """The decoder gradient of every word of B captions on (B, P, C) features in place of the encoder's (an engine without an
         encoder): d_feat (B, T, P, C) - zero in rows behind an image's last word (`lens`) - and r_words (B, T, T)."""
+        self._features_stage("explain_features_gradient")
         enc = self.encode(features=features)
         B, T, _, rg, d_feat, r_words, row2img = self._decoder_gradient(enc, captions, lens)
         return self._finish(rg, B, T, d_feat, r_words, row2img, lambda feat, m: feat, (self.P, self.C))

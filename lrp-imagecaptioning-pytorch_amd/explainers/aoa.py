@@ -370,6 +370,7 @@ class AOAEngine(EngineBase):
         ExplainAOAGuidedGradCam ("guided_gradcam", :1714-1751; VGG16 only).  With a ResNet encoder the maps are
         `ResNetEncoder.gradient` / `.guided_backprop(relus="stem")` (the reference hooks the encoder's direct children, :1596-1613: the
         stem's ReLU alone) at the images' own size."""
+        self._preset_only("explain_batch_gradient", self._NO_GRAD_AB)
         if kind == "guided_gradcam":
             self._refuse_resnet("explain_batch_gradient(kind='guided_gradcam')", self._GUIDED_GRADCAM_MISSING)
         if kind == "gradcam" and self.cnn is not None and self._feature_pixels(images) > self._GRADCAM_MAX_PIXELS:           # before any launch
@@ -480,7 +481,10 @@ class AOAEngine(EngineBase):
                       return_features=False, predictions=False):
         """Batched `explain_caption(img, head_idx)` (:1165-1181).  With images: maps (B,T,3,H,W), 224 x 224 for VGG16; with
         `features` (bottom-up): the region-feature relevance (B,T,P,C) is the result (no CNN stage).
-        predictions=True keeps the (T,V) scores of the trace as the reference's explainer does (:1026)."""
+        predictions=True keeps the (T,V) scores of the trace as the reference's explainer does (:1026).  The instance attribute
+        `lrp_params` selects the encoder's Conv2d rule on the images path (explainers/engine_base.py: `_maps_stage`); with `features`
+        there is no encoder stage and anything but None is a ValueError."""
+        maps_of = self._features_stage("explain_batch") if features is not None else self._maps_stage("explain_batch")
         enc = self.encode(images, features)
         captions = captions.to(self.device, torch.int64).contiguous()
         B, T = captions.shape[0], captions.shape[1] - 1
@@ -492,7 +496,7 @@ class AOAEngine(EngineBase):
         r_feat, r_words, row2img = self.relevance(enc, tr, head_idx, rg)
         # unequal caption lengths (models/aoamodel.py:1171-1176 explains `caption_length` words): the VGG16 chain runs on the sum(lens)
         # valid maps; `_finish` takes the result back to the padded layout
-        return self._finish(rg, B, T, r_feat, r_words, row2img, self.cnn.relevance, tuple(images.shape[1:]), accumulate=accumulate,
+        return self._finish(rg, B, T, r_feat, r_words, row2img, maps_of, tuple(images.shape[1:]), accumulate=accumulate,
                             features=(tr, enc) if return_features else None)
 
     def _static(self, graph, key, captions, head_idx, images, features, accumulate, predictions):
@@ -502,6 +506,7 @@ class AOAEngine(EngineBase):
 
     def explain_batch_graph(self, captions, head_idx, images=None, features=None, accumulate=False, predictions=False):
         """`explain_batch` replayed from a captured HIP graph, one per input shape and head (explainers/engine_base.py: `_static_step`)."""
+        self._features_stage("explain_batch_graph") if features is not None else self._preset_only("explain_batch_graph", self._NO_STATIC_AB)
         if features is None:
             self._refuse_resnet("explain_batch_graph", self._NO_GRAPH)
         src = features if features is not None else images
@@ -510,6 +515,7 @@ class AOAEngine(EngineBase):
 
     def explain_batch_replay(self, captions, head_idx, images=None, features=None, accumulate=False, predictions=False):
         """`explain_batch` as a RECORDED step, one per input shape, head and stream (explainers/engine_base.py: `_static_step`)."""
+        self._features_stage("explain_batch_replay") if features is not None else self._preset_only("explain_batch_replay", self._NO_STATIC_AB)
         if features is None:
             self._refuse_resnet("explain_batch_replay", self._NO_RECORDING)
         src = features if features is not None else images
@@ -519,6 +525,7 @@ class AOAEngine(EngineBase):
 
     def explain_stream(self, batches, head_idx, depth=3, accumulate=False):
         """`explain_batch` over an iterable of (images, captions[, lens]) batches, `depth` in flight (explainers/engine_base.py)."""
+        self._maps_stage("explain_stream")                # a refusal here, not inside the generator's first step
         return self._explain_stream(batches, depth, lambda eng, images, captions, lens: eng.explain_batch(
             captions, head_idx, images=images, lens=lens, accumulate=accumulate))
 

@@ -51,8 +51,9 @@ class ExplainerBase(object):
         raise NotImplementedError
 
     def _cnn(self, feat_nhwc, row2img):
-        """the encoder stage: (rows,P,C) at the encoder's features -> maps"""
-        return self.engine.cnn.relevance(feat_nhwc, row2img)
+        """the encoder stage: (rows,P,C) at the encoder's features -> maps, under this explainer's `lrp_params` (None: the preset;
+        explainers/engine_base.py: `_maps_stage`).  The value is passed, never written to the engine: engines are shared."""
+        return self.engine._maps_stage("explain_cnn", getattr(self, "lrp_params", None))(feat_nhwc, row2img)
 
     # ---- shared --------------------------------------------------------------------------------------------------------------------------
     def __init__(self, args, word_map, model=None):
@@ -60,6 +61,7 @@ class ExplainerBase(object):
         self.word_map = word_map
         self.vocab_size = len(word_map)
         self.model = model
+        self.lrp_params = None          # {"alpha": 2., "beta": 1.}: the Conv2d rule of `explain_cnn` (LRP explainers; None: the preset)
         from . import engine_cache
 
         def build():

@@ -31,6 +31,32 @@ def resnet_encoder_keys(state):
     return VGG_PREFIX + "conv1.weight" in state
 
 
+_LRP_PARAM_KEYS = ("alpha", "beta", "ignore_bias")      # the reference's own names (lrp_wrapper.add_lrp(model, lrp_params))
+_OWN = object()                                         # `_maps_stage`: read the engine's own `lrp_params`
+
+
+def _lrp_rule(where, lrp_params):
+    """`lrp_params` of an engine or a drop-in explainer -> None (the preset: None, or alpha 1 with beta 0) or (alpha, beta) of the
+    general Conv2d rule.  ValueError, named after `where`, for anything but a dict, unknown keys, non-finite or non-numeric values and
+    ignore_bias=False (the batched paths run the rule without bias).  Host logic: nothing touches the device."""
+    if lrp_params is None:
+        return None
+    if not isinstance(lrp_params, dict):
+        raise ValueError("{}: lrp_params must be None or a dict with the keys {}, got {!r}".format(where, _LRP_PARAM_KEYS, lrp_params))
+    unknown = sorted(str(k) for k in lrp_params if k not in _LRP_PARAM_KEYS)
+    if unknown:
+        raise ValueError("{}: lrp_params has unknown keys {} (known: {})".format(where, unknown, _LRP_PARAM_KEYS))
+    vals = []
+    for k, default in (("alpha", 1.), ("beta", 0.)):
+        v = lrp_params.get(k, default)
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not np.isfinite(float(v)):
+            raise ValueError("{}: lrp_params[{!r}] must be a finite number, got {!r}".format(where, k, v))
+        vals.append(float(v))
+    if not lrp_params.get("ignore_bias", True):
+        raise ValueError("{}: lrp_params['ignore_bias'] = False is not built on the batched paths (the rule runs without bias)".format(where))
+    return None if vals == [1., 0.] else (vals[0], vals[1])
+
+
 class _CapturedGraph(object):
     """a step captured in a HIP graph, with the surface of `_lib.Recording`: `result` (static outputs) and `replay()`"""
 
@@ -86,7 +112,55 @@ class EngineBase(object):
                                      [_t(state[k.replace(".weight", ".bias")], dev) for k in names])
             self.cnn = self.vgg
         self.resnet = encoder is not None
+        self.lrp_params = None          # the Conv2d rule of the encoder stage (`_maps_stage`); None: the preset, alpha 1 beta 0
         return sd
+
+    def _maps_stage(self, entry, lrp_params=_OWN):
+        """The encoder stage of `entry` under `self.lrp_params` ({"alpha": .., "beta": ..}; a drop-in explainer passes its own value, the
+        engine may be shared): validated here, at the top of the entry point and before any device work (`_lrp_rule`).  Returns
+        `maps_of(feat, row2img)`: `self.cnn.relevance` - today's call - for None or alpha 1 / beta 0; else the encoder's
+        `relevance_alpha_beta` (a ResNet encoder: in the engine's mode; VGG16: in the context's resolved conv mode, 0 or 1 - the split
+        modes 2 / 3 have no alpha-beta chain, ValueError).  The decoder is not touched: the reference applies alpha / beta to Conv2d only.
+        Without an encoder any value but None is a ValueError."""
+        where = "{}.{}".format(type(self).__name__, entry)
+        params = getattr(self, "lrp_params", None) if lrp_params is _OWN else lrp_params
+        rule = _lrp_rule(where, params)
+        if self.cnn is None:
+            if params is not None:
+                raise ValueError("{}: lrp_params is the encoder's Conv2d rule and this engine has no encoder".format(where))
+            return None
+        if rule is None:
+            return self.cnn.relevance
+        alpha, beta = rule
+        if self.resnet:
+            return lambda feat, row2img: self.cnn.relevance_alpha_beta(feat, row2img, alpha, beta)
+        o, cm, ff = _lib.VggOpts(), _lib.C.c_int(0), _lib.C.c_int(0)
+        o.conv_mode = -1 if self.vgg.conv_mode is None else int(self.vgg.conv_mode)
+        o.forward_f16 = -1 if self.vgg.forward_f16 is None else int(self.vgg.forward_f16)
+        check(_lib.load().lrpx_vgg16_resolve_opts(_lib.C.byref(o), _lib.C.byref(cm), _lib.C.byref(ff)))      # (host logic: no launch)
+        mode = cm.value
+        if mode not in (0, 1):
+            raise ValueError("{}: the alpha-beta rule runs in conv modes 0 and 1, the encoder context is in mode {}".format(where, mode))
+        return lambda feat, row2img: self.vgg.relevance_alpha_beta(feat, row2img, alpha, beta, conv_mode=mode)
+
+    def _features_stage(self, entry):
+        """an entry point on region features: there is no encoder stage, so `lrp_params` must be None (ValueError otherwise)"""
+        if getattr(self, "lrp_params", None) is not None:
+            raise ValueError("{}.{}: lrp_params is the encoder's Conv2d rule and features have no encoder stage".format(type(self).__name__, entry))
+
+    def _preset_only(self, entry, why):
+        """refuse `entry` under a Conv2d rule other than the preset (after validating `lrp_params`)"""
+        where = "{}.{}".format(type(self).__name__, entry)
+        params = getattr(self, "lrp_params", None)
+        if params is None:
+            return
+        if self.cnn is None:
+            raise ValueError("{}: lrp_params is the encoder's Conv2d rule and this engine has no encoder".format(where))
+        if _lrp_rule(where, params) is not None:
+            raise NotImplementedError("{}: not built under lrp_params = {!r} - {}".format(where, params, why))
+
+    _NO_STATIC_AB = "the per-trace coefficients of the alpha-beta chain are made lazily: the step is not recordable"
+    _NO_GRAD_AB = "alpha / beta belong to the LRP Conv2d rule; the gradient family has none"
 
     def _refuse_resnet(self, entry, missing):
         if self.resnet:
@@ -307,6 +381,8 @@ class EngineBase(object):
         while len(self._replicas) < depth:
             self._replicas.append(self.replica())
             self._streams.append(torch.cuda.Stream(device=self.device))
+        for rep in self._replicas[1:]:                                     # kept between calls: the rule may have been set since
+            rep.lrp_params = getattr(self, "lrp_params", None)
         pending = []
         for i, batch in enumerate(batches):
             images, captions = batch[0], batch[1]

@@ -346,11 +346,13 @@ class GridTDEngine(EngineBase):
 
     def explain_batch_graph(self, images, captions, accumulate=False, predictions=False):
         """`explain_batch` replayed from a captured HIP graph, one per (B,T) shape (explainers/engine_base.py: `_static_step`)."""
+        self._preset_only("explain_batch_graph", self._NO_STATIC_AB)
         self._refuse_resnet("explain_batch_graph", self._NO_GRAPH)
         return self._static(True, images, captions, accumulate, predictions)
 
     def explain_batch_replay(self, images, captions, accumulate=False, predictions=False):
         """`explain_batch` as a RECORDED step, one per input shape and stream (explainers/engine_base.py: `_static_step`)."""
+        self._preset_only("explain_batch_replay", self._NO_STATIC_AB)
         self._refuse_resnet("explain_batch_replay", self._NO_RECORDING)
         return self._static(False, images, captions, accumulate, predictions, _lib.stream_ptr().value,
                             self.vgg.conv_mode if self.vgg is not None else None)
@@ -412,6 +414,7 @@ class GridTDEngine(EngineBase):
         scores (B,T,T).  (No running sums here: the reference zeroes the image gradient per word, :1717.)
         gradcam=True: `ExplainGridTDGuidedGradCam` (:1796-1836) - every map times the 16x expanded Grad-CAM heat map of the
         same (guided) decoder gradient."""
+        self._preset_only("explain_batch_guided", self._NO_GRAD_AB)
         self._refuse_resnet("explain_batch_guided", self.GRADIENT_MISSING)
         images = images.to(self.device, torch.float32).contiguous()
         captions = captions.to(self.device, torch.int64).contiguous()
@@ -432,6 +435,7 @@ class GridTDEngine(EngineBase):
         """Batched `ExplainGridTDGradient.explain_caption` (models/gridTDmodel.py:1214-1539): plain
         decoder gradient + autograd gradient through the encoder -> maps (B,T,3,224,224), word scores (B,T,T).
         cam=True: `ExplainGridTDGradCam` (:1752-1771) - the per-word result is the Grad-CAM heat map (B,T,196)."""
+        self._preset_only("explain_batch_gradient", self._NO_GRAD_AB)
         self._refuse_resnet("explain_batch_gradient", self.GRADIENT_MISSING)
         images = images.to(self.device, torch.float32).contiguous()
         captions = captions.to(self.device, torch.int64).contiguous()
@@ -449,7 +453,10 @@ class GridTDEngine(EngineBase):
         Returns maps (B,T,3,H,W) and r_words (B,T,T) (row t holds t+1 valid entries).
         accumulate=True reproduces the running sums the reference returns (lrp_wrapper.py:64-82 quirk).
         predictions=True also computes the (B,T,V) scores the reference's explainer keeps (`self.predictions`, :1011; read
-        by evaluation.py:109) and returns them as a third tensor."""
+        by evaluation.py:109) and returns them as a third tensor.  The instance attribute `lrp_params` ({"alpha": 2., "beta": 1.};
+        None: the preset) selects the encoder's Conv2d rule (explainers/engine_base.py: `_maps_stage`); the decoder's rules, r_words and
+        the feature relevance do not depend on it."""
+        maps_of = self._maps_stage("explain_batch")
         images = images.to(self.device, torch.float32).contiguous()
         captions = captions.to(self.device, torch.int64).contiguous()
         B, T = captions.shape[0], captions.shape[1] - 1
@@ -459,11 +466,12 @@ class GridTDEngine(EngineBase):
         r_feat, r_words, row2img = self.relevance(enc, tr, rg)
         # unequal caption lengths (models/gridTDmodel.py:1147-1153 explains `caption_length` words): the chain runs on the
         # sum(lens) valid maps; `_finish` takes the result back to the padded layout
-        return self._finish(rg, B, T, r_feat, r_words, row2img, self.cnn.relevance, tuple(images.shape[1:]), accumulate=accumulate,
+        return self._finish(rg, B, T, r_feat, r_words, row2img, maps_of, tuple(images.shape[1:]), accumulate=accumulate,
                             extra=(tr["pred"],) if predictions else (), features=(tr, enc) if return_features else None)
 
     def explain_stream(self, batches, depth=3, accumulate=False):
         """`explain_batch` over an iterable of (images, captions[, lens]) batches, `depth` in flight (explainers/engine_base.py)."""
+        self._maps_stage("explain_stream")                # a refusal here, not inside the generator's first step
         return self._explain_stream(batches, depth, lambda eng, images, captions, lens: eng.explain_batch(images, captions, lens=lens,
                                                                                                          accumulate=accumulate))
 
@@ -575,6 +583,7 @@ class GridTDBUEngine(GridTDEngine):
         r_feat (B, T, P, C) - the relevance of the region features, zero in rows behind an image's last word (`lens`) - and r_words
         (B, T, T) (row t holds t + 1 valid entries); then the (B, T, V) scores with predictions=True; then the trace and `encode`'s
         dict with return_features=True."""
+        self._maps_stage("explain_batch")                 # no encoder: `lrp_params` must be None
         enc = self.encode(features)
         captions = captions.to(self.device, torch.int64).contiguous()
         B, T = captions.shape[0], captions.shape[1] - 1
@@ -603,6 +612,7 @@ class GridTDBUEngine(GridTDEngine):
 
     def explain_stream(self, batches, depth=3):
         """`explain_batch` over an iterable of (features, captions[, lens]) batches, `depth` in flight (explainers/engine_base.py)."""
+        self._maps_stage("explain_stream")
         return self._explain_stream(batches, depth, lambda eng, features, captions, lens: eng.explain_batch(features, captions, lens=lens))
 
     def _no_gradient(self, entry):

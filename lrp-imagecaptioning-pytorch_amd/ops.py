@@ -416,6 +416,8 @@ class Vgg16:
         self._ws = None
         self._weights = ws              # (the model's own fp32 tensors where it has them: the alpha-beta packs are built from these on demand)
         self._ab = None                 # relevance_alpha_beta: packs, Z+ / Z- of the current trace, workspace
+        self._ab1 = None                # relevance_alpha_beta(conv_mode=1): coefficients of the current trace, workspace
+        self._ab1_packs = {"fwd": {}, "bwd": {}, "bwd_pos": {}, "rows": {}}     # ... its packs: ONE holder, shared with every replica, filled on demand
         self._trace_serial = 0
         # per-context matrix-core mode (None = the process default of lrpx_set_conv_mode / lrpx_set_forward_f16): carried in
         # every call (lrpx_vgg16_opts), so contexts with different modes can be in flight on different streams / threads
@@ -453,6 +455,7 @@ class Vgg16:
         r = copy.copy(self)
         r.trace, r.n_img, r._ws = None, 0, None
         r._ab, r._trace_serial = None, 0
+        r._ab1 = None                   # (the mode-1 packs stay shared through `_ab1_packs`, whoever fills them first)
         if hasattr(r, "_ws_multi"):
             del r._ws_multi
         return r
@@ -571,7 +574,7 @@ class Vgg16:
                 conv_mfma(acts[l], pk, n, hw, k_in, cout, 9, EPI_PLAIN, oc_split=cout, out0=z)
         st["serial"] = self._trace_serial
 
-    def relevance_alpha_beta(self, r_feat_nhwc, map2img=None, alpha=2., beta=1., out=None, layer_ms=None):
+    def relevance_alpha_beta(self, r_feat_nhwc, map2img=None, alpha=2., beta=1., out=None, layer_ms=None, conv_mode=0):
         """compute_lrp (LRPtools/lrp_wrapper.py:63-87) with the preset's Conv2d rule replaced by the general alpha-beta rule without
         bias, R = alpha * lrp_backward(PosNetConv) - beta * lrp_backward(NegNetConv) (lrp_modules.py:124-150), for N maps:
         (N,196,512) -> (N,3,224,224); maps of one image share that image's trace through `map2img` (null = map n on image n), the
@@ -589,10 +592,20 @@ class Vgg16:
         its blocks on to the stage below, so each of the five stages owns two relevance buffers of 8 x 224^2 x 64 floats beside
         the one S2 buffer of 8 x 224^2 x 128 floats: 8 x 224^2 x (128 + 10 x 64) x 4 = 1 233 125 376 bytes.  A map's result does
         not depend on the blocks it travels in.
-        layer_ms: a list of 17 floats - the call then adds each layer's milliseconds (HIP events, one wait per layer: profiling)."""
+        layer_ms: a list of 17 floats - the call then adds each layer's milliseconds (HIP events, one wait per layer: profiling).
+
+        conv_mode=0 (the default) is everything above.  conv_mode=1 runs the rule in the exact bf16-split arithmetic of conv mode 1 on
+        the runtime-geometry engine, the design of `ResNetEncoder.relevance_alpha_beta`: per image and forward()
+        the coefficients qp = win / safe(Z+), qn = win / safe(Z-) (`_ab1_coef`; win: the Pool2d rule of a pool above the conv as a
+        0 / 1 factor), then per map 13 launches of `conv_geom_ab(b6=True)` - the operand (R qp) alpha | (R qn) (-beta) is formed
+        while the tile is gathered, under the four pools from the relevance at the POOLED resolution (pool=2) - and one
+        `resnet_stem_fold`.  No S2, no Pool2d pass; beta == 0 contracts over W+ alone.  The maps travel in blocks of AB1_BLOCK
+        through two relevance buffers; no kernel has atomics, a map's result does not depend on its block.  Modes 2 / 3: ValueError."""
         alpha, beta = float(alpha), float(beta)
         if not (alpha == alpha and beta == beta and abs(alpha) != float("inf") and abs(beta) != float("inf")):
             raise ValueError("relevance_alpha_beta: alpha and beta must be finite")
+        if isinstance(conv_mode, bool) or conv_mode not in (0, 1):
+            raise ValueError("relevance_alpha_beta: conv_mode is 0 (fp32 MFMA) or 1 (exact bf16 split), got {!r}".format(conv_mode))
         if self.trace is None:
             raise ValueError("relevance_alpha_beta: no trace - call forward() first")
         r_feat_nhwc = _dev(r_feat_nhwc).contiguous()
@@ -603,6 +616,8 @@ class Vgg16:
             if n_maps != self.n_img:
                 raise ValueError("relevance_alpha_beta: without map2img there is one map per image of the trace")
             map2img = torch.arange(n_maps, dtype=torch.int32, device=self.device)
+        if conv_mode == 1:
+            return self._ab1_chain(r_feat_nhwc, map2img.contiguous(), alpha, beta, out, layer_ms)
         st = self._ab_state()
         self._ab_zpn(st)
         if out is None:
@@ -654,6 +669,102 @@ class Vgg16:
             check(lib.lrpx_nhwc_to_nchw(ptr(r), ptr(o), nb, 3, 224 * 224, 8, stream_ptr()))
             check(lib.lrpx_nhwc_to_nchw(_lib.ptr_at(r, 3), ptr(tmp), nb, 3, 224 * 224, 8, stream_ptr()))
             check(lib.lrpx_accumulate(ptr(o), ptr(tmp), o.numel(), stream_ptr()))
+
+    # ---- the same rule on the exact bf16 splits: relevance_alpha_beta(conv_mode=1) ---------------------------------
+    AB1_BLOCK = 16      # maps per pass: two relevance buffers of 16 x 224^2 x 64 floats
+    AB1_COEF_FLOATS = 4 * 224 * 224 * 128       # the [Z+ | Z-] rows of one coefficient pass: 4 images at conv1_2, more where the maps are smaller
+    _GEOM3 = (3, 3, 1, 1, 1, 1)
+
+    def _ab1_state(self):
+        """bf16x3 packs of the 13 convs, built once per context from `self._weights`: `fwd`, the columns [W+ | W-] (conv1_1 on the
+        split image [x+ | x- | 0 0]: Z+ = x+ W+ + x- W-, Z- = x+ W- + x- W+) and `bwd`, the transposed pack of the rows [W+ ; W-]
+        (conv1_1: [W+ | W- | 0 0 ; W- | W+ | 0 0]); `bwd_pos`, the W+ rows alone, at the first call with beta == 0.  The packs live in
+        `_ab1_packs`, one holder that a context and all its replicas share (a replica made before the first alpha-beta call
+        included); coefficients and workspace are per context."""
+        st = self._ab1_packs
+        if not st["fwd"]:
+            convs = [l for l in range(17) if self.IS_CONV[l]]
+            for l, w in zip(convs, self._weights):
+                wt = w.detach().to(torch.float32)
+                wpos, wneg = wt.clamp(min=0), wt.clamp(max=0)
+                if l == 0:
+                    pad = torch.zeros(wt.shape[0], 8 - 2 * wt.shape[1], 3, 3, device=self.device)
+                    wpos, wneg = torch.cat([wpos, wneg, pad], 1), torch.cat([wneg, wpos, pad], 1)
+                rows = torch.cat([wpos, wneg], 0)
+                st["fwd"][l] = conv_geom_pack_bf16x3(rows, _lib.GEOM_FWD)
+                st["bwd"][l] = conv_geom_pack_bf16x3(rows, _lib.GEOM_BWD)
+                st["rows"][l] = wpos
+            torch.cuda.current_stream().synchronize()
+        if self._ab1 is None:
+            self._ab1 = dict(st, serial=-1, qp={}, qn={}, ws=None)      # (the pack dicts themselves: shared)
+        return self._ab1
+
+    def _ab1_coef(self, st):
+        """qp = win / safe(Z+), qn = win / safe(Z-) of the 13 convs, per IMAGE, from the trace's activations: one stacked forward
+        contraction [Z+ | Z-] (`conv_geom_ex`, exact splits, blocked sums) and one streaming pass (`vgg16_ab_coef`) per conv, a few images at a time;
+        win is the Pool2d rule of the pool above conv1_2 / 2_2 / 3_3 / 4_3 from that pool's input.  Independent of alpha and beta;
+        kept until the next forward() (13.5 M floats per image and coefficient: 108 MB per image)."""
+        if st["serial"] == self._trace_serial:
+            return
+        acts, _ = self.trace_views()
+        n = self.n_img
+        for l in st["fwd"]:
+            hw, k_in = self.ACT_DIMS[l]
+            cout = self.ACT_DIMS[l + 1][1]
+            pooled = l + 1 < 17 and not self.IS_CONV[l + 1]
+            for name in ("qp", "qn"):
+                if st[name].get(l) is None or st[name][l].shape[0] != n:
+                    st[name][l] = torch.empty(n, hw * hw, cout, dtype=torch.float32, device=self.device)
+            step = max(1, min(n, self.AB1_COEF_FLOATS // (hw * hw * 2 * cout)))
+            zz = torch.empty(step, hw * hw, 2 * cout, dtype=torch.float32, device=self.device)
+            for lo in range(0, n, step):
+                nb = min(step, n - lo)
+                conv_geom_ex(acts[l][lo: lo + nb], st["fwd"][l], _lib.GEOM_FWD, nb, (hw, hw), (hw, hw), self._GEOM3, k_in, 2 * cout,
+                             out=zz[:nb], b6=True, blocked=True)
+                vgg16_ab_coef(zz[:nb], st["qp"][l][lo: lo + nb], st["qn"][l][lo: lo + nb], nb, (hw, hw), cout,
+                              xpool=acts[l + 1][lo: lo + nb] if pooled else None)
+        st["serial"] = self._trace_serial
+
+    def _ab1_chain(self, r_feat, map2img, alpha, beta, out, layer_ms):
+        """relevance_alpha_beta(conv_mode=1) for checked arguments: block by block, top down, 13 `conv_geom_ab` + `resnet_stem_fold`"""
+        st = self._ab1_state()
+        self._ab1_coef(st)
+        dual = beta != 0.
+        if not dual and not st["bwd_pos"]:
+            for l, wpos in st["rows"].items():
+                st["bwd_pos"][l] = conv_geom_pack_bf16x3(wpos, _lib.GEOM_BWD)
+            torch.cuda.current_stream().synchronize()
+        packs = st["bwd"] if dual else st["bwd_pos"]
+        n_maps = r_feat.shape[0]
+        if out is None:
+            out = torch.empty(n_maps, 3, 224, 224, dtype=torch.float32, device=self.device)
+        map2img = check_map2img(map2img, n_maps, self.n_img)
+        per = 224 * 224 * 64
+        if st["ws"] is None or st["ws"].numel() != 2 * int(self.AB1_BLOCK) * per:
+            st["ws"] = torch.empty(2 * int(self.AB1_BLOCK) * per, dtype=torch.float32, device=self.device)
+        bufs = (st["ws"][: int(self.AB1_BLOCK) * per], st["ws"][int(self.AB1_BLOCK) * per:])
+        acts = self.trace_views()[0]
+        layers = [l for l in range(16, -1, -1) if self.IS_CONV[l]]
+        for lo in range(0, n_maps, int(self.AB1_BLOCK)):
+            nb = min(int(self.AB1_BLOCK), n_maps - lo)
+            r, m2i, cur = r_feat[lo: lo + nb], map2img[lo: lo + nb], 0
+            for l in layers:
+                ev = _events(layer_ms)
+                hw, k_in = self.ACT_DIMS[l]
+                cout = self.ACT_DIMS[l + 1][1]
+                pooled = l + 1 < 17 and not self.IS_CONV[l + 1]           # r is the relevance BEHIND the pool above this conv
+                r_new = bufs[cur][: nb * hw * hw * k_in].view(nb, hw * hw, k_in)
+                conv_geom_ab(r, packs[l], nb, (hw, hw), (hw, hw), self._GEOM3, cout, k_in, acts[l], st["qp"][l],
+                             q2=st["qn"][l] if dual else None, scale=alpha, scale2=-beta if dual else 0., map2img=m2i, n_img=self.n_img,
+                             out=r_new, validate=False, b6=True, pool=2 if pooled else 1)
+                r, cur = r_new, 1 - cur
+                if ev is not None:
+                    ev[1].record()
+                    ev[1].synchronize()
+                    layer_ms[l] += ev[0].elapsed_time(ev[1])
+            # conv1_1 left [x+ convT(.) | x- convT(.) | 0 0] in 8 channels: join the halves into the NCHW result
+            resnet_stem_fold(r, out[lo: lo + nb], nb, 3, 3, 8, 224 * 224)
+        return out
 
     def relevance(self, r_feat_nhwc, map2img=None, out=None, streams=1, layer_ms=None):
         """compute_lrp (LRPtools/lrp_wrapper.py:63-87) for N maps: (N,196,512) -> (N,3,224,224).
@@ -725,11 +836,12 @@ def check_map2img(map2img, n_maps, n_img):
 
 
 def _conv_geom_desc(fn, direction, inp, wpacked, n, hw, ohw, geom, k, n_oc, k_inp, kname, operands, bias, x, q, addend, map2img, n_img, out,
-                    validate):
+                    validate, pix_inp=None):
     """What the `conv_geom_ex` / `_ab` / `_grad` wrappers share, each refusal once under the wrapper's name `fn`: the shapes of the
     transposed direction's per-image `operands` = (name, tensor, kind, required), kind 'x' (n_img, H W, n_oc) | 'q' (n_img, OH OW, k_inp)
     | 'k' (k_inp,), of the addend and of the input (k_inp channels, named `kname`; k is the contraction's length), `check_map2img`
-    where asked, `out` allocated or refused.  -> (the base ConvGeomExDesc, out)."""
+    where asked, `out` allocated or refused.  pix_inp: the pixels per map of the input where they are not the source map's (the pooled
+    operand of `conv_geom_ab(pool=2)`).  -> (the base ConvGeomExDesc, out)."""
     bwd = direction == _lib.GEOM_BWD
     pix_in, pix_out = (ohw[0] * ohw[1], hw[0] * hw[1]) if bwd else (hw[0] * hw[1], ohw[0] * ohw[1])
     if bwd:
@@ -743,8 +855,9 @@ def _conv_geom_desc(fn, direction, inp, wpacked, n, hw, ohw, geom, k, n_oc, k_in
             raise ValueError("{}: addend must have the output's shape".format(fn))
         if map2img is not None and validate:
             map2img = check_map2img(map2img, n, n_img)
-    if inp.numel() != n * pix_in * k_inp:
-        raise ValueError("{}: the input must hold n x pixels x {} = {} x {} x {} floats".format(fn, kname, n, pix_in, k_inp))
+    pix_inp = pix_in if pix_inp is None else pix_inp
+    if inp.numel() != n * pix_inp * k_inp:
+        raise ValueError("{}: the input must hold n x pixels x {} = {} x {} x {} floats".format(fn, kname, n, pix_inp, k_inp))
     if out is None:
         out = torch.empty(n, pix_out, n_oc, dtype=torch.float32, device=inp.device)
     elif out.numel() != n * pix_out * n_oc:
@@ -754,14 +867,21 @@ def _conv_geom_desc(fn, direction, inp, wpacked, n, hw, ohw, geom, k, n_oc, k_in
 
 
 def conv_geom_ex(inp, wpacked, direction, n, hw, ohw, geom, k, n_oc, bias=None, x=None, q=None, addend=None, map2img=None, n_img=None,
-                 out=None, validate=True, b6=False):
+                 out=None, validate=True, b6=False, blocked=False):
     """`lrpx_conv_geom_ex` (csrc/conv_geom.hip; b6: `lrpx_conv_geom_ex_b6`, csrc/conv_geom_b6.hip, the exact bf16-split arithmetic of
     conv mode 1, with wpacked from `conv_geom_pack_bf16x3`), NHWC fp32; hw / ohw / geom as `conv_geom`.  GEOM_FWD: inp (n, H W, k) -> out
     (n, OH OW, n_oc) (+ bias).  GEOM_BWD: inp (n maps, OH OW, k) -> out (n, H W, n_oc) = x[img] * convT(inp * q[img]) + addend with
     img = map2img[m] (None: identity); x (n_img, H W, n_oc), q (n_img, OH OW, k), addend like out.  validate: check map2img on the host
-    first (`check_map2img`; a caller that already has passes False)."""
+    first (`check_map2img`; a caller that already has passes False).  blocked (b6, GEOM_FWD only): `lrpx_conv_geom_ex_b6_blocked`, the same
+    sums in a blocked order - fewer roundings at the running sum's size, for the Z+ / Z- of the alpha-beta coefficients."""
+    if blocked and (not b6 or direction != _lib.GEOM_FWD):
+        raise ValueError("conv_geom_ex: blocked goes with b6 and the forward direction")
     d, out = _conv_geom_desc("conv_geom_ex", direction, inp, wpacked, n, hw, ohw, geom, k, n_oc, k, "k",
                              (("x", x, "x", True), ("q", q, "q", False)), bias, x, q, addend, map2img, n_img, out, validate)
+    if blocked:
+        _count("conv_geom_ex_b6_blocked", direction)
+        check(_lib.load().lrpx_conv_geom_ex_b6_blocked(C.byref(d), stream_ptr()))
+        return out
     if b6:
         _count("conv_geom_ex_b6", direction)
         check(_lib.load().lrpx_conv_geom_ex_b6(C.byref(d), stream_ptr()))
@@ -772,21 +892,42 @@ def conv_geom_ex(inp, wpacked, direction, n, hw, ohw, geom, k, n_oc, bias=None, 
 
 
 def conv_geom_ab(inp, wpacked, n, hw, ohw, geom, kr, n_oc, x, q, q2=None, scale=1., scale2=0., addend=None, map2img=None, n_img=None,
-                 out=None, validate=True, b6=False):
+                 out=None, validate=True, b6=False, pool=1):
     """`lrpx_conv_geom_ab` (b6: `lrpx_conv_geom_ab_b6`): the transposed direction of `conv_geom_ex` with two coefficients, the general
     alpha-beta rule of a conv without bias (include/lrpx.h).  inp (n maps, OH OW, kr) -> out (n, H W, n_oc) =
     x[img] * (convT((inp q[img]) scale, W+) + convT((inp q2[img]) scale2, W-)) + addend; q / q2 (n_img, OH OW, kr).  wpacked: the
     transposed pack of the rows [W+ ; W-] (2 kr of them) - or, with q2 None (beta == 0), of W+ alone: the contraction then runs over
-    kr only.  LAUNCHES counts the two under 'conv_geom_ab_dual' and 'conv_geom_ab' (b6: + '_b6')."""
+    kr only.  LAUNCHES counts the two under 'conv_geom_ab_dual' and 'conv_geom_ab' (b6: + '_b6').
+    pool=2 (`lrpx_conv_geom_ab_pool`, `_b6`): the conv sits directly under a 2x2 / stride-2 max-pool and inp is the
+    relevance BEHIND the pool, (n maps, (OH // 2) (OW // 2), kr); q / q2 stay at the conv's resolution and carry the pool's winner
+    factor (`vgg16_ab_coef`).  LAUNCHES: the same names + '_pool'.  Any other pool but 1 is refused."""
+    if pool not in (1, 2):
+        raise ValueError("conv_geom_ab: pool is 1 (none) or 2 (kernel = stride = 2, no padding, floor mode), got {!r}".format(pool))
     base, out = _conv_geom_desc("conv_geom_ab", _lib.GEOM_BWD, inp, wpacked, n, hw, ohw, geom, kr if q2 is None else 2 * kr, n_oc, kr, "kr",
                                 (("x", x, "x", True), ("q", q, "q", True), ("q2", q2, "q", False)), None, x, q, addend, map2img, n_img, out,
-                                validate)
+                                validate, pix_inp=(ohw[0] // 2) * (ohw[1] // 2) if pool == 2 else None)
     d = _lib.ConvGeomAbDesc(base, ptr(_dev(q2)), scale, scale2, kr)
-    name = "conv_geom_ab" + ("" if q2 is None else "_dual") + ("_b6" if b6 else "")
+    name = "conv_geom_ab" + ("" if q2 is None else "_dual") + ("_b6" if b6 else "") + ("_pool" if pool == 2 else "")
     _count(name, _lib.GEOM_BWD)
     lib = _lib.load()
+    if pool == 2:
+        dp = _lib.ConvGeomAbPoolDesc(d, 2)
+        check((lib.lrpx_conv_geom_ab_pool_b6 if b6 else lib.lrpx_conv_geom_ab_pool)(C.byref(dp), stream_ptr()))
+        return out
     check((lib.lrpx_conv_geom_ab_b6 if b6 else lib.lrpx_conv_geom_ab)(C.byref(d), stream_ptr()))
     return out
+
+
+def vgg16_ab_coef(zz, qp, qn, n_img, ohw, c, xpool=None):
+    """`lrpx_vgg16_ab_coef`: zz (n_img, OH OW, 2c) = [Z+ | Z-] -> qp, qn (n_img, OH OW, c) = win / safe(Z+), win / safe(Z-); xpool
+    (n_img, OH OW, c), the input of the 2x2 max-pool above the conv: win = 1 at each window's first non-zero maximum, 0 elsewhere
+    (None: win = 1).  The per-image coefficients of `conv_geom_ab` on VGG16."""
+    pix = ohw[0] * ohw[1]
+    for name, t, ch in (("zz", zz, 2 * c), ("qp", qp, c), ("qn", qn, c), ("xpool", xpool, c)):
+        if t is not None and (_dev(t).numel() != n_img * pix * ch or not t.is_contiguous() or t.dtype != torch.float32):
+            raise ValueError("vgg16_ab_coef: {} must be contiguous fp32 of n_img x OH OW x {} = {} x {} x {}".format(name, ch, n_img, pix, ch))
+    _count("vgg16_ab_coef")
+    check(_lib.load().lrpx_vgg16_ab_coef(ptr(zz), ptr(xpool), ptr(qp), ptr(qn), n_img, ohw[0], ohw[1], c, stream_ptr()))
 
 
 def conv_geom_grad(inp, wpacked, n, hw, ohw, geom, k, n_oc, mask=None, scale=None, clamp=False, addend=None, map2img=None, n_img=None,
