@@ -563,6 +563,48 @@ int lrpx_lrp_reweight_rows(const float* pred, long ld, int V, const float* h, lo
  * best first (ties: lower flat index).  cum may be NULL (zeros). */
 int lrpx_beam_topk(const float* x, long ld, int n_rows, int n, const float* cum, int k, long long* out_idx, float* out_val,
                    void* stream);
+/* The same beam search for N images at once with its state on the device: no device -> host read per step.  Image i owns rows
+ * i k .. i k + k - 1 of the decoder trace (k = beam size <= 4), its live rows first, in the order the reference keeps them.
+ *   toks       [N k][tok_ld] int64, tok_ld >= T + 1: the live sequences; column t is the decoder's input of step t.  The caller fills ALL of
+ *              it with start_id: a row that is not live carries a valid id for the embedding gather, and is never read by a selection
+ *   cum        [N k] cumulative scores (zeros), n_live [N] (k), best [N][best_ld >= T + 1] / best_len [N] (zeros) / best_score [N]: the
+ *              best complete sequence so far - a later one replaces it only with a strictly greater score (the reference takes the
+ *              first maximum in order of completion, :469-470)
+ *   live_images  one int, N at the start: the images with n_live > 0 (a caller may poll it to stop early; the result does not depend on it)
+ *   end_id / end_ids   the <end> id, or one per image (device, may be NULL)
+ *   state      up to 4 tensors [N k][T + 1][state_w] (row stride state_ld floats): the LSTM state the decoder step t wrote at time t + 1
+ * lrpx_beam_step_batch, after the decoder step t and its scores x [N k][ld >= V]: selection (the arithmetic of lrpx_beam_topk: step 0
+ * row 0 alone with k candidates, else n_live rows and n_live candidates, flat index r V + w, ties to the lower index), the bookkeeping
+ * (:447-467: append the word, set <end> candidates aside in ascending candidate index, compact the survivors in their order), toks
+ * column t + 1, cum, and the state at time t + 1 gathered by the survivors' parents - ONE launch, one workgroup per image.  An image whose
+ * n_live is 0 is not touched.  The first step (t = 0) validates every pointer, the later ones under LRPX_CHECK_PTRS=1.
+ * lrpx_beam_result_batch after `steps` steps: out[i] = [length, tokens ...] (out_ld >= T + 2 int64) - the best complete sequence, or
+ * live sequence 0 cut to 20 tokens (:472); incl. <start>.
+ * T = max_cap_length <= LRPX_BEAM_MAX_STEPS: the kernel keeps one thread per sequence position; larger values are LRPX_EINVAL. */
+#define LRPX_BEAM_MAX_STEPS 1024
+typedef struct lrpx_beam_batch {
+    int N, k, V, T;
+    int start_id, end_id;
+    const int32_t* end_ids;
+    long long* toks;
+    long long* best;
+    float *cum, *best_score;
+    int32_t *n_live, *best_len, *live_images;
+    float* state[4];
+    long state_ld;
+    int tok_ld, best_ld, state_w, n_state;
+} lrpx_beam_batch;
+int lrpx_beam_step_batch(const lrpx_beam_batch* p, const float* x, long ld, int t, void* stream);
+int lrpx_beam_result_batch(const lrpx_beam_batch* p, int steps, long long* out, int out_ld, void* stream);
+/* out[r] = softmax(x[r,:n])[ids[r]] (evaluation.py:122, :149, :252: the score of one word); an id outside [0, n) gives NaN */
+int lrpx_softmax_pick_rows(const float* x, long ld, int rows, int n, const long long* ids, float* out, void* stream);
+/* word ablation (evaluation.py:242-247): row r is a caption prefix caps[r][0 .. t[r]] (column 0 = <start>) with the relevance of its
+ * words r_words[r][0 .. t[r]].  The kdel <= LRPX_DELETE_MAX positions 1 + topk(r_words[r][1 : t + 1], kdel) are dropped (position 0 is never
+ * a candidate; ties: lower position; fewer than kdel candidates: all of them), the others keep their order: out[r][0 .. out_len[r] - 1].
+ * deleted (may be NULL): [rows][kdel] the dropped positions, most relevant first, -1 where there was none. */
+#define LRPX_DELETE_MAX 4
+int lrpx_delete_topk_tokens(const long long* caps, int cap_ld, const float* r_words, int rw_ld, const int32_t* t, int rows, int kdel,
+                            long long* out, int out_ld, int32_t* out_len, int32_t* deleted, void* stream);
 /* scratch: [B][3*P] floats (scores, W_g h, W_s s) */
 int lrpx_gridtd_fwd_attention(const lrpx_gridtd_trace* tr, int t, const float* Vp, const float* att_img,
                               const float* Wg, const float* Ws, const float* bs, const float* wh, float* scratch,

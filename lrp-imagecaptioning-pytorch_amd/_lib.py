@@ -58,6 +58,13 @@ class GridStepArgs(C.Structure):
         "w_il1", "b_il1", "w_il2", "b_il2")]
 
 
+class BeamBatch(C.Structure):
+    """lrpx_beam_batch: the device state of a batched beam search (lrpx_beam_step_batch)"""
+    _fields_ = [("N", _i), ("k", _i), ("V", _i), ("T", _i), ("start_id", _i), ("end_id", _i), ("end_ids", _f), ("toks", _f), ("best", _f),
+                ("cum", _f), ("best_score", _f), ("n_live", _f), ("best_len", _f), ("live_images", _f), ("state", _f * 4), ("state_ld", _l),
+                ("tok_ld", _i), ("best_ld", _i), ("state_w", _i), ("n_state", _i)]
+
+
 class AdaTrace(C.Structure):
     """lrpx_adaatt_trace"""
     _fields_ = [("B", _i), ("T", _i), ("H", _i), ("E", _i), ("P", _i)] + [(k, _f) for k in (
@@ -267,6 +274,10 @@ SIGNATURES = {
     "lrpx_vgg16_guided_backprop_ex": (_i, [_f, _f, _i, _f, _f, _i, _f, _f, C.POINTER(VggOpts), _f]),
     "lrpx_vgg16_gradient_ex": (_i, [_f, _f, _i, _f, _f, _i, _f, _f, C.POINTER(VggOpts), _f]),
     "lrpx_beam_topk": (_i, [_f, _l, _i, _i, _f, _i, _f, _f, _f]),
+    "lrpx_beam_step_batch": (_i, [C.POINTER(BeamBatch), _f, _l, _i, _f]),
+    "lrpx_beam_result_batch": (_i, [C.POINTER(BeamBatch), _i, _f, _i, _f]),
+    "lrpx_softmax_pick_rows": (_i, [_f, _l, _i, _i, _f, _f, _f]),
+    "lrpx_delete_topk_tokens": (_i, [_f, _i, _f, _i, _f, _i, _i, _f, _i, _f, _f, _f]),
     "lrpx_guided_gradcam": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _f]),
     "lrpx_linear_eps_rule": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _f]),
     "lrpx_batchnorm_rule": (_i, [_f, _f, _f, _f, _f, _f, C.c_float, _f, _l, _i, _l, _i, _f]),

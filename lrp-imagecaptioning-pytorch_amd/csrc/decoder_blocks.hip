@@ -256,10 +256,13 @@ __global__ __launch_bounds__(256) void argmax_logprob_rows_kernel(const float* _
 // log-sum-exps, a per-thread top-k (k <= 4) over the flat range, then k rounds of a block-wide arg-max over the list heads
 // (1024 threads: one workgroup has to walk n_rows x vocab scores three times, so the width of the group is the speed).
 // Ties: lower flat index first.
+// The selection is `beam_topk_block`: `beam_topk_kernel` (one image, the winners go to memory) and `beam_step_batch_kernel` (one workgroup
+// per image, the winners stay in registers for the bookkeeping) call the same body - the same sums in the same order.  Every thread
+// returns the k winners, best first: win_i[o] the flat index (BEAM_NONE where the range holds fewer than k scores), win_v[o] the score.
+constexpr int BEAM_NONE = 0x7fffffff;
 template <int KMAX>
-__global__ __launch_bounds__(1024) void beam_topk_kernel(const float* __restrict__ x, long ld, int n_rows, int n,
-                                                         const float* __restrict__ cum, int k,
-                                                         long long* __restrict__ out_idx, float* __restrict__ out_val) {
+__device__ __forceinline__ void beam_topk_block(const float* __restrict__ x, long ld, int n_rows, int n,
+                                                const float* __restrict__ cum, int k, int (&win_i)[KMAX], float (&win_v)[KMAX]) {
     constexpr int NT = 1024, NW = NT / 64;
     __shared__ float red[NW];
     __shared__ float lse[8];
@@ -333,8 +336,192 @@ __global__ __launch_bounds__(1024) void beam_topk_kernel(const float* __restrict
             best = take ? cv[w] : best; bidx = take ? ci[w] : bidx;
         }
         if (bidx != 0x7fffffff && vi == bidx) ++head;                       // the owner of the winner moves on to its next candidate
-        if (tid == 0) { out_idx[o] = bidx != 0x7fffffff ? bidx : 0; out_val[o] = best; }
+#pragma unroll
+        for (int j = 0; j < KMAX; ++j) if (j == o) { win_i[j] = bidx; win_v[j] = best; }
     }
+}
+
+template <int KMAX>
+__global__ __launch_bounds__(1024) void beam_topk_kernel(const float* __restrict__ x, long ld, int n_rows, int n,
+                                                         const float* __restrict__ cum, int k,
+                                                         long long* __restrict__ out_idx, float* __restrict__ out_val) {
+    int wi[KMAX];
+    float wv[KMAX];
+    beam_topk_block<KMAX>(x, ld, n_rows, n, cum, k, wi, wv);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int j = 0; j < KMAX; ++j)
+            if (j < k) { out_idx[j] = wi[j] != BEAM_NONE ? wi[j] : 0; out_val[j] = wv[j]; }
+    }
+}
+
+// one of four registers by a run-time s (an indexed register array would leave the registers)
+template <typename T>
+__device__ __forceinline__ T beam_pick(T a, T b, T c, T d, int s) {
+    T r = a;
+    r = s == 1 ? b : r;
+    r = s == 2 ? c : r;
+    r = s == 3 ? d : r;
+    return r;
+}
+
+// One step of the reference's beam search (models/gridTDmodel.py:437-467) for N images, one workgroup per image, the state on the device
+// (lrpx_beam_batch, include/lrpx.h).  Image i owns rows i k .. i k + k - 1, live rows first.  The selection is `beam_topk_block` over the
+// image's live rows (step 0: row 0 alone with k candidates, :440-443); the bookkeeping - what `run_beam_search` (explainers/beam.py) does in
+// Python lists - runs in every thread on the same registers: a candidate that is <end> is set aside and replaces the kept complete
+// sequence only with a strictly greater score (candidates come best first, the reference keeps the first maximum, :469-470), the others
+// are compacted to the front in their order.  Then thread c owns column c: it reads the k tokens of sequence position c (and the k values
+// of every state tensor's feature c at time t + 1) into registers and writes them back permuted - no scratch buffer and no
+// read-after-write hazard.  An image without live rows is a no-op.
+template <int KMAX>
+__global__ __launch_bounds__(1024) void beam_step_batch_kernel(const lrpx_beam_batch p, const float* __restrict__ x, long ld, int t) {
+    constexpr int NT = 1024;
+    static_assert(KMAX == 4, "beam_pick takes four registers");
+    const int img = blockIdx.x, tid = threadIdx.x, k = p.k, V = p.V;
+    const int nl = p.n_live[img];
+    if (nl == 0) return;
+    const bool had = p.best_len[img] > 0;
+    const float had_score = p.best_score[img];
+    const long r0 = (long)img * k;
+    const int kc = t == 0 ? k : nl;
+    int wi[KMAX];
+    float wv[KMAX];
+    beam_topk_block<KMAX>(x + r0 * ld, ld, t == 0 ? 1 : nl, V, p.cum + r0, kc, wi, wv);
+    const int end = p.end_ids ? p.end_ids[img] : p.end_id;
+    int src[KMAX], word[KMAX];
+    float sc[KMAX];
+#pragma unroll
+    for (int j = 0; j < KMAX; ++j) { src[j] = 0; word[j] = p.start_id; sc[j] = 0.f; }
+    int nn = 0, done_src = -1;
+    float best_score = had_score;
+    bool has = had;
+#pragma unroll
+    for (int o = 0; o < KMAX; ++o) {
+        const int flat = wi[o] != BEAM_NONE ? wi[o] : 0;
+        const int b = flat / V, w = flat - b * V;
+        if (o >= kc) {
+        } else if (w == end) {
+            if (!has || wv[o] > best_score) { has = true; best_score = wv[o]; done_src = b; }
+        } else {
+#pragma unroll
+            for (int j = 0; j < KMAX; ++j) if (j == nn) { src[j] = b; word[j] = w; sc[j] = wv[o]; }
+            ++nn;
+        }
+    }
+    __syncthreads();                                   // (every thread has read cum, n_live and the kept score)
+    if (const int c = tid; c <= t) {                  // one thread per sequence position: t < LRPX_BEAM_MAX_STEPS = NT
+        long long v[KMAX];
+#pragma unroll
+        for (int j = 0; j < KMAX; ++j) v[j] = j < k ? p.toks[(r0 + j) * p.tok_ld + c] : 0;
+        if (done_src >= 0) p.best[(long)img * p.best_ld + c] = beam_pick(v[0], v[1], v[2], v[3], done_src);
+#pragma unroll
+        for (int j = 0; j < KMAX; ++j) if (j < nn) p.toks[(r0 + j) * p.tok_ld + c] = beam_pick(v[0], v[1], v[2], v[3], src[j]);
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        if (s >= p.n_state) continue;
+        float* st = p.state[s] + (long)(t + 1) * p.state_w;
+        for (int c = tid; c < p.state_w; c += NT) {
+            float v[KMAX];
+#pragma unroll
+            for (int j = 0; j < KMAX; ++j) v[j] = j < k ? st[(r0 + j) * p.state_ld + c] : 0.f;
+#pragma unroll
+            for (int j = 0; j < KMAX; ++j) if (j < nn) st[(r0 + j) * p.state_ld + c] = beam_pick(v[0], v[1], v[2], v[3], src[j]);
+        }
+    }
+    if (tid == 0) {
+#pragma unroll
+        for (int j = 0; j < KMAX; ++j)
+            if (j < k) {
+                p.toks[(r0 + j) * p.tok_ld + t + 1] = j < nn ? word[j] : p.start_id;      // rows that are not live carry a valid id
+                if (j < nn) p.cum[r0 + j] = sc[j];
+            }
+        p.n_live[img] = nn;
+        if (done_src >= 0) {
+            p.best[(long)img * p.best_ld + t + 1] = end;
+            p.best_len[img] = t + 2;
+            p.best_score[img] = best_score;
+        }
+        if (nn == 0) atomicSub(p.live_images, 1);
+    }
+}
+
+// the result of a batched beam search after `steps` steps: out[i] = [length, tokens ...] - the kept complete sequence, or live sequence 0
+// cut to 20 tokens (:472)
+__global__ __launch_bounds__(256) void beam_result_batch_kernel(const lrpx_beam_batch p, int steps, long long* __restrict__ out, int out_ld) {
+    const int img = blockIdx.x;
+    const int bl = p.best_len[img];
+    const int len = bl > 0 ? bl : min(steps + 1, 20);
+    const long long* from = bl > 0 ? p.best + (long)img * p.best_ld : p.toks + (long)img * p.k * p.tok_ld;
+    long long* o = out + (long)img * out_ld;
+    if (threadIdx.x == 0) o[0] = len;
+    for (int c = threadIdx.x; c < len; c += 256) o[1 + c] = from[c];
+}
+
+// softmax(x[r])[ids[r]] per row (the reference's `torch.softmax(scores, dim=-1)[word]`, evaluation.py:122, :149, :252): one block per row,
+// the reduction shape of argmax_logprob_rows_kernel
+__global__ __launch_bounds__(256) void softmax_pick_rows_kernel(const float* __restrict__ x, long ld, int n, const long long* __restrict__ ids,
+                                                                float* __restrict__ out) {
+    __shared__ float red[8];
+    const int tid = threadIdx.x;
+    const float* r = x + (long)blockIdx.x * ld;
+    float m = -INFINITY;
+    for (int i = tid; i < n; i += 256) m = fmaxf(m, r[i]);
+    m = block_max(m, red);
+    float se = 0.f;
+    for (int i = tid; i < n; i += 256) se += expf(r[i] - m);
+    se = block_sum(se, red);
+    if (tid == 0) {
+        const long long id = ids[blockIdx.x];
+        out[blockIdx.x] = (id >= 0 && id < n) ? expf(r[id] - m) / se : NAN;
+    }
+}
+
+// word ablation (evaluation.py:242-247): row r holds a caption prefix of t + 1 tokens and the relevance of its words; the kdel most
+// relevant of the positions 1 .. t (<start> is never a candidate; ties: lower position) are dropped, the others keep their order.
+// One wave per row: kdel rounds of an arg-max over the positions (lane p - 1, p + 63, ...).
+__global__ __launch_bounds__(64) void delete_topk_tokens_kernel(const long long* __restrict__ caps, int cap_ld, const float* __restrict__ rw,
+                                                                int rw_ld, const int* __restrict__ ts, int kdel,
+                                                                long long* __restrict__ out, int out_ld, int* __restrict__ out_len,
+                                                                int* __restrict__ deleted) {
+    const int row = blockIdx.x, lane = threadIdx.x;
+    const int t = max(0, min(ts[row], min(cap_ld, min(rw_ld, out_ld)) - 1));      // (a t past a row's end never leaves the row)
+    const long long* cp = caps + (long)row * cap_ld;
+    const float* rp = rw + (long)row * rw_ld;
+    int gone[LRPX_DELETE_MAX];
+#pragma unroll
+    for (int d = 0; d < LRPX_DELETE_MAX; ++d) gone[d] = -1;
+#pragma unroll
+    for (int d = 0; d < LRPX_DELETE_MAX; ++d) {
+        if (d >= kdel) continue;
+        float bv = -INFINITY; int bi = BEAM_NONE;
+        for (int pos = 1 + lane; pos <= t; pos += 64) {
+            bool taken = false;
+#pragma unroll
+            for (int e = 0; e < LRPX_DELETE_MAX; ++e) taken = taken || gone[e] == pos;
+            const float v = rp[pos];
+            if (!taken && (bi == BEAM_NONE || v > bv)) { bv = v; bi = pos; }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const float ov = __shfl_xor(bv, off, 64); const int oi = __shfl_xor(bi, off, 64);
+            const bool take = oi != BEAM_NONE && (bi == BEAM_NONE || ov > bv || (ov == bv && oi < bi));
+            bv = take ? ov : bv; bi = take ? oi : bi;
+        }
+#pragma unroll
+        for (int e = 0; e < LRPX_DELETE_MAX; ++e) if (e == d) gone[e] = bi == BEAM_NONE ? -1 : bi;
+        if (lane == 0 && deleted) deleted[(long)row * kdel + d] = bi == BEAM_NONE ? -1 : bi;
+    }
+    int n_gone = 0;
+#pragma unroll
+    for (int e = 0; e < LRPX_DELETE_MAX; ++e) n_gone += gone[e] >= 0;
+    for (int pos = lane; pos <= t; pos += 64) {
+        int before = 0; bool taken = false;
+#pragma unroll
+        for (int e = 0; e < LRPX_DELETE_MAX; ++e) { before += gone[e] >= 0 && gone[e] < pos; taken = taken || gone[e] == pos; }
+        if (!taken) out[(long)row * out_ld + pos - before] = cp[pos];
+    }
+    if (lane == 0) out_len[row] = t + 1 - n_gone;
 }
 
 
@@ -471,6 +658,59 @@ int lrpx_beam_topk(const float* x, long ld, int n_rows, int n, const float* cum,
     hipLaunchKernelGGL((beam_topk_kernel<4>), dim3(1), dim3(1024), 0, (hipStream_t)stream, x, ld, n_rows, n, cum, k, out_idx,
                        out_val);
     return check_launch("beam_topk");
+}
+
+int lrpx_beam_step_batch(const lrpx_beam_batch* p, const float* x, long ld, int t, void* stream) {
+    LRPX_REQUIRE(p, "beam_step_batch: null state");
+    LRPX_REQUIRE(p->k >= 1 && p->k <= 4 && p->N >= 1 && p->V >= 1 && (long)p->k * p->V < 0x7fffffffL,
+                 "beam_step_batch: bad arguments (beam size 1..4, N >= 1, V >= 1; got k = %d, N = %d, V = %d)", p->k, p->N, p->V);
+    LRPX_REQUIRE(p->T >= 1 && p->T <= LRPX_BEAM_MAX_STEPS, "beam_step_batch: max_cap_length %d outside 1..%d (one thread per sequence position)",
+                 p->T, LRPX_BEAM_MAX_STEPS);
+    LRPX_REQUIRE(t >= 0 && t < p->T && p->tok_ld > p->T && p->best_ld > p->T && ld >= p->V, "beam_step_batch: step %d of %d, or a row stride shorter than its rows", t, p->T);
+    LRPX_REQUIRE(x && p->toks && p->cum && p->n_live && p->best && p->best_len && p->best_score && p->live_images, "beam_step_batch: null pointer");
+    LRPX_REQUIRE(p->n_state >= 0 && p->n_state <= 4 && (p->n_state == 0 || (p->state_w >= 1 && p->state_ld >= (long)(p->T + 1) * p->state_w)),
+                 "beam_step_batch: at most 4 state tensors (rows, T + 1, width)");
+    for (int s = 0; s < p->n_state; ++s) LRPX_REQUIRE(p->state[s], "beam_step_batch: null state tensor %d", s);
+#define LRPX_BEAM_PTRS {x, "x"}, {p->end_ids, "end_ids"}, {p->toks, "toks"}, {p->cum, "cum"}, {p->n_live, "n_live"}, {p->best, "best"},         \
+                       {p->best_len, "best_len"}, {p->best_score, "best_score"}, {p->live_images, "live_images"}, {p->n_state > 0 ? p->state[0] : nullptr, "state[0]"},    \
+                       {p->n_state > 1 ? p->state[1] : nullptr, "state[1]"}, {p->n_state > 2 ? p->state[2] : nullptr, "state[2]"},               \
+                       {p->n_state > 3 ? p->state[3] : nullptr, "state[3]"}
+    if (t == 0) {      // the first step of a search looks at every pointer; the later ones only under LRPX_CHECK_PTRS=1, like their neighbours
+        LRPX_CHECK_PTRS("lrpx_beam_step_batch", LRPX_BEAM_PTRS);
+    } else {
+        LRPX_CHECK_PTRS_OPT("lrpx_beam_step_batch", LRPX_BEAM_PTRS);
+    }
+#undef LRPX_BEAM_PTRS
+    hipLaunchKernelGGL((beam_step_batch_kernel<4>), dim3(p->N), dim3(1024), 0, (hipStream_t)stream, *p, x, ld, t);
+    return check_launch("beam_step_batch");
+}
+
+int lrpx_beam_result_batch(const lrpx_beam_batch* p, int steps, long long* out, int out_ld, void* stream) {
+    LRPX_REQUIRE(p && out, "beam_result_batch: null pointer");
+    LRPX_CHECK_PTRS("lrpx_beam_result_batch", {out, "out"}, {p->toks, "toks"}, {p->best, "best"}, {p->best_len, "best_len"});
+    LRPX_REQUIRE(p->k >= 1 && p->k <= 4 && p->N >= 1 && p->T >= 1 && p->T <= LRPX_BEAM_MAX_STEPS && steps >= 1 && steps <= p->T &&
+                     p->tok_ld > p->T && p->best_ld > p->T && out_ld >= p->T + 2 && p->toks && p->best && p->best_len,
+                 "beam_result_batch: bad arguments (out rows hold the length and T + 1 tokens)");
+    hipLaunchKernelGGL(beam_result_batch_kernel, dim3(p->N), dim3(256), 0, (hipStream_t)stream, *p, steps, out, out_ld);
+    return check_launch("beam_result_batch");
+}
+
+int lrpx_softmax_pick_rows(const float* x, long ld, int rows, int n, const long long* ids, float* out, void* stream) {
+    LRPX_CHECK_PTRS_OPT("lrpx_softmax_pick_rows", {x, "x"}, {ids, "ids"}, {out, "out"});
+    LRPX_REQUIRE(x && ids && out && rows > 0 && n > 0 && ld >= n, "softmax_pick_rows: bad arguments");
+    hipLaunchKernelGGL(softmax_pick_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, x, ld, n, ids, out);
+    return check_launch("softmax_pick_rows");
+}
+
+int lrpx_delete_topk_tokens(const long long* caps, int cap_ld, const float* r_words, int rw_ld, const int32_t* t, int rows, int kdel,
+                            long long* out, int out_ld, int32_t* out_len, int32_t* deleted, void* stream) {
+    LRPX_CHECK_PTRS_OPT("lrpx_delete_topk_tokens", {caps, "caps"}, {r_words, "r_words"}, {t, "t"}, {out, "out"}, {out_len, "out_len"},
+                        {deleted, "deleted"});
+    LRPX_REQUIRE(caps && r_words && t && out && out_len && rows > 0 && kdel >= 0 && kdel <= LRPX_DELETE_MAX && cap_ld >= 1 && rw_ld >= 1 &&
+                     out_ld >= 1, "delete_topk_tokens: bad arguments (at most %d deletions)", LRPX_DELETE_MAX);
+    hipLaunchKernelGGL(delete_topk_tokens_kernel, dim3(rows), dim3(64), 0, (hipStream_t)stream, caps, cap_ld, r_words, rw_ld, t, kdel, out,
+                       out_ld, out_len, deleted);
+    return check_launch("delete_topk_tokens");
 }
 
 int lrpx_target_logit(const float* hc, const float* fcw, const float* fcb, const long long* tok, int tok_ld,

@@ -52,6 +52,85 @@ def run_beam_search(step, logits, reorder, vocab, beam_size, max_cap_length, sta
     return seqs[0][:20]                                                    # :472 (the cut at 20 tokens is the reference's)
 
 
+BEAM_ROWS = 64      # rows per launch of a batched beam search: up to here `lrpx_linear_small` stays on the kernel `beam_search` runs
+
+
+def beam_search_batch(engine, enc, beam_size, max_cap_length, start_id, end_id, poll=None):
+    """`engine.beam_search` for every image of `enc` at once, on any caption engine (explainers/engine_base.py: its hooks `_decode_trace`,
+    `_decode_step`, `logits`, `_BEAM_STATE`): a list of enc["B"] token lists, each what `beam_search` returns for that image alone, token
+    for token.  Image i owns `beam_size` rows of the decoder trace; selection, sequence bookkeeping and the re-order of the LSTM state
+    are one launch per step (`lrpx_beam_step_batch`), and nothing is read back before the end.  More than `BEAM_ROWS` rows are split
+    into chunks of whole images (above 64 rows the skinny linear sums in another order).  `end_id`: one id, or one per image.  `poll`:
+    every `poll` steps the device's count of images with live beams is read, and the loop stops when it is 0; the result does not
+    depend on it.  A function, not an engine method: the engines' public surface is the recorded one (tests/test_explainer_api_host.py).
+    Not one of the static-buffer drivers (no HIP graph, no recording)."""
+    import numpy as np
+    N, nb, T = int(enc["B"]), int(beam_size), int(max_cap_length)
+    if not 1 <= nb <= 4:
+        raise ValueError("beam_search_batch: beam_size {} (lrpx_beam_step_batch keeps 1..4 beams)".format(nb))
+    ends = None
+    if not isinstance(end_id, (int, np.integer)):
+        ends = torch.as_tensor(end_id).to(engine.device, torch.int32).contiguous()
+        if ends.shape != (N,):
+            raise ValueError("beam_search_batch: end_id must be one id or one per image ({}), got shape {}".format(N, tuple(ends.shape)))
+    per = max(1, BEAM_ROWS // nb)
+    out = []
+    for i0 in range(0, N, per):
+        i1 = min(N, i0 + per)
+        sub = {k: (v[i0:i1] if torch.is_tensor(v) else v) for k, v in enc.items()}
+        sub["B"] = i1 - i0
+        out += _beam_chunk(engine, sub, nb, T, int(start_id), end_id if ends is None else ends[i0:i1].contiguous(), poll)
+    return out
+
+
+def _beam_chunk(engine, enc, nb, T, start_id, end_id, poll):
+    lib, dev, n = _lib.load(), engine.device, enc["B"]
+    rows = n * nb
+    encb = {k: (v.repeat_interleave(nb, 0).contiguous() if torch.is_tensor(v) else v) for k, v in enc.items()}
+    encb["B"] = rows
+    tr = engine._decode_trace(encb, rows, T)
+    toks = torch.full((rows, T + 1), start_id, dtype=torch.int64, device=dev)      # rows that are not live feed a valid id to the embedding
+    best = torch.zeros(n, T + 1, dtype=torch.int64, device=dev)
+    cum, best_score = torch.zeros(rows, device=dev), torch.zeros(n, device=dev)
+    n_live = torch.full((n,), nb, dtype=torch.int32, device=dev)
+    best_len = torch.zeros(n, dtype=torch.int32, device=dev)
+    live = torch.full((1,), n, dtype=torch.int32, device=dev)
+    st = _lib.BeamBatch()
+    st.N, st.k, st.V, st.T, st.start_id = n, nb, engine.V, T, start_id
+    if torch.is_tensor(end_id):
+        st.end_id, st.end_ids = -1, ptr(end_id)
+    else:
+        st.end_id, st.end_ids = int(end_id), None
+    st.toks, st.tok_ld, st.best, st.best_ld = ptr(toks), T + 1, ptr(best), T + 1
+    st.cum, st.best_score, st.n_live, st.best_len, st.live_images = ptr(cum), ptr(best_score), ptr(n_live), ptr(best_len), ptr(live)
+    state = [tr[k] for k in engine._BEAM_STATE]
+    st.n_state = len(state)
+    for j, s in enumerate(state):
+        assert s.shape[0] == rows and s.shape[1] == T + 1 and s.shape[2:] == state[0].shape[2:]
+        st.state[j] = ptr(s)
+    if state:
+        st.state_w = int(state[0][0, 0].numel())
+        st.state_ld = (T + 1) * st.state_w
+    steps = 0
+    for t in range(T):
+        engine._decode_step(tr, encb, t, toks)
+        lg = engine.logits(tr["hc"][:, t].contiguous())
+        check(lib.lrpx_beam_step_batch(_lib.C.byref(st), ptr(lg), lg.shape[1], t, stream_ptr()))
+        steps = t + 1
+        if poll and steps % int(poll) == 0 and steps < T and int(live.item()) == 0:
+            break
+    res = torch.empty(n, T + 2, dtype=torch.int64, device=dev)
+    check(lib.lrpx_beam_result_batch(_lib.C.byref(st), steps, ptr(res), T + 2, stream_ptr()))
+    host = res.cpu()                                   # the one device -> host read of the search
+    return [host[i, 1:1 + int(host[i, 0])].tolist() for i in range(n)]
+
+
+def caption_batch(engine, enc, word_map, beam_size, max_cap_length):
+    """the captions the explainers explain (`[<start>] + sen_idx`, models/gridTDmodel.py:474, :937) for every image of `enc`"""
+    seqs = beam_search_batch(engine, enc, beam_size, max_cap_length, word_map['<start>'], word_map['<end>'])
+    return [caption_from_sequence(s, word_map) for s in seqs]
+
+
 def caption_from_sequence(seq, word_map):
     """`sen_idx` (:474): the sequence without <start>, <end>, <unk>, <pad>; the explainers prepend <start> (:937)."""
     drop = {word_map[k] for k in ('<start>', '<end>', '<unk>', '<pad>') if k in word_map}
