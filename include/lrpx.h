@@ -1004,6 +1004,14 @@ int lrpx_max_abs_diff(const float* a, const float* b, long n, float* out_dev, vo
  * built on the host by lrp_amd.ops.pyramid_expand_matrix). */
 int lrpx_guided_gradcam(const float* guided, const float* cam, const float* expand_m, float* out, int rows, int p, int hw,
                         int channels, void* stream);
+/* Feature-resolution heat maps at image size (attention maps evaluation.py:198-211, :390-400, :483-494, :744-750; 2-D Grad-CAM maps
+ * :125-132, :401-407, :496-501): out_n = E_n = expand_m a_n expand_m^T, the factor lrpx_guided_gradcam multiplies by, bit for bit.
+ * maps: (rows, heads, p*p); a_n is head `head` (>= 0) or, head == -1, the mean over the heads (fp32 sum in head order, one division;
+ * heads == 1 copies).  normalize == 1: every map divided by its max |E| as lrpx_project_maxabs would (same bits; all-zero maps stay
+ * zero); out (rows, hw, hw) is written exactly once either way.  p in 2..32, hw a multiple of p, (hw * 4 * ceil(p / 4) + p*p + 16)
+ * floats of LDS at most 64 KiB; anything else, a bad head / heads and null pointers are LRPX_EINVAL before any launch. */
+int lrpx_expand_maps(const float* maps, const float* expand_m, float* out, int rows, int heads, int head, int p, int hw, int normalize,
+                     void* stream);
 
 /* ---- the VGG16 chains with a per-call context (see THREADING above): same arguments + opts (NULL = process defaults) -- */
 int lrpx_vgg16_forward_ex(const void* packed, const float* img_nchw, int n_img, void* trace, float* feat_nhwc,

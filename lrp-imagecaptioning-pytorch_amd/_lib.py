@@ -279,6 +279,7 @@ SIGNATURES = {
     "lrpx_softmax_pick_rows": (_i, [_f, _l, _i, _i, _f, _f, _f]),
     "lrpx_delete_topk_tokens": (_i, [_f, _i, _f, _i, _f, _i, _i, _f, _i, _f, _f, _f]),
     "lrpx_guided_gradcam": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _f]),
+    "lrpx_expand_maps": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _f]),
     "lrpx_linear_eps_rule": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _f]),
     "lrpx_batchnorm_rule": (_i, [_f, _f, _f, _f, _f, _f, C.c_float, _f, _l, _i, _l, _i, _f]),
     "lrpx_add_rule": (_i, [_f, _f, _f, _f, _f, _l, _f]),

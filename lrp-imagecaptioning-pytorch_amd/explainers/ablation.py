@@ -83,12 +83,45 @@ def delete_topk_tokens(engine, captions, t_rows, r_words, kdel=3):
     return short, lens, deleted[:, :int(kdel)]
 
 
-def word_ablation(engine, enc, row2img, captions, t_rows, r_words, kdel=3, model_bias=False):
+def delete_tokens(engine, captions, t_rows, delete_ids):
+    """evaluation.py:268-269 for R rows: `np.delete(captions[r, :t + 1], delete_ids[r])` with positions the caller drew (the random arm:
+    `random.sample(range(1, t), 3)`).  As np.delete: a position counts once however often it is named, negative positions count from
+    the end of the prefix, positions outside it are an IndexError.  Returns (short (R, max t + 2) int64, zeros behind a row's tokens,
+    lens (R,) int32).  Host index arithmetic on a few ids per row; the teacher-forced pass is the device work."""
+    t_host = [int(v) for v in torch.as_tensor(t_rows).tolist()]
+    R = len(t_host)
+    captions = _rows(engine, captions, R).to(torch.int64)
+    ids = torch.as_tensor(delete_ids).to(torch.int64).cpu()
+    if ids.dim() != 2 or ids.shape[0] != R:
+        raise ValueError("delete_tokens: delete_ids must be (rows, kdel) positions for {} rows, got {}".format(R, tuple(ids.shape)))
+    if R == 0 or min(t_host) < 0 or max(t_host) >= captions.shape[1]:
+        raise ValueError("delete_tokens: a row needs t + 1 caption tokens (t = {}, captions {})".format(t_host, tuple(captions.shape)))
+    cap_host = captions.cpu().tolist()
+    L = max(t_host) + 1
+    short = torch.zeros(R, L + 1, dtype=torch.int64)
+    lens = torch.empty(R, dtype=torch.int32)
+    for r, t in enumerate(t_host):
+        gone = set()
+        for d in ids[r].tolist():
+            if d < -(t + 1) or d > t:
+                raise IndexError("delete_tokens: position {} is out of bounds for the {} tokens of row {}".format(d, t + 1, r))
+            gone.add(d % (t + 1))
+        keep = [c for pos, c in enumerate(cap_host[r][:t + 1]) if pos not in gone]
+        if not keep:
+            raise ValueError("delete_tokens: row {} would be left without a token to teacher-force".format(r))
+        short[r, :len(keep)] = torch.tensor(keep, dtype=torch.int64)
+        lens[r] = len(keep)
+    return short.to(engine.device), lens.to(engine.device)
+
+
+def word_ablation(engine, enc, row2img, captions, t_rows, r_words, kdel=3, model_bias=False, delete_ids=None):
     """Row r explains word t = t_rows[r] of image row2img[r]: captions[r] holds its caption incl. <start> (at least t + 2 tokens),
     r_words[r, :t + 1] the relevance of the words before it.  The `kdel` most relevant of the words 1 .. t are deleted
     (`delete_topk_tokens`), the shortened prefix is teacher-forced on the image's own encoding `enc`, and the probability of
     captions[r, t + 1] at its last step is returned: new_prob (R,) (evaluation.py:236-253).  `model_bias` selects the explainer family's
-    `teacherforce_forward`, as `TF_MODEL_BIAS` does in explainers/dropin.py."""
+    `teacherforce_forward`, as `TF_MODEL_BIAS` does in explainers/dropin.py.
+    delete_ids (R, k): the positions to delete in place of the top-`kdel` relevant ones (`delete_tokens`; the random arm,
+    evaluation.py:265-287) - `r_words` and `kdel` are then not read."""
     dev = engine.device
     t_host = [int(v) for v in torch.as_tensor(t_rows).tolist()]
     R = len(t_host)
@@ -98,13 +131,18 @@ def word_ablation(engine, enc, row2img, captions, t_rows, r_words, kdel=3, model
     if max(t_host) + 1 >= captions.shape[1]:
         raise ValueError("word_ablation: a row needs t + 2 caption tokens (t up to {}, captions {})".format(max(t_host), tuple(captions.shape)))
     row2img = _rows(engine, row2img, R).to(torch.int64)
-    short, lens, _ = delete_topk_tokens(engine, captions, t_host, r_words, kdel)
+    if delete_ids is None:
+        short, lens, _ = delete_topk_tokens(engine, captions, t_host, r_words, kdel)
+    else:
+        short, lens = delete_tokens(engine, captions, t_host, delete_ids)
+    lens_host = lens.tolist() if delete_ids is not None else None
     targets = captions[torch.arange(R, device=dev), torch.tensor(t_host, dtype=torch.int64, device=dev) + 1]
     out = torch.empty(R, device=dev)
     for r0 in range(0, R, ROWS):
         r1 = min(R, r0 + ROWS)
         tmax = max(t_host[r0:r1])
-        Lc = tmax + 1 - min(int(kdel), tmax)          # the longest shortened prefix of the chunk
+        # the longest shortened prefix of the chunk
+        Lc = tmax + 1 - min(int(kdel), tmax) if lens_host is None else max(lens_host[r0:r1])
         out[r0:r1] = _teacherforce_last(engine, _enc_rows(enc, row2img[r0:r1]), short[r0:r1, :Lc + 1].contiguous(), lens[r0:r1],
                                         targets[r0:r1], model_bias)
     return out

@@ -391,6 +391,37 @@ def guided_gradcam(guided_maps, cam, p=14):
     return out
 
 
+def expand_maps(maps, hw, head=None, normalize=False, out=None):
+    """Feature-resolution heat maps at image size: maps (R, P) or (R, NH, P) with P = p*p -> (R, hw, hw), each map
+    `skimage.transform.pyramid_expand(a.reshape(p, p), upscale = hw / p)` - bit for bit the factor `guided_gradcam` multiplies by - and,
+    normalize=True, divided by its max |.| as `evaluation.project_maxabs` would (evaluation.py:198-211, :390-407, :483-501, :744-750).
+    head=None on (R, NH, P) is `np.mean(attention, axis=0)` (:202), head=k is `alphas[t][k]` (:744)."""
+    if maps.dim() not in (2, 3):
+        raise ValueError("expand_maps: maps must be (R, P) or (R, NH, P), got {}".format(tuple(maps.shape)))
+    if maps.dim() == 2 and head is not None:
+        raise ValueError("expand_maps: head selects among (R, NH, P) maps, got {}".format(tuple(maps.shape)))
+    rows, heads, pp = maps.shape[0], (1 if maps.dim() == 2 else maps.shape[1]), maps.shape[-1]
+    p = int(round(pp ** 0.5))
+    if p * p != pp:
+        raise ValueError("expand_maps: {} values per map are not a square grid".format(pp))        # the reference fails at `reshape`
+    hw = int(hw)
+    if hw <= 0 or hw % p:
+        raise ValueError("expand_maps: the image size {} is not a multiple of the grid size {}".format(hw, p))    # ... at `mask * image`
+    if head is not None and not 0 <= int(head) < heads:
+        raise ValueError("expand_maps: head {} of {}".format(head, heads))
+    _dev(maps)
+    if out is None:
+        out = torch.empty(rows, hw, hw, device=maps.device, dtype=torch.float32)
+    elif tuple(out.shape) != (rows, hw, hw) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != maps.device:
+        raise ValueError("expand_maps: out must be a contiguous float32 ({}, {}, {}) tensor on the maps' device".format(rows, hw, hw))
+    if rows == 0:
+        return out
+    m = pyramid_expand_matrix(p, hw // p, maps.device)
+    check(_lib.load().lrpx_expand_maps(ptr(maps.to(torch.float32).contiguous()), ptr(m), ptr(out), rows, heads,
+                                       -1 if head is None else int(head), p, hw, 1 if normalize else 0, stream_ptr()))
+    return out
+
+
 class Vgg16:
     """VGG16 encoder context: packed weights + per-batch trace (device memory owned by torch)."""
 

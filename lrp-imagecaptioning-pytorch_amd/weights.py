@@ -167,6 +167,22 @@ def make_aoa_state(seed=0, vocab_size=11027, embed_dim=512, hidden_dim=512, feat
     return sd
 
 
+def sharpen_attention(state, factor):
+    """A copy of `state` whose attention logits are `factor` times as large: `AdaAttention.w_h.weight` for gridTD / AdaAtt (the logits
+    are w_h tanh(.), no bias), `decoder_multihead_attention.q_proj.{weight,bias}` for AoA (the logits are q k / sqrt(dk)).  Random-init
+    attention is uniform to a few percent: the 20 largest of 784 patch sums of such a map are decided by rounding (gap between the 20th
+    and 21st 1e-4 .. 1e-6 of the largest); the experiments' attention arms are tested on sharpened states."""
+    keys = [k for k in ("AdaAttention.w_h.weight", "decoder_multihead_attention.q_proj.weight", "decoder_multihead_attention.q_proj.bias")
+            if k in state]
+    if not keys or (keys[0].startswith("AdaAttention") and len(keys) != 1) or (keys[0].startswith("decoder_") and len(keys) != 2):
+        raise ValueError("sharpen_attention: the state holds neither AdaAttention.w_h.weight (gridTD, AdaAtt) nor "
+                         "decoder_multihead_attention.q_proj.weight / .bias (AoA) alone")
+    out = OrderedDict(state)
+    for k in keys:
+        out[k] = (np.asarray(state[k], np.float32) * np.float32(factor)).astype(np.float32)
+    return out
+
+
 def make_word_map(vocab_size):
     """Synthetic word map with the reference's special-token layout (dataset/wordmap_*.json:
     <pad>=0, <unk>=V-3, <start>=V-2, <end>=V-1)."""
