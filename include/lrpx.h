@@ -596,6 +596,40 @@ typedef struct lrpx_beam_batch {
 } lrpx_beam_batch;
 int lrpx_beam_step_batch(const lrpx_beam_batch* p, const float* x, long ld, int t, void* stream);
 int lrpx_beam_result_batch(const lrpx_beam_batch* p, int steps, long long* out, int out_ld, void* stream);
+/* Diverse beam search (GridTDModel.diverse_beam_search, models/gridTDmodel.py:304-398; the other four model classes run the same
+ * algorithm on their own step) for N images at once, its state on the device.  Image i owns G k rows of the decoder trace: G = k = beam
+ * size <= 4 groups of k beams, group g the rows (i G + g) k .. + k - 1, live rows first.  One launch per decoder step, one workgroup per
+ * image, the groups in sequence inside it:
+ *   - a group without live beams is passed over (:340-341);
+ *   - scores cum[r] + ((x[r][w] - lse[r]) - diversity), the subtraction only for the columns w that are among the distinct INPUT words
+ *     of this step of groups 0 and 1, as far as these selected earlier in this step (:346-349, :377-380; at most 8 ids);
+ *   - selection and bookkeeping as lrpx_beam_step_batch (t = 0: row 0 alone with k candidates);
+ *   - a group whose last live beam completes ends the step for the groups after it (the `break`, :365-366): they keep sequences, scores
+ *     and input words, and their state tensors are carried from time t to time t + 1.
+ * So a group's sequences are not as long as the step count: seqs [N G k][seq_ld >= T + 1] int64 with seq_len [N G] (the caller fills
+ * column 0 with start_id and seq_len with 1), while toks [N G k][tok_ld >= T + 1] holds only the decoder's inputs (column t = the input
+ * of step t; the caller fills ALL of it with start_id).  cum [N G k] zeros, n_live [N G] = k, best [N G][best_ld >= T + 1] / best_len
+ * (zeros) / best_score [N G] per group as in lrpx_beam_batch, live_images one int = N (images with a live group).  When a group's last
+ * beam completes, its sequence row 0 becomes candidate 0 of that step, <end> included (what `seqs[g][0]` holds after :357).
+ * lrpx_dbs_result_batch: out[i G + g] = [length, tokens ...] (out_ld >= T + 2) - group g's best complete sequence, or, where it has
+ * none, the first 20 tokens of sequence row 0 of GROUP 0 (:389: `seqs[0][0][:20]`).
+ * T <= LRPX_BEAM_MAX_STEPS.  The first step (t = 0) validates every pointer, the later ones under LRPX_CHECK_PTRS=1. */
+typedef struct lrpx_dbs_batch {
+    int N, k, G, V, T;
+    int start_id, end_id;
+    float diversity;
+    const int32_t* end_ids;
+    long long* toks;
+    long long* seqs;
+    long long* best;
+    float *cum, *best_score;
+    int32_t *n_live, *seq_len, *best_len, *live_images;
+    float* state[4];
+    long state_ld;
+    int tok_ld, seq_ld, best_ld, state_w, n_state;
+} lrpx_dbs_batch;
+int lrpx_dbs_step_batch(const lrpx_dbs_batch* p, const float* x, long ld, int t, void* stream);
+int lrpx_dbs_result_batch(const lrpx_dbs_batch* p, long long* out, int out_ld, void* stream);
 /* out[r] = softmax(x[r,:n])[ids[r]] (evaluation.py:122, :149, :252: the score of one word); an id outside [0, n) gives NaN */
 int lrpx_softmax_pick_rows(const float* x, long ld, int rows, int n, const long long* ids, float* out, void* stream);
 /* word ablation (evaluation.py:242-247): row r is a caption prefix caps[r][0 .. t[r]] (column 0 = <start>) with the relevance of its

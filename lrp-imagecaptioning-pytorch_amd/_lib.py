@@ -65,6 +65,14 @@ class BeamBatch(C.Structure):
                 ("tok_ld", _i), ("best_ld", _i), ("state_w", _i), ("n_state", _i)]
 
 
+class DbsBatch(C.Structure):
+    """lrpx_dbs_batch: the device state of a batched diverse beam search (lrpx_dbs_step_batch)"""
+    _fields_ = [("N", _i), ("k", _i), ("G", _i), ("V", _i), ("T", _i), ("start_id", _i), ("end_id", _i), ("diversity", C.c_float),
+                ("end_ids", _f), ("toks", _f), ("seqs", _f), ("best", _f), ("cum", _f), ("best_score", _f), ("n_live", _f), ("seq_len", _f),
+                ("best_len", _f), ("live_images", _f), ("state", _f * 4), ("state_ld", _l), ("tok_ld", _i), ("seq_ld", _i), ("best_ld", _i),
+                ("state_w", _i), ("n_state", _i)]
+
+
 class AdaTrace(C.Structure):
     """lrpx_adaatt_trace"""
     _fields_ = [("B", _i), ("T", _i), ("H", _i), ("E", _i), ("P", _i)] + [(k, _f) for k in (
@@ -276,6 +284,8 @@ SIGNATURES = {
     "lrpx_beam_topk": (_i, [_f, _l, _i, _i, _f, _i, _f, _f, _f]),
     "lrpx_beam_step_batch": (_i, [C.POINTER(BeamBatch), _f, _l, _i, _f]),
     "lrpx_beam_result_batch": (_i, [C.POINTER(BeamBatch), _i, _f, _i, _f]),
+    "lrpx_dbs_step_batch": (_i, [C.POINTER(DbsBatch), _f, _l, _i, _f]),
+    "lrpx_dbs_result_batch": (_i, [C.POINTER(DbsBatch), _f, _i, _f]),
     "lrpx_softmax_pick_rows": (_i, [_f, _l, _i, _i, _f, _f, _f]),
     "lrpx_delete_topk_tokens": (_i, [_f, _i, _f, _i, _f, _i, _i, _f, _i, _f, _f, _f]),
     "lrpx_guided_gradcam": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _f]),

@@ -260,9 +260,26 @@ __global__ __launch_bounds__(256) void argmax_logprob_rows_kernel(const float* _
 // per image, the winners stay in registers for the bookkeeping) call the same body - the same sums in the same order.  Every thread
 // returns the k winners, best first: win_i[o] the flat index (BEAM_NONE where the range holds fewer than k scores), win_v[o] the score.
 constexpr int BEAM_NONE = 0x7fffffff;
-template <int KMAX>
+// What a selection does to log_softmax(x[r])[w] before the cumulative score is added.  `BeamPlain`: nothing - the beam search.
+// `BeamDiverse` (diverse beam search, models/gridTDmodel.py:346-349): `diversity` comes off the columns of at most 8 word ids (-1: unused).
+// Two types, so two instantiations of `beam_topk_block`: the plain one carries no trace of the other.
+struct BeamPlain {
+    __device__ __forceinline__ float operator()(float lp, int) const { return lp; }
+};
+struct BeamDiverse {
+    int id[8];
+    float diversity;
+    __device__ __forceinline__ float operator()(float lp, int w) const {
+        bool hit = false;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) hit |= w == id[q];
+        return hit ? lp - diversity : lp;
+    }
+};
+template <int KMAX, class ADJUST = BeamPlain>
 __device__ __forceinline__ void beam_topk_block(const float* __restrict__ x, long ld, int n_rows, int n,
-                                                const float* __restrict__ cum, int k, int (&win_i)[KMAX], float (&win_v)[KMAX]) {
+                                                const float* __restrict__ cum, int k, int (&win_i)[KMAX], float (&win_v)[KMAX],
+                                                const ADJUST& adjust = ADJUST()) {
     constexpr int NT = 1024, NW = NT / 64;
     __shared__ float red[NW];
     __shared__ float lse[8];
@@ -302,7 +319,7 @@ __device__ __forceinline__ void beam_topk_block(const float* __restrict__ x, lon
         const float off = (cum ? cum[r] : 0.f), l = lse[r];
         const float* xr = x + (long)r * ld;
         for (int w = tid; w < n; w += NT) {
-            float v = off + (xr[w] - l);
+            float v = off + adjust(xr[w] - l, w);
             int vi = r * n + w;
 #pragma unroll
             for (int j = 0; j < KMAX; ++j) {          // insertion into the sorted list (descending value, ascending index)
@@ -454,6 +471,134 @@ __global__ __launch_bounds__(256) void beam_result_batch_kernel(const lrpx_beam_
     const int len = bl > 0 ? bl : min(steps + 1, 20);
     const long long* from = bl > 0 ? p.best + (long)img * p.best_ld : p.toks + (long)img * p.k * p.tok_ld;
     long long* o = out + (long)img * out_ld;
+    if (threadIdx.x == 0) o[0] = len;
+    for (int c = threadIdx.x; c < len; c += 256) o[1 + c] = from[c];
+}
+
+// One step of the reference's diverse beam search (models/gridTDmodel.py:337-381) for N images, one workgroup per image (lrpx_dbs_batch,
+// include/lrpx.h).  The image's G groups run in sequence in the launch - group g + 1 needs the outcome of group g twice: the `break`
+// (:365-366: a group whose last beam completes ends the step for the later ones) and the penalty set (the distinct input words of groups
+// 0 and 1, :377-380).  The first is a register every thread computes alike, the second eight ids in LDS that thread 0 keeps.  A group's
+// selection is `beam_topk_block<BeamDiverse>` over its live rows; bookkeeping and the re-order are those of `beam_step_batch_kernel`, on
+// the group's own sequence buffer (a group that was passed over is shorter than the step count).  A passed-over group keeps everything;
+// its input word and its state move from time t to time t + 1, where the next decoder step reads them.
+template <int KMAX>
+__global__ __launch_bounds__(1024) void dbs_step_batch_kernel(const lrpx_dbs_batch p, const float* __restrict__ x, long ld, int t) {
+    constexpr int NT = 1024;
+    static_assert(KMAX == 4, "beam_pick takes four registers");
+    const int img = blockIdx.x, tid = threadIdx.x, k = p.k, G = p.G, V = p.V;
+    const int end = p.end_ids ? p.end_ids[img] : p.end_id;
+    __shared__ int pen_id[8];                             // the penalty set (-1: unused), kept by thread 0 between the groups
+    if (tid < 8) pen_id[tid] = -1;
+    __syncthreads();
+    int n_pen = 0, live_before = 0, live_after = 0;
+    bool broken = false;
+#pragma unroll 1
+    for (int g = 0; g < G; ++g) {
+        const int grp = img * G + g;
+        const long r0 = (long)grp * k;
+        const int nl = p.n_live[grp];
+        if (nl == 0) continue;                             // :340-341
+        ++live_before;
+        // a group that is passed over (`broken`) runs the tail below as the identity from time t: the same input words, the same state
+        const bool sel = !broken;
+        const int sl = p.seq_len[grp];
+        int src[KMAX], word[KMAX];
+        float sc[KMAX];
+#pragma unroll
+        for (int j = 0; j < KMAX; ++j) { src[j] = j; word[j] = p.start_id; sc[j] = 0.f; }
+        int nn = k, ns = 0, done_src = -1;
+        float best_score = 0.f;
+        if (sel) {
+            bool has = p.best_len[grp] > 0;
+            best_score = p.best_score[grp];
+            const int kc = t == 0 ? k : nl;
+            int wi[KMAX];
+            float wv[KMAX];
+            BeamDiverse pen;                               // (read from LDS: eight vector registers, the scalar file is full)
+#pragma unroll
+            for (int q = 0; q < 8; ++q) pen.id[q] = pen_id[q];
+            pen.diversity = p.diversity;
+            beam_topk_block<KMAX, BeamDiverse>(x + r0 * ld, ld, t == 0 ? 1 : nl, V, p.cum + r0, kc, wi, wv, pen);
+            nn = 0;
+#pragma unroll
+            for (int o = 0; o < KMAX; ++o) {
+                const int flat = wi[o] != BEAM_NONE ? wi[o] : 0;
+                const int b = flat / V, w = flat - b * V;
+                if (o >= kc) {
+                } else if (w == end) {
+                    if (!has || wv[o] > best_score) { has = true; best_score = wv[o]; done_src = b; }
+                } else {
+#pragma unroll
+                    for (int j = 0; j < KMAX; ++j) if (j == nn) { src[j] = b; word[j] = w; sc[j] = wv[o]; }
+                    ++nn;
+                }
+            }
+            // the last beam completed: `seqs[g]` stays what :357 made it - row 0 is candidate 0 with its <end> (the fallback reads it, :389)
+            ns = nn > 0 ? nn : 1;
+            if (nn == 0) { const int flat = wi[0] != BEAM_NONE ? wi[0] : 0; src[0] = flat / V; word[0] = flat - src[0] * V; }
+            if (g < 2 && nn > 0 && tid == 0) {             // :377-380: the distinct input words of this group join the penalty set
+                for (int j = 0; j < nl; ++j) {
+                    const int w = (int)p.toks[(r0 + j) * p.tok_ld + t];
+                    bool known = false;
+                    for (int q = 0; q < n_pen; ++q) known |= pen_id[q] == w;
+                    if (!known) pen_id[n_pen++] = w;       // at most 2 groups x 4 live rows
+                }
+            }
+        }
+        __syncthreads();                                   // (every thread has read cum, n_live, seq_len, the kept score and the set)
+        if (const int c = tid; c < sl && sel) {           // one thread per sequence position: sl <= t + 1 <= LRPX_BEAM_MAX_STEPS = NT
+            long long v[KMAX];
+#pragma unroll
+            for (int j = 0; j < KMAX; ++j) v[j] = j < k ? p.seqs[(r0 + j) * p.seq_ld + c] : 0;
+            if (done_src >= 0) p.best[(long)grp * p.best_ld + c] = beam_pick(v[0], v[1], v[2], v[3], done_src);
+#pragma unroll
+            for (int j = 0; j < KMAX; ++j) if (j < ns) p.seqs[(r0 + j) * p.seq_ld + c] = beam_pick(v[0], v[1], v[2], v[3], src[j]);
+        }
+        const long from = (long)(sel ? t + 1 : t) * p.state_w, to = (long)(t + 1) * p.state_w;
+#pragma unroll 1
+        for (int s = 0; s < p.n_state; ++s) {
+            float* st = p.state[s];
+            for (int c = tid; c < p.state_w; c += NT) {
+                float v[KMAX];
+#pragma unroll
+                for (int j = 0; j < KMAX; ++j) v[j] = j < k ? st[(r0 + j) * p.state_ld + from + c] : 0.f;
+#pragma unroll
+                for (int j = 0; j < KMAX; ++j) if (j < nn) st[(r0 + j) * p.state_ld + to + c] = beam_pick(v[0], v[1], v[2], v[3], src[j]);
+            }
+        }
+        if (tid == 0) {
+#pragma unroll
+            for (int j = 0; j < KMAX; ++j)
+                if (j < k) {
+                    long long* tk = p.toks + (r0 + j) * p.tok_ld + t;
+                    tk[1] = !sel ? tk[0] : j < nn ? word[j] : p.start_id;                 // rows that are not live carry a valid id
+                    if (j < ns) p.seqs[(r0 + j) * p.seq_ld + sl] = word[j];
+                    if (sel && j < nn) p.cum[r0 + j] = sc[j];
+                }
+            if (sel) {
+                p.n_live[grp] = nn;
+                p.seq_len[grp] = sl + 1;
+            }
+            if (done_src >= 0) {
+                p.best[(long)grp * p.best_ld + sl] = end;
+                p.best_len[grp] = sl + 1;
+                p.best_score[grp] = best_score;
+            }
+        }
+        if (nn > 0) ++live_after; else broken = true;
+    }
+    if (tid == 0 && live_before > 0 && live_after == 0) atomicSub(p.live_images, 1);
+}
+
+// the result of a batched diverse beam search: out[i G + g] = [length, tokens ...] - the group's kept complete sequence, or sequence row
+// 0 of the image's GROUP 0 cut to 20 tokens (:389)
+__global__ __launch_bounds__(256) void dbs_result_batch_kernel(const lrpx_dbs_batch p, long long* __restrict__ out, int out_ld) {
+    const int grp = blockIdx.x, g0 = grp / p.G * p.G;
+    const int bl = p.best_len[grp];
+    const int len = bl > 0 ? bl : min(p.seq_len[g0], 20);
+    const long long* from = bl > 0 ? p.best + (long)grp * p.best_ld : p.seqs + (long)g0 * p.k * p.seq_ld;
+    long long* o = out + (long)grp * out_ld;
     if (threadIdx.x == 0) o[0] = len;
     for (int c = threadIdx.x; c < len; c += 256) o[1 + c] = from[c];
 }
@@ -693,6 +838,52 @@ int lrpx_beam_result_batch(const lrpx_beam_batch* p, int steps, long long* out, 
                  "beam_result_batch: bad arguments (out rows hold the length and T + 1 tokens)");
     hipLaunchKernelGGL(beam_result_batch_kernel, dim3(p->N), dim3(256), 0, (hipStream_t)stream, *p, steps, out, out_ld);
     return check_launch("beam_result_batch");
+}
+
+// the shape of a diverse beam search's state: G = k groups of k beams, at most 16 rows per image, one thread per sequence position
+static int dbs_check_shape(const lrpx_dbs_batch* p, const char* who) {
+    LRPX_REQUIRE(p, "%s: null state", who);
+    LRPX_REQUIRE(p->k >= 1 && p->k <= 4 && p->G == p->k && p->N >= 1 && p->V >= 1 && (long)p->k * p->V < 0x7fffffffL &&
+                     (long)p->N * p->G * p->k < 0x7fffffffL,
+                 "%s: bad arguments (beam size 1..4, as many groups as beams, N >= 1, V >= 1; got k = %d, G = %d, N = %d, V = %d)", who,
+                 p->k, p->G, p->N, p->V);
+    LRPX_REQUIRE(p->T >= 1 && p->T <= LRPX_BEAM_MAX_STEPS, "%s: max_cap_length %d outside 1..%d (one thread per sequence position)", who,
+                 p->T, LRPX_BEAM_MAX_STEPS);
+    LRPX_REQUIRE(p->tok_ld > p->T && p->seq_ld > p->T && p->best_ld > p->T, "%s: a row stride shorter than T + 1 = %d", who, p->T + 1);
+    LRPX_REQUIRE(p->toks && p->seqs && p->cum && p->n_live && p->seq_len && p->best && p->best_len && p->best_score && p->live_images,
+                 "%s: null pointer", who);
+    return LRPX_OK;
+}
+
+int lrpx_dbs_step_batch(const lrpx_dbs_batch* p, const float* x, long ld, int t, void* stream) {
+    if (const int rc = dbs_check_shape(p, "dbs_step_batch")) return rc;
+    LRPX_REQUIRE(x && t >= 0 && t < p->T && ld >= p->V, "dbs_step_batch: null scores, step %d of %d, or a row stride shorter than V", t, p->T);
+    LRPX_REQUIRE(p->diversity == p->diversity, "dbs_step_batch: diversity is NaN");
+    LRPX_REQUIRE(p->n_state >= 0 && p->n_state <= 4 && (p->n_state == 0 || (p->state_w >= 1 && p->state_ld >= (long)(p->T + 1) * p->state_w)),
+                 "dbs_step_batch: at most 4 state tensors (rows, T + 1, width)");
+    for (int s = 0; s < p->n_state; ++s) LRPX_REQUIRE(p->state[s], "dbs_step_batch: null state tensor %d", s);
+#define LRPX_DBS_PTRS {x, "x"}, {p->end_ids, "end_ids"}, {p->toks, "toks"}, {p->seqs, "seqs"}, {p->cum, "cum"}, {p->n_live, "n_live"},          \
+                      {p->seq_len, "seq_len"}, {p->best, "best"}, {p->best_len, "best_len"}, {p->best_score, "best_score"},                     \
+                      {p->live_images, "live_images"}, {p->n_state > 0 ? p->state[0] : nullptr, "state[0]"},                                    \
+                      {p->n_state > 1 ? p->state[1] : nullptr, "state[1]"}, {p->n_state > 2 ? p->state[2] : nullptr, "state[2]"},               \
+                      {p->n_state > 3 ? p->state[3] : nullptr, "state[3]"}
+    if (t == 0) {      // the first step of a search looks at every pointer; the later ones only under LRPX_CHECK_PTRS=1, like their neighbours
+        LRPX_CHECK_PTRS("lrpx_dbs_step_batch", LRPX_DBS_PTRS);
+    } else {
+        LRPX_CHECK_PTRS_OPT("lrpx_dbs_step_batch", LRPX_DBS_PTRS);
+    }
+#undef LRPX_DBS_PTRS
+    hipLaunchKernelGGL((dbs_step_batch_kernel<4>), dim3(p->N), dim3(1024), 0, (hipStream_t)stream, *p, x, ld, t);
+    return check_launch("dbs_step_batch");
+}
+
+int lrpx_dbs_result_batch(const lrpx_dbs_batch* p, long long* out, int out_ld, void* stream) {
+    if (const int rc = dbs_check_shape(p, "dbs_result_batch")) return rc;
+    LRPX_REQUIRE(out && out_ld >= p->T + 2, "dbs_result_batch: out rows hold the length and T + 1 tokens");
+    LRPX_CHECK_PTRS("lrpx_dbs_result_batch", {out, "out"}, {p->seqs, "seqs"}, {p->seq_len, "seq_len"}, {p->best, "best"},
+                    {p->best_len, "best_len"});
+    hipLaunchKernelGGL(dbs_result_batch_kernel, dim3(p->N * p->G), dim3(256), 0, (hipStream_t)stream, *p, out, out_ld);
+    return check_launch("dbs_result_batch");
 }
 
 int lrpx_softmax_pick_rows(const float* x, long ld, int rows, int n, const long long* ids, float* out, void* stream) {

@@ -64,15 +64,10 @@ def beam_search_batch(engine, enc, beam_size, max_cap_length, start_id, end_id, 
     every `poll` steps the device's count of images with live beams is read, and the loop stops when it is 0; the result does not
     depend on it.  A function, not an engine method: the engines' public surface is the recorded one (tests/test_explainer_api_host.py).
     Not one of the static-buffer drivers (no HIP graph, no recording)."""
-    import numpy as np
     N, nb, T = int(enc["B"]), int(beam_size), int(max_cap_length)
     if not 1 <= nb <= 4:
         raise ValueError("beam_search_batch: beam_size {} (lrpx_beam_step_batch keeps 1..4 beams)".format(nb))
-    ends = None
-    if not isinstance(end_id, (int, np.integer)):
-        ends = torch.as_tensor(end_id).to(engine.device, torch.int32).contiguous()
-        if ends.shape != (N,):
-            raise ValueError("beam_search_batch: end_id must be one id or one per image ({}), got shape {}".format(N, tuple(ends.shape)))
+    ends = _end_ids("beam_search_batch", end_id, N, engine.device)
     per = max(1, BEAM_ROWS // nb)
     out = []
     for i0 in range(0, N, per):
@@ -123,6 +118,94 @@ def _beam_chunk(engine, enc, nb, T, start_id, end_id, poll):
     check(lib.lrpx_beam_result_batch(_lib.C.byref(st), steps, ptr(res), T + 2, stream_ptr()))
     host = res.cpu()                                   # the one device -> host read of the search
     return [host[i, 1:1 + int(host[i, 0])].tolist() for i in range(n)]
+
+
+def _end_ids(who, end_id, N, device):
+    import numpy as np
+    if isinstance(end_id, (int, np.integer)):
+        return None
+    ends = torch.as_tensor(end_id).to(device, torch.int32).contiguous()
+    if ends.shape != (N,):
+        raise ValueError("{}: end_id must be one id or one per image ({}), got shape {}".format(who, N, tuple(ends.shape)))
+    return ends
+
+
+def diverse_beam_search_batch(engine, enc, beam_size, max_cap_length, start_id, end_id, diversity_prob=0.5, poll=None):
+    """The reference's `diverse_beam_search` (models/gridTDmodel.py:304-398, and the same loop in the other four model classes) for every
+    image of `enc` at once, on any caption engine (the hooks of `beam_search_batch`): a list of enc["B"] lists of G = `beam_size` token
+    lists - the reference's `seq` of each group, incl. <start> (and <end> where the group completed a sequence).  The reference takes one
+    image and walks its groups in Python; here image i owns G * beam_size rows of the decoder trace, the groups of every image select in
+    ONE launch per step (`lrpx_dbs_step_batch`, include/lrpx.h: the penalty of `diversity_prob` on the input words of groups 0 and 1,
+    the `break` that passes the later groups over, the fallback to group 0's first sequence), and nothing is read back before the end.
+    Chunks are whole images of at most `BEAM_ROWS` rows: 16 images at beam 2, 7 at beam 3, 4 at beam 4.  `end_id`: one id, or one per
+    image.  `poll`: as in `beam_search_batch`; the result does not depend on it."""
+    N, nb, T = int(enc["B"]), int(beam_size), int(max_cap_length)
+    if not 1 <= nb <= 4:
+        raise ValueError("diverse_beam_search_batch: beam_size {} (lrpx_dbs_step_batch keeps 1..4 groups of as many beams)".format(nb))
+    ends = _end_ids("diverse_beam_search_batch", end_id, N, engine.device)
+    per = max(1, BEAM_ROWS // (nb * nb))
+    out = []
+    for i0 in range(0, N, per):
+        i1 = min(N, i0 + per)
+        sub = {k: (v[i0:i1] if torch.is_tensor(v) else v) for k, v in enc.items()}
+        sub["B"] = i1 - i0
+        out += _dbs_chunk(engine, sub, nb, T, int(start_id), end_id if ends is None else ends[i0:i1].contiguous(), float(diversity_prob), poll)
+    return out
+
+
+def _dbs_chunk(engine, enc, nb, T, start_id, end_id, diversity, poll):
+    lib, dev, n = _lib.load(), engine.device, enc["B"]
+    groups, rows = n * nb, n * nb * nb
+    encb = {k: (v.repeat_interleave(nb * nb, 0).contiguous() if torch.is_tensor(v) else v) for k, v in enc.items()}
+    encb["B"] = rows
+    tr = engine._decode_trace(encb, rows, T)
+    toks = torch.full((rows, T + 1), start_id, dtype=torch.int64, device=dev)      # the decoder's inputs; rows that are not live feed <start>
+    seqs = torch.full((rows, T + 1), start_id, dtype=torch.int64, device=dev)      # the sequences: a group that was passed over is shorter
+    best = torch.zeros(groups, T + 1, dtype=torch.int64, device=dev)
+    cum, best_score = torch.zeros(rows, device=dev), torch.zeros(groups, device=dev)
+    n_live = torch.full((groups,), nb, dtype=torch.int32, device=dev)
+    seq_len = torch.ones(groups, dtype=torch.int32, device=dev)
+    best_len = torch.zeros(groups, dtype=torch.int32, device=dev)
+    live = torch.full((1,), n, dtype=torch.int32, device=dev)
+    st = _lib.DbsBatch()
+    st.N, st.k, st.G, st.V, st.T, st.start_id, st.diversity = n, nb, nb, engine.V, T, start_id, diversity
+    if torch.is_tensor(end_id):
+        st.end_id, st.end_ids = -1, ptr(end_id)
+    else:
+        st.end_id, st.end_ids = int(end_id), None
+    st.toks, st.tok_ld, st.seqs, st.seq_ld, st.best, st.best_ld = ptr(toks), T + 1, ptr(seqs), T + 1, ptr(best), T + 1
+    st.cum, st.best_score, st.n_live, st.seq_len = ptr(cum), ptr(best_score), ptr(n_live), ptr(seq_len)
+    st.best_len, st.live_images = ptr(best_len), ptr(live)
+    state = [tr[k] for k in engine._BEAM_STATE]
+    st.n_state = len(state)
+    for j, s in enumerate(state):
+        assert s.shape[0] == rows and s.shape[1] == T + 1 and s.shape[2:] == state[0].shape[2:]
+        st.state[j] = ptr(s)
+    if state:
+        st.state_w = int(state[0][0, 0].numel())
+        st.state_ld = (T + 1) * st.state_w
+    for t in range(T):
+        engine._decode_step(tr, encb, t, toks)
+        lg = engine.logits(tr["hc"][:, t].contiguous())
+        check(lib.lrpx_dbs_step_batch(_lib.C.byref(st), ptr(lg), lg.shape[1], t, stream_ptr()))
+        if poll and (t + 1) % int(poll) == 0 and t + 1 < T and int(live.item()) == 0:
+            break
+    res = torch.empty(groups, T + 2, dtype=torch.int64, device=dev)
+    check(lib.lrpx_dbs_result_batch(_lib.C.byref(st), ptr(res), T + 2, stream_ptr()))
+    host = res.cpu()                                   # the one device -> host read of the search
+    return [[host[i * nb + g, 1:1 + int(host[i * nb + g, 0])].tolist() for g in range(nb)] for i in range(n)]
+
+
+def diverse_captions_batch(engine, enc, word_map, beam_size, max_cap_length, diversity_prob=0.5, bad_ending_ids=None):
+    """the G captions per image `diverse_beam_search` returns, as ids: `[<start>] + sen_idx` per group (:391-392), with
+    `remove_bad_endings` (:284-302, :396) at id level where `bad_ending_ids` is given - ready for `explain_batch(..., lens=)`"""
+    from .ablation import trim_bad_endings
+    seqs = diverse_beam_search_batch(engine, enc, beam_size, max_cap_length, word_map['<start>'], word_map['<end>'], diversity_prob)
+    caps = [[caption_from_sequence(s, word_map) for s in groups] for groups in seqs]
+    if bad_ending_ids is not None:
+        bad = list(bad_ending_ids)                     # (trim_bad_endings makes the set)
+        caps = [[c[:1] + trim_bad_endings(c[1:], bad) for c in groups] for groups in caps]
+    return caps
 
 
 def caption_batch(engine, enc, word_map, beam_size, max_cap_length):

@@ -183,6 +183,15 @@ def sharpen_attention(state, factor):
     return out
 
 
+def scale_fc(state, factor):
+    """A copy of `state` whose word scores depend `factor` times as strongly on the decoder's state (`fc.weight`; `fc.bias`, which
+    favours the same words at every step, stays).  Random-init scores are flat: the candidates of a beam search then lie 1e-5 apart.
+    The diverse-beam-search goldens are drawn on scaled states, where selections rest on a gap a test can stand on."""
+    out = OrderedDict(state)
+    out["fc.weight"] = (np.asarray(state["fc.weight"], np.float32) * np.float32(factor)).astype(np.float32)
+    return out
+
+
 def make_word_map(vocab_size):
     """Synthetic word map with the reference's special-token layout (dataset/wordmap_*.json:
     <pad>=0, <unk>=V-3, <start>=V-2, <end>=V-1)."""
