@@ -1106,8 +1106,25 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
     // B6: three planes per entry (12 registers)
     // (measured, same-box A/B of builds: the map-aligned pooled-input kernels have the registers for a deeper queue - their staging items
     // are a quarter as many - conv1_2 5.16 -> 5.04 ms, conv2_2 4.41 -> 4.25; one entry more spills in every other instantiation)
-    constexpr int NBQ_B6 = (POOL && AL) ? (HW == 112 ? 7 : 6) : ((HW <= 56) ? 5 : 4);
+    constexpr int NBQ_B6 = (POOL && AL) ? (HW == 112 ? 7 : 6) : ((HW <= 56) ? 5 : 4);       // (compiled for conv1_2's tile only: RING below)
     constexpr int NBQ = B6 ? NBQ_B6 : NBQ_H3;
+    // B6 keeps its weight fragments in a RING whose entry is a compile-time function of the tap alone, so that no register copy and
+    // no unrolling of the K-chunk loop is needed: the loads of step t + BQD are issued behind the first accumulator tile of step t
+    // into the entry RSLOT(t + BQD).  A ring of period 9 (the taps of a chunk) in which any BQD + 1 consecutive steps own distinct
+    // entries exists with 3 entries for BQD = 2 (0 1 2 0 1 2 0 1 2) and with 5 for BQD = 3 (0 1 2 3 0 1 2 3 4); deeper ones need 9
+    // entries (108 registers).  The shift queue above was compiled into something else than it says: nothing pins its loads, and the
+    // scheduler sank most of them to their uses - load, vmcnt(1 / 0), MFMA on that register, four times per chunk in every
+    // instantiation (profiles/bq_ring_isa.txt).  One tap is 42 MFMAs of 8 passes, 1344 cycles of the matrix pipe: two taps ahead
+    // cover an L2 round trip and more.
+    //   depth     rows                                  measured (same box, parent's library alternating with this one, 5 times: profiles/bq_ring_ab.txt)
+    //   BQD = 2   every B6 row but the two below        conv2_1 - 4 %, conv2_2 - 6 %, conv3_3 - 4 %, conv4_3 - 6 %, forward trace 5.32 - 5.34 -> 5.12 - 5.15 ms;
+    //                                                   BQD = 3 the same within the spread at 12 - 18 registers more
+    //   shift     b6_224_pool, b6_224_pool_guided       ring 4.93 - 5.01 ms against 4.98 - 5.16: overlapping, so the tile keeps the parent's code
+    constexpr int BQD = 2;
+    constexpr bool RING = B6 && !(HW == 224 && POOL);
+    constexpr int NRING = !RING ? 1 : (BQD == 2 ? 3 : 5);
+    static_assert(BQD == 2 || BQD == 3, "conv_f16x3 (B6): a ring of period 9 exists for 2 or 3 steps ahead only");
+#define LRPXH_RSLOT(T) (BQD == 2 ? ((T) % TAPS) % 3 : (((T) % TAPS) < 8 ? ((T) % TAPS) % 4 : 4))
     float inv_w = 1.f;
     if constexpr (!B6) inv_w = a.wp[0];
     // F8: one queue entry per tap ROW g = 7 planes of 64 lanes x 16 B: fp16 hi of dx = 0,1,2 | the B operands of fp6
@@ -1116,7 +1133,7 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
     constexpr int BSTEPS = F8 ? 3 : TAPS;           // queue entries per K-chunk
     // measured (tools/variant_sweep3.sh, chain of 320 maps): 2 entries 24.1 ms, 3 entries 25.1 (spills), 4: 30.1; with fp6
     // staging items of 16 floats a third entry spills everywhere
-    constexpr int NQ = F8 ? 2 : NBQ;
+    constexpr int NQ = F8 ? 2 : (RING ? 1 : NBQ);
     // (a wave without a channel block of its own - n_oc not a multiple of the workgroup's channels - multiplies the last
     // valid block again and drops the result: one code path, see PRECISE below)
     const int ocb_w = wave_active ? ocb : (a.n_oc - 1) / 32;
@@ -1142,6 +1159,22 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
     for (int i = 0; i < NQ - 1; ++i)
 #pragma unroll
         for (int p = 0; p < BP; ++p) bq[i][p] = ldb(min(i, last_step), p);
+    // B6: raw buffer loads through one resource over the wave's packed block [K-chunk][tap][plane][64 lanes][16 B] (its K-split range):
+    // the lane's 16 B and the plane in the one address register + immediate, the step in the scalar offset - a load is one
+    // instruction that the compiler can count and, between two scheduling barriers, cannot move.  The launcher checks that a
+    // block stays within the 32-bit offsets.  Every offset is that of a step <= last_step: inside the block.
+    u32x4_ rq[NRING][3];
+    const unsigned rlane = (unsigned)lane * 16u;
+    const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(a.wp) + ((long)ocb_w * nchunk_all + c_begin) * (long)(TAPS * 3 * 64 * 4), 0,
+        RING ? nchunk * (TAPS * 3 * 1024) : 0, 0x00020000);
+#define LRPXH_RLOAD(SLOT, STEP)                                                                                      \
+    _Pragma("unroll") for (int p_ = 0; p_ < 3; ++p_)                                                                 \
+        rq[SLOT][p_] = __builtin_bit_cast(u32x4_, __builtin_amdgcn_raw_buffer_load_b128(rrsrc, rlane + p_ * 1024u, (STEP) * 3072, 0));
+    if constexpr (RING) {
+#pragma unroll
+        for (int i = 0; i < BQD; ++i) LRPXH_RLOAD(LRPXH_RSLOT(i), min(i, last_step))
+    }
     // F8: the operand of fp6 MFMA mm = 0..4 is the 32 bytes at byte 32 of ONE pixel per lane: tap 2mm for lanes 0-31, tap 2mm + 1
     // for lanes 32-63 (mm = 4: tap 8 again, against zero weights) - the lane halves differ by one pixel (mm = 0, 2, 3), by a row
     // less two pixels (mm = 1) or not at all (mm = 4); abase[] carries + 16 for lanes 32-63
@@ -1294,13 +1327,15 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
             __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
 #pragma unroll
             for (int tap = 0; tap < TAPS; ++tap) {
-                const long nxt = (long)min(chunk * TAPS + tap + NBQ - 1, last_step) * 3;
+                if constexpr (!RING) {
+                    const long nxt = (long)min(chunk * TAPS + tap + NBQ - 1, last_step) * 3;
 #pragma unroll
-                for (int p = 0; p < 3; ++p) bq[NBQ - 1][p] = wp[(nxt + p) * 64];
-                if (tap == 0 && ISSUE_LATE) { __builtin_amdgcn_sched_barrier(0); LRPXH_ISSUE_NEXT }
-                const bf16x8 b0 = __builtin_bit_cast(bf16x8, bq[0][0]);
-                const bf16x8 b1 = __builtin_bit_cast(bf16x8, bq[0][1]);
-                const bf16x8 b2 = __builtin_bit_cast(bf16x8, bq[0][2]);
+                    for (int p = 0; p < 3; ++p) bq[NBQ - 1][p] = wp[(nxt + p) * 64];
+                    if (tap == 0 && ISSUE_LATE) { __builtin_amdgcn_sched_barrier(0); LRPXH_ISSUE_NEXT }
+                }
+                const bf16x8 b0 = __builtin_bit_cast(bf16x8, RING ? rq[LRPXH_RSLOT(tap)][0] : bq[0][0]);
+                const bf16x8 b1 = __builtin_bit_cast(bf16x8, RING ? rq[LRPXH_RSLOT(tap)][1] : bq[0][1]);
+                const bf16x8 b2 = __builtin_bit_cast(bf16x8, RING ? rq[LRPXH_RSLOT(tap)][2] : bq[0][2]);
 #pragma unroll
                 for (int j = 0; j < 7; ++j) {
                     const bf16x8 a0 = n0, a1 = n1, a2 = n2;
@@ -1319,11 +1354,23 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc[j], 0, 0, 0);
                     __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);   // the 3 reads of the NEXT tile ...
                     __builtin_amdgcn_sched_group_barrier(0x008, 6, 0);   // ... then the 6 MFMAs of this one
+                    if (RING && j == 0) {
+                        // the fragments of step t + BQD, behind the first tile of step t and fenced there: the wait in front of
+                        // step t + 1 then leaves them (and with BQD = 3 those of step t + 2) in flight.  Past the block's last
+                        // step the last one is read again (nobody uses it): no branch around a load.
+                        __builtin_amdgcn_sched_barrier(0);
+                        const int st = chunk * TAPS + tap + BQD;
+                        LRPXH_RLOAD(LRPXH_RSLOT(tap + BQD), (tap + BQD >= TAPS ? min(st, last_step) : st))
+                        if (tap == 0 && ISSUE_LATE) { __builtin_amdgcn_sched_barrier(0); LRPXH_ISSUE_NEXT }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
                 }
+                if constexpr (!RING) {
 #pragma unroll
-                for (int i = 0; i < NBQ - 1; ++i)
+                    for (int i = 0; i < NBQ - 1; ++i)
 #pragma unroll
-                    for (int p = 0; p < 3; ++p) bq[i][p] = bq[i + 1][p];
+                        for (int p = 0; p < 3; ++p) bq[i][p] = bq[i + 1][p];
+                }
             }
             } else {
             constexpr int AD = 1;     // A fragments read this many accumulator tiles ahead of their MFMAs (forward trace, mode 2)
@@ -1400,6 +1447,8 @@ __global__ __launch_bounds__(64 * MT * NWN, (MT * NWN >= 8) ? 1 : 2) void conv_f
         }
     }
 #undef LRPXH_ISSUE_NEXT
+#undef LRPXH_RLOAD
+#undef LRPXH_RSLOT
 #undef LRPXH_REFRESH
 #undef LRPXH_ISSUE
 #undef LRPXH_COMMIT
@@ -1660,6 +1709,14 @@ int launch_conv_f16x3(const ConvArgs& a, hipStream_t stream) {
     if (HW % CC::R == 0 && a.tile_group > 1) {       // grouped order: every XCD walks whole (image, row block) groups
         const long n_groups = (long)(a.n_maps / a.tile_group) * (HW / CC::R);
         grid = ceil_div(n_groups, 8) * 8 * a.tile_group * n_blocks;
+    }
+    if constexpr (B6) {
+        // the kernel's 32-bit buffer offsets: a channel block of the packed weights, [K-chunk][tap][3 planes][64 lanes][16 B]
+        const long wbytes = (long)(a.cin / 16) * 9 * 3 * 1024;
+        if (wbytes > 0x7fffffffL) {
+            set_error("conv_f16x3 (bf16x6): %ld B of packed weights per channel block are beyond the kernel's 32-bit offsets", wbytes);
+            return LRPX_EINVAL;
+        }
     }
     auto kern = conv_f16x3_kernel<HW, MT, NWN, DB, EPI, POOL, F8, B6>;
     static LdsOnce attr_once;
