@@ -100,16 +100,11 @@ static int initial_fwd_f16() {
 static std::atomic<int> g_default_fwd_f16{initial_fwd_f16()};
 
 // what one call runs with: resolved once at entry from its opts (or the process defaults)
-struct VggCtx {
-    int mode, fwd_f16;
-    float* layer_ms;      // host [17]: per-layer HIP-event times of THIS call (events live and die inside the call)
-    bool bf16x6() const { return mode >= 1; }
-};
+struct VggCtx { int mode, fwd_f16; };
 static VggCtx resolve_ctx(const lrpx_vgg16_opts* o) {
     VggCtx c;
     c.mode = (o && o->conv_mode >= 0) ? (o->conv_mode > 3 ? 3 : o->conv_mode) : g_default_mode.load(std::memory_order_relaxed);
     c.fwd_f16 = (o && o->forward_f16 >= 0) ? (o->forward_f16 ? 1 : 0) : g_default_fwd_f16.load(std::memory_order_relaxed);
-    c.layer_ms = o ? o->layer_ms : nullptr;
     return c;
 }
 
@@ -118,56 +113,123 @@ static VggCtx resolve_ctx(const lrpx_vgg16_opts* o) {
 static thread_local int tl_timing = 0;
 static thread_local float tl_ms[17];
 
-struct VggPacked {   // offsets in floats into the packed blob
-    size_t fwd[17], bwd[17], bwdp[17], bwd6[17], bwdp6[17], bwdh[17], bwdph[17], bwd8[17], bwdp8[17], fwd6[17], fwdh[17], bias[17], fwdh0, first6, first6p, first16, first16p, total;
-    size_t chs[17];      // per-output-channel balance factors rs_l[c] of conv l (powers of two, see lrpx_vgg16_pack)
-    size_t bwdw6[17];    // Winograd F(2x2,3x3) form of bwd6 (lrpx_pack_weights_wino_b6) for the relevance convs wino_layer() names, else 0
-    size_t spread;       // [17] per conv layer: largest ratio of row maxima max|W[c,:]| inside one 16-row K slice (lrpx_vgg16_row_spread)
-    size_t scratch;      // scaled weight copies while packing: cout*cin*9 + 2*cout*2*cin*9 floats of the largest layer
-};
 // relevance convs that can run on conv_wino_b6.h: long K on 56 / 28 / 14-pixel maps, not under a pool (conv3_1/2, conv4_1/2, conv5_1/2/3)
 static bool wino_layer(int l) {
     return l > 0 && kVgg[l].conv && kVgg[l].hw <= 56 && kVgg[l].cin % 64 == 0 && !(l + 1 < kNL && !kVgg[l + 1].conv);
 }
-static VggPacked vgg_packed_layout() {
-    VggPacked p;
+
+// ---- the packed blob: ONE list of its regions, in blob order (a new pack is one line here) -----------------------
+// vgg_packed_layout() and lrpx_vgg16_pack() both walk it; the chains address a region by its name and layer (VggPacked::at).
+enum PackLayers { L_CONV, L_UPPER, L_WINO, L_ONCE };   // every conv; the convs above conv1_1; wino_layer(); once, filled with conv1_1
+enum PackSrc { SRC_NONE, SRC_DUAL, SRC_SCALED, SRC_RAW, SRC_BIAS };   // the dual rows wd, the scaled rows wr, W itself (lrpx_vgg16_pack); the bias
+// fp32 fragments (K-chunk of the layer: lrpx_conv_kc), bf16x3, f16x2, f16f8, Winograd bf16x3; the first layer's direct-conv weights and
+// their matrix-core form; plain floats: `floats` of them, or one per output channel where that is 0.  X(name, layers, source, format, pack mode, floats)
+enum PackFmt { FMT_FP32, FMT_BF16X3, FMT_F16X2, FMT_F16F8, FMT_WINO, FMT_FIRST_VALU, FMT_FIRST_MFMA, FMT_FLOATS };
+#define LRPX_VGG_REGIONS(X)                                                                  \
+    X(fwd, L_CONV, SRC_DUAL, FMT_FP32, LRPX_PACK_FWD, 0)                                     \
+    X(bwd, L_CONV, SRC_SCALED, FMT_FP32, LRPX_PACK_BWD_POS, 0)                              /* conv1_1: LRPX_PACK_BWD_FIRST */ \
+    X(bias, L_CONV, SRC_BIAS, FMT_FLOATS, 0, 0)                                              \
+    X(bwdp, L_UPPER, SRC_RAW, FMT_FP32, LRPX_PACK_BWD_PLAIN, 0)                              \
+    X(bwd6, L_UPPER, SRC_SCALED, FMT_BF16X3, LRPX_PACK_BWD_POS, 0)                           \
+    X(bwdp6, L_UPPER, SRC_RAW, FMT_BF16X3, LRPX_PACK_BWD_PLAIN, 0)                           \
+    X(bwdh, L_UPPER, SRC_SCALED, FMT_F16X2, LRPX_PACK_BWD_POS, 0)                            \
+    X(fwdh, L_UPPER, SRC_DUAL, FMT_F16X2, LRPX_PACK_FWD, 0)                                  \
+    X(bwdph, L_UPPER, SRC_RAW, FMT_F16X2, LRPX_PACK_BWD_PLAIN, 0)                            \
+    X(bwd8, L_UPPER, SRC_SCALED, FMT_F16F8, LRPX_PACK_BWD_POS, 0)                            \
+    X(bwdp8, L_UPPER, SRC_RAW, FMT_F16F8, LRPX_PACK_BWD_PLAIN, 0)                            \
+    X(fwd6, L_UPPER, SRC_DUAL, FMT_BF16X3, LRPX_PACK_FWD, 0)                                 \
+    X(fwdh0, L_ONCE, SRC_DUAL, FMT_F16X2, LRPX_PACK_FWD, 0)                                 /* conv1_1 forward on the fp16 matrix cores */ \
+    X(first6, L_ONCE, SRC_SCALED, FMT_FIRST_VALU, LRPX_PACK_BWD_POS, 64 * 9 * 6)            /* direct-conv weights of the first layer's rule */ \
+    X(first6p, L_ONCE, SRC_RAW, FMT_FIRST_VALU, LRPX_PACK_BWD_PLAIN, 64 * 9 * 6)            /* ... and of its plain transposed conv (guided backprop) */ \
+    X(first16, L_ONCE, SRC_SCALED, FMT_FIRST_MFMA, LRPX_PACK_BWD_POS, 16 + 2 * 9 * 64 * 4)  /* first layer's rule on the matrix cores (header + A fragments) */ \
+    X(first16p, L_ONCE, SRC_RAW, FMT_FIRST_MFMA, LRPX_PACK_BWD_PLAIN, 16 + 2 * 9 * 64 * 4)  /* ... and its plain transposed conv */ \
+    X(chs, L_CONV, SRC_NONE, FMT_FLOATS, 0, 0)                                              /* per-output-channel balance factors rs_l[c] of conv l (powers of two, see lrpx_vgg16_pack) */ \
+    X(spread, L_ONCE, SRC_NONE, FMT_FLOATS, 0, 32)                                          /* [17] per conv layer: largest ratio of row maxima max|W[c,:]| inside one 16-row K slice (lrpx_vgg16_row_spread) */ \
+    X(bwdw6, L_WINO, SRC_SCALED, FMT_WINO, LRPX_PACK_BWD_POS, 0)                            /* Winograd F(2x2,3x3) form of bwd6 (lrpx_pack_weights_wino_b6) */ \
+    X(scratch, L_ONCE, SRC_NONE, FMT_FLOATS, 0, 512 * 512 * 9 * 3)                          /* scaled weight copies while packing: cout*cin*9 + 2*cout*2*cin*9 floats of the largest layer */
+#define X(name, ...) R_##name,
+enum PackId { LRPX_VGG_REGIONS(X) R_COUNT };
+#undef X
+#define X(name, ...) {__VA_ARGS__},
+static constexpr struct PackRegion { int layers, src, fmt, mode; size_t floats; } kRegions[R_COUNT] = {LRPX_VGG_REGIONS(X)};
+#undef X
+
+static bool region_has(const PackRegion& r, int l) {
+    return r.layers == L_ONCE ? l == 0 : (r.layers == L_WINO ? wino_layer(l) : (kVgg[l].conv && (l > 0 || r.layers == L_CONV)));
+}
+// The floats that region r takes for layer l and, with a destination, its pack from `src` (status in *rc): each format's size formula
+// next to its packer.  A weight pack feeds a GEMM of n_oc output channels over k from a source matrix of rows x cols x 9 taps: the conv
+// (LRPX_PACK_FWD) or its transpose.  conv1_1: its image is [x+ | x-] in 8 channels (one 16-channel K-chunk on the fp16 matrix cores), its
+// transposed conv is padded to 32 output channels and takes LRPX_PACK_BWD_FIRST
+static size_t region_floats(const PackRegion& r, int l, const float* src = nullptr, float* dst = nullptr, void* stream = nullptr, int* rc = nullptr) {
+    const VggLayer& L = kVgg[l];
+    const bool fwd = r.mode == LRPX_PACK_FWD, plain = r.mode == LRPX_PACK_BWD_PLAIN;
+    const int n_oc = fwd ? 2 * L.cout : (l > 0 ? L.cin : 32), k = !fwd ? L.cout : (l > 0 ? L.cin : (r.fmt == FMT_FP32 ? cin_pad(0) : 16));
+    const int rows = fwd ? 2 * L.cout : L.cout, cols = (fwd && l == 0) ? 2 * L.cin : L.cin, kc = lrpx_conv_kc(L.hw, 9, k);
+    const size_t plain_floats = r.floats ? r.floats : (size_t)L.cout;
+    switch (r.fmt) {
+        case FMT_FP32: if (dst) *rc = lrpx_pack_weights(src, rows, cols, 9, (l == 0 && !fwd && !plain) ? LRPX_PACK_BWD_FIRST : r.mode, kc, dst, stream);
+            return lrpx_packed_floats(n_oc, k, 9, kc);
+        case FMT_BF16X3: if (dst) *rc = lrpx_pack_weights_bf16x3(src, rows, cols, 9, r.mode, dst, stream);
+            return lrpx_packed_bf16x3_bytes(n_oc, k, 9) / sizeof(float);
+        case FMT_F16X2: if (dst) *rc = lrpx_pack_weights_f16x2(src, rows, cols, 9, r.mode, dst, stream);
+            return lrpx_packed_f16x2_bytes(n_oc, k, 9) / sizeof(float);
+        case FMT_F16F8: if (dst) *rc = lrpx_pack_weights_f16f8(src, rows, cols, r.mode, dst, stream);
+            return lrpx_packed_f16f8_bytes(n_oc, k) / sizeof(float);
+        case FMT_WINO: if (dst) *rc = lrpx_pack_weights_wino_b6(src, rows, cols, r.mode, dst, stream);
+            return lrpx_packed_wino_b6_bytes(n_oc, k) / sizeof(float);
+        case FMT_FIRST_VALU: if (dst) *rc = first_layer_pack(src, dst, L.cout, plain, (hipStream_t)stream); return r.floats;
+        case FMT_FIRST_MFMA: if (dst) *rc = first_layer_pack_mfma(src, dst, plain, (hipStream_t)stream); return r.floats;
+        default:      // (of the sources, only the bias is copied as it is)
+            if (dst && hipMemcpyAsync(dst, src, plain_floats * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
+                set_error("vgg16_pack: bias copy failed");
+                *rc = LRPX_ELAUNCH;
+            }
+            return plain_floats;
+    }
+}
+
+struct VggPacked {   // offsets in floats into the packed blob (0: the layer has no such region)
+    size_t off[R_COUNT][17], total;
+    size_t at(int region, int l = 0) const { return off[region][l]; }
+};
+// regions that follow each other in the list and are not L_ONCE lie layer by layer: [fwd .. fwd6] of conv1_1, of conv1_2, ...
+static VggPacked make_packed_layout() {
+    VggPacked p = {};
     size_t off = 0;
-    for (int l = 0; l < kNL; ++l) {
-        p.fwd[l] = p.bwd[l] = p.bwdp[l] = p.bwd6[l] = p.bwdp6[l] = p.bwdh[l] = p.bwdph[l] = p.bwd8[l] = p.bwdp8[l] = p.fwd6[l] = p.fwdh[l] = p.bias[l] = 0;
-        if (!kVgg[l].conv) continue;
-        const VggLayer& L = kVgg[l];
-        p.fwd[l] = off; off += lrpx_packed_floats(2 * L.cout, cin_pad(l), 9, lrpx_conv_kc(L.hw, 9, cin_pad(l)));
-        p.bwd[l] = off; off += lrpx_packed_floats(l == 0 ? 32 : L.cin, L.cout, 9, lrpx_conv_kc(L.hw, 9, L.cout));
-        p.bias[l] = off; off += (size_t)L.cout;
-        if (l > 0) { p.bwdp[l] = off; off += lrpx_packed_floats(L.cin, L.cout, 9, lrpx_conv_kc(L.hw, 9, L.cout)); }
-        if (l > 0) { p.bwd6[l] = off; off += lrpx_packed_bf16x3_bytes(L.cin, L.cout, 9) / sizeof(float); }
-        if (l > 0) { p.bwdp6[l] = off; off += lrpx_packed_bf16x3_bytes(L.cin, L.cout, 9) / sizeof(float); }
-        if (l > 0) { p.bwdh[l] = off; off += lrpx_packed_f16x2_bytes(L.cin, L.cout, 9) / sizeof(float); }
-        if (l > 0) { p.fwdh[l] = off; off += lrpx_packed_f16x2_bytes(2 * L.cout, L.cin, 9) / sizeof(float); }
-        if (l > 0) { p.bwdph[l] = off; off += lrpx_packed_f16x2_bytes(L.cin, L.cout, 9) / sizeof(float); }
-        if (l > 0) { p.bwd8[l] = off; off += lrpx_packed_f16f8_bytes(L.cin, L.cout) / sizeof(float); }
-        if (l > 0) { p.bwdp8[l] = off; off += lrpx_packed_f16f8_bytes(L.cin, L.cout) / sizeof(float); }
-        if (l > 0) {
-            p.fwd6[l] = off; off += lrpx_packed_bf16x3_bytes(2 * L.cout, L.cin, 9) / sizeof(float);
-        }
+    for (int r = 0, end; r < R_COUNT; r = end) {
+        for (end = r + 1; kRegions[r].layers != L_ONCE && end < R_COUNT && kRegions[end].layers != L_ONCE;) ++end;
+        for (int l = 0; l < kNL; ++l)
+            for (int e = r; e < end; ++e)
+                if (region_has(kRegions[e], l)) { p.off[e][l] = off; off += region_floats(kRegions[e], l); }
     }
-    p.fwdh0 = off; off += lrpx_packed_f16x2_bytes(2 * 64, 16, 9) / sizeof(float);   // conv1_1 forward on the fp16 matrix cores
-    p.first6 = off; off += (size_t)64 * 9 * 6;   // direct-conv weights of the first layer's rule
-    p.first6p = off; off += (size_t)64 * 9 * 6;  // ... and of its plain transposed conv (guided backprop)
-    p.first16 = off; off += (size_t)16 + 2 * 9 * 64 * 4;   // first layer's rule on the matrix cores (header + A fragments)
-    p.first16p = off; off += (size_t)16 + 2 * 9 * 64 * 4;  // ... and its plain transposed conv
-    for (int l = 0; l < kNL; ++l) {
-        p.chs[l] = off;
-        if (kVgg[l].conv) off += (size_t)kVgg[l].cout;
-    }
-    p.spread = off; off += 32;
-    for (int l = 0; l < kNL; ++l) {
-        p.bwdw6[l] = 0;
-        if (wino_layer(l)) { p.bwdw6[l] = off; off += lrpx_packed_wino_b6_bytes(kVgg[l].cin, kVgg[l].cout) / sizeof(float); }
-    }
-    p.scratch = off; off += (size_t)512 * 512 * 9 * 3;
     p.total = off;
     return p;
+}
+static const VggPacked& vgg_packed_layout() { static const VggPacked p = make_packed_layout(); return p; }   // (once: every chain call asks for it)
+
+// ---- what a conv mode is to the chains: one row per resolved mode (a new arithmetic is one row here) ----------
+struct ConvArith { int f16x3, bf16x6, pack; };   // lrpx_conv_desc.f16x3 / .bf16x6 and the region that holds the weights
+struct ModeRow {
+    ConvArith rel, plain, fwd;   // the relevance convs (rows rs W+), the plain transposed convs of the image-gradient chains (W itself), the exact forward
+    bool amax;         // operands sit behind per-map power-of-two scales: max|S| words per (layer, map) behind the R buffer
+    bool blocked;      // every S tensor of the relevance chain and the multiplicands are BLOCKED (blocked.h), the kernels accumulate channels x pixels
+    bool fused;        // relevance: the fused flow (relevance_fused), else round 1's (relevance_rel)
+    bool lowres;       // gradient chains: a conv under a pool takes the gradient at the pool's OUTPUT resolution (vgg16_backprop), else a pool-backward kernel
+    bool first_mfma;   // conv1_1 on the matrix cores (S in 32-channel chunks), else the direct fp32 VALU conv (16-channel chunks): Chain::first_layer
+};
+static constexpr ModeRow kModes[4] = {
+    {{0, 0, R_bwd}, {0, 0, R_bwdp}, {0, 0, R_fwd}, false, false, false, false, false},      // 0: fp32 MFMA
+    // 1 (round 6): exact bf16 splits on the conv_f16x3.h tiling (B6): no operand scales, hence no amax words; pools folded into the staging as in mode 3
+    {{0, 1, R_bwd6}, {0, 1, R_bwdp6}, {0, 1, R_fwd6}, false, false, true, true, false},
+    {{1, 0, R_bwdh}, {1, 0, R_bwdph}, {0, 1, R_fwd6}, true, false, true, false, true},      // 2: fp16 split products
+    {{2, 0, R_bwd8}, {2, 0, R_bwdp8}, {0, 1, R_fwd6}, true, true, true, true, true},        // 3: ... with the cross products on the fp8 matrix cores
+};
+// the forward trace runs on the EXACT kernels (fp32 MFMA for conv1_1; above it the mode's, round 6: conv1_2 too) unless forward_f16
+// comes with mode 2 / 3: the fp16 split products then, conv1_1 included
+static ConvArith fwd_arith(const VggCtx& cx, int l) {
+    if (cx.fwd_f16 && cx.mode >= 2) return {1, 0, l > 0 ? R_fwdh : R_fwdh0};
+    return l > 0 ? kModes[cx.mode].fwd : kModes[0].fwd;
 }
 
 // ---- channel balance of the Z+ / relevance side (round 5) ----------------------------------------------------------------------
@@ -346,7 +408,7 @@ int lrpx_vgg16_pack(const float* const* w, const float* const* b, void* packed, 
     LRPX_REQUIRE(w && b && packed, "vgg16_pack: null pointer");
     LRPX_CHECK_PTRS("lrpx_vgg16_pack", {packed, "packed"});
     for (int i = 0; i < 13; ++i) LRPX_CHECK_PTRS("lrpx_vgg16_pack", {w[i], "w[i]"}, {b[i], "b[i]"});
-    VggPacked p = vgg_packed_layout();
+    const VggPacked& p = vgg_packed_layout();
     float* base = (float*)packed;
     int ci = 0;
     hipStream_t st = (hipStream_t)stream;
@@ -355,48 +417,25 @@ int lrpx_vgg16_pack(const float* const* w, const float* const* b, void* packed, 
         const VggLayer& L = kVgg[l];
         LRPX_REQUIRE(w[ci] && b[ci], "vgg16_pack: null weight %d", ci);
         // channel balance (see row_scale_kernel): rs, wr = rs W (every row), wd = [W ; rs W+] for the forward packs
-        float* rs = base + p.chs[l];
-        float* wr = base + p.scratch;
+        float* rs = base + p.at(R_chs, l);
+        float* wr = base + p.at(R_scratch);
         float* wd = wr + (size_t)L.cout * L.cin * 9;
         const int first = l == 0, cin2 = first ? 2 * L.cin : L.cin;
         float* rmax = wr;                                    // (row maxima: 2 x cout floats at the head of the scratch, consumed before wr is written)
         hipLaunchKernelGGL(row_max_kernel, dim3(L.cout), dim3(256), 0, st, w[ci], L.cin * 9, first, rmax, rmax + L.cout);
         LRPX_TRY(check_launch("vgg16_pack: row maxima"));
-        hipLaunchKernelGGL(row_scale_kernel, dim3(1), dim3(512), 0, st, rmax, rmax + L.cout, L.cout, rs, base + p.spread + l);
+        hipLaunchKernelGGL(row_scale_kernel, dim3(1), dim3(512), 0, st, rmax, rmax + L.cout, L.cout, rs, base + p.at(R_spread) + l);
         LRPX_TRY(check_launch("vgg16_pack: row scales"));
         const long n_w = (long)L.cout * L.cin * 9, n_d = (long)2 * L.cout * cin2 * 9;
         hipLaunchKernelGGL(scale_rows_kernel, dim3((unsigned)((n_w + 255) / 256)), dim3(256), 0, st, w[ci], rs, wr, L.cin * 9, n_w);
         LRPX_TRY(check_launch("vgg16_pack: scaled rows"));
         hipLaunchKernelGGL(dual_rows_kernel, dim3((unsigned)((n_d + 255) / 256)), dim3(256), 0, st, w[ci], rs, wd, L.cout, L.cin, first, n_d);
         LRPX_TRY(check_launch("vgg16_pack: dual rows"));
-        const float* w_plain = w[ci];      // the image-gradient chains (guided backprop, plain gradient) take W itself
-        LRPX_TRY(lrpx_pack_weights(wd, 2 * L.cout, cin2, 9, LRPX_PACK_FWD, lrpx_conv_kc(L.hw, 9, cin_pad(l)), base + p.fwd[l], stream));
-        LRPX_TRY(lrpx_pack_weights(wr, L.cout, L.cin, 9, l == 0 ? LRPX_PACK_BWD_FIRST : LRPX_PACK_BWD_POS,
-                                   lrpx_conv_kc(L.hw, 9, L.cout), base + p.bwd[l], stream));
-        if (hipMemcpyAsync(base + p.bias[l], b[ci], L.cout * sizeof(float), hipMemcpyDeviceToDevice,
-                           (hipStream_t)stream) != hipSuccess) {
-            set_error("vgg16_pack: bias copy failed");
-            return LRPX_ELAUNCH;
-        }
-        if (l == 0) {
-            LRPX_TRY(lrpx_pack_weights_f16x2(wd, 2 * L.cout, cin2, 9, LRPX_PACK_FWD, base + p.fwdh0, stream));
-            LRPX_TRY(first_layer_pack(wr, base + p.first6, L.cout, 0, (hipStream_t)stream));
-            LRPX_TRY(first_layer_pack(w_plain, base + p.first6p, L.cout, 1, (hipStream_t)stream));
-            LRPX_TRY(first_layer_pack_mfma(wr, base + p.first16, 0, (hipStream_t)stream));
-            LRPX_TRY(first_layer_pack_mfma(w_plain, base + p.first16p, 1, (hipStream_t)stream));
-        } else {
-            LRPX_TRY(lrpx_pack_weights(w_plain, L.cout, L.cin, 9, LRPX_PACK_BWD_PLAIN, lrpx_conv_kc(L.hw, 9, L.cout),
-                                       base + p.bwdp[l], stream));
-        }
-        if (l > 0) LRPX_TRY(lrpx_pack_weights_bf16x3(wr, L.cout, L.cin, 9, LRPX_PACK_BWD_POS, base + p.bwd6[l], stream));
-        if (wino_layer(l)) LRPX_TRY(lrpx_pack_weights_wino_b6(wr, L.cout, L.cin, LRPX_PACK_BWD_POS, base + p.bwdw6[l], stream));
-        if (l > 0) LRPX_TRY(lrpx_pack_weights_f16x2(wr, L.cout, L.cin, 9, LRPX_PACK_BWD_POS, base + p.bwdh[l], stream));
-        if (l > 0) LRPX_TRY(lrpx_pack_weights_f16x2(wd, 2 * L.cout, L.cin, 9, LRPX_PACK_FWD, base + p.fwdh[l], stream));
-        if (l > 0) LRPX_TRY(lrpx_pack_weights_f16x2(w_plain, L.cout, L.cin, 9, LRPX_PACK_BWD_PLAIN, base + p.bwdph[l], stream));
-        if (l > 0) LRPX_TRY(lrpx_pack_weights_f16f8(wr, L.cout, L.cin, LRPX_PACK_BWD_POS, base + p.bwd8[l], stream));
-        if (l > 0) LRPX_TRY(lrpx_pack_weights_f16f8(w_plain, L.cout, L.cin, LRPX_PACK_BWD_PLAIN, base + p.bwdp8[l], stream));
-        if (l > 0) LRPX_TRY(lrpx_pack_weights_bf16x3(wd, 2 * L.cout, L.cin, 9, LRPX_PACK_FWD, base + p.fwd6[l], stream));
-        if (l > 0) LRPX_TRY(lrpx_pack_weights_bf16x3(w_plain, L.cout, L.cin, 9, LRPX_PACK_BWD_PLAIN, base + p.bwdp6[l], stream));
+        // every region of this layer that has a source, in list order: they write disjoint parts of the blob from sources that are complete by now
+        // (SRC_RAW: the image-gradient chains - guided backprop, plain gradient - take W itself)
+        const float* srcs[] = {nullptr, wd, wr, w[ci], b[ci]};
+        for (int r = 0, rc = LRPX_OK; r < R_COUNT; ++r)
+            if (kRegions[r].src != SRC_NONE && region_has(kRegions[r], l)) { region_floats(kRegions[r], l, srcs[kRegions[r].src], base + p.at(r, l), stream, &rc); LRPX_TRY(rc); }
         ++ci;
     }
     return LRPX_OK;
@@ -448,13 +487,13 @@ const float* lrpx_vgg16_trace_features(const void* trace, int n_img) {
 }
 
 const float* lrpx_vgg16_row_spread(const void* packed) {
-    return packed ? (const float*)packed + vgg_packed_layout().spread : nullptr;
+    return packed ? (const float*)packed + vgg_packed_layout().at(R_spread) : nullptr;
 }
 
 const float* lrpx_vgg16_channel_scales(const void* packed, int layer, int* n_channels) {
     if (!packed || layer < 0 || layer >= kNL || !kVgg[layer].conv) return nullptr;
     if (n_channels) *n_channels = kVgg[layer].cout;
-    return (const float*)packed + vgg_packed_layout().chs[layer];
+    return (const float*)packed + vgg_packed_layout().at(R_chs, layer);
 }
 
 int lrpx_vgg16_forward(const void* packed, const float* img_nchw, int n_img, void* trace, float* feat_nhwc,
@@ -466,45 +505,40 @@ int lrpx_vgg16_forward_ex(const void* packed, const float* img_nchw, int n_img, 
                           const lrpx_vgg16_opts* opts, void* stream) {
     LRPX_CHECK_PTRS("lrpx_vgg16_forward_ex", {packed, "packed"}, {img_nchw, "img_nchw"}, {trace, "trace"}, {feat_nhwc, "feat_nhwc"});
     LRPX_REQUIRE(packed && img_nchw && trace && n_img > 0, "vgg16_forward: bad arguments");
-    const VggCtx cx = resolve_ctx(opts);
-    const int mode = cx.mode, fwd_f16 = cx.fwd_f16;      // this call's values
-    const bool use_bf16x6 = cx.bf16x6();
-    const VggPacked p = vgg_packed_layout();
+    const VggCtx cx = resolve_ctx(opts);      // this call's values
+    const bool f16 = fwd_arith(cx, 0).f16x3;
+    const VggPacked& p = vgg_packed_layout();
     const VggTrace t = vgg_trace_layout(n_img);
     const float* pk = (const float*)packed;
     float* tr = (float*)trace;
-    if (fwd_f16 && mode >= 2) LRPX_TRY(clear_async(tr + t.famax, (size_t)18 * n_img * sizeof(unsigned), (hipStream_t)stream));
+    // fp16 split products (conv_f16x3.h): operand scale = max of the layer input per image
+    unsigned* fam = reinterpret_cast<unsigned*>(tr + t.famax);
+    if (f16) LRPX_TRY(clear_async(fam, (size_t)18 * n_img * sizeof(unsigned), (hipStream_t)stream));
     // the signed image is kept split into x+ / x- (channels 0-2 / 3-5 of 8): Z of the first conv needs both
     LRPX_TRY(lrpx_nchw_to_nhwc_posneg(img_nchw, tr + t.act[0], n_img, 3, 224 * 224, 8, stream));
     bool pools_fused = false, pools_plain = false;
     for (int l = 0; l < kNL; ++l) {
         const VggLayer& L = kVgg[l];
         if (L.conv) {
+            const ConvArith a = fwd_arith(cx, l);
             lrpx_conv_desc d = {};
-            d.in = tr + t.act[l]; d.wpacked = pk + p.fwd[l];
+            d.in = tr + t.act[l]; d.wpacked = pk + p.at(a.pack, l); d.f16x3 = a.f16x3; d.bf16x6 = a.bf16x6;
             d.n_maps = n_img; d.hw = L.hw; d.cin = cin_pad(l); d.n_oc = 2 * L.cout; d.taps = 9;
-            d.epi = EPI_FWD_DUAL; d.oc_split = L.cout; d.bias = pk + p.bias[l];
+            d.epi = EPI_FWD_DUAL; d.oc_split = L.cout; d.bias = pk + p.at(R_bias, l);
             d.out0 = tr + t.act[l + 1]; d.out1 = tr + t.zpos[l];
-            if (fwd_f16 && mode >= 2 && l >= 1) {
-                // fp16 split products (conv_f16x3.h): operand scale = max of the layer input per image; a max-pool keeps it
-                unsigned* fam = reinterpret_cast<unsigned*>(tr + t.famax);
-                const int in_l = kVgg[l - 1].conv ? l : l - 1;
-                // (the maximum of act[1] is recorded by conv1_1's epilogue below: l == 0)
-                d.f16x3 = 1; d.wpacked = pk + p.fwdh[l];
-                d.in_amax = fam + (size_t)in_l * n_img; d.out0_amax = fam + (size_t)(l + 1) * n_img;
-            } else if (use_bf16x6 && l > 0) {
-                // mode 1: exact bf16 splits (round 6: conv1_2 too)
-                d.bf16x6 = 1; d.wpacked = pk + p.fwd6[l];
-            } else if (fwd_f16 && mode >= 2) {
+            if (f16) {
+                // a max-pool keeps the maximum of its input; the epilogue records the per-image maximum of the activations, the next conv's scale
+                d.in_amax = fam + (size_t)((l == 0 || kVgg[l - 1].conv) ? l : l - 1) * n_img;
+                d.out0_amax = fam + (size_t)(l + 1) * n_img;
+            }
+            if (f16 && l == 0) {
                 // conv1_1 on the fp16 matrix cores too (the fp32 MFMA kernel: 0.67 ms per 16 images for 15 GFLOP and 0.4 GB -
                 // neither its matrix nor its memory time): the signed image [x+ | x- | 0] padded to one 16-channel
                 // K-chunk (51 MB per 16 images, in the scratch region of the trace), scale = max|pixel| per image
-                unsigned* fam = reinterpret_cast<unsigned*>(tr + t.famax);
                 float* img16 = tr + t.xz[1];
                 LRPX_TRY(lrpx_nchw_to_nhwc_posneg(img_nchw, img16, n_img, 3, 224 * 224, 16, stream));
                 LRPX_TRY(lrpx_amax_maps(img16, n_img, (long)224 * 224 * 16, fam, stream));
-                d.in = img16; d.cin = 16; d.f16x3 = 1; d.wpacked = pk + p.fwdh0; d.in_amax = fam;
-                d.out0_amax = fam + (size_t)1 * n_img;       // per-image maximum of the activations: conv1_2's fp16 scale
+                d.in = img16; d.cin = 16;
             }
             const int fwd_ks = fwd_ksplit(d.f16x3, d.bf16x6, L.hw);
             if (fwd_ks > 1) {
@@ -517,7 +551,7 @@ int lrpx_vgg16_forward_ex(const void* packed, const float* img_nchw, int n_img, 
                 d.epi = EPI_PLAIN; d.bias = nullptr; d.oc_split = 2 * L.cout;
                 d.out0 = part; d.out1 = nullptr; d.out0_amax = nullptr;
                 LRPX_TRY(conv_dispatch(&d, (hipStream_t)stream, fwd_ks));
-                LRPX_TRY(fwd_dual_finish(part, fwd_ks, pk + p.bias[l], tr + t.act[l + 1], tr + t.zpos[l], n_img,
+                LRPX_TRY(fwd_dual_finish(part, fwd_ks, pk + p.at(R_bias, l), tr + t.act[l + 1], tr + t.zpos[l], n_img,
                                          (long)L.hw * L.hw, L.cout, act_amax, (hipStream_t)stream));
                 continue;
             }
@@ -545,32 +579,32 @@ int lrpx_vgg16_forward_ex(const void* packed, const float* img_nchw, int n_img, 
     return LRPX_OK;
 }
 
-int lrpx_vgg16_relevance(const void* packed, const void* trace, int n_img, const float* r_feat_nhwc,
-                         const int32_t* map2img, int n_maps, void* workspace, float* out_nchw, void* stream) {
-    if (tl_timing) {       // legacy per-thread profiling switch: this call records and waits for its own events
-        lrpx_vgg16_opts o = {-1, -1, tl_ms};
-        return lrpx_vgg16_relevance_ex(packed, trace, n_img, r_feat_nhwc, map2img, n_maps, workspace, out_nchw, &o, stream);
-    }
-    return lrpx_vgg16_relevance_ex(packed, trace, n_img, r_feat_nhwc, map2img, n_maps, workspace, out_nchw, nullptr, stream);
-}
+}  // extern "C"
 
 // per-call HIP events around the conv launches of one relevance pass (opts.layer_ms)
 struct LayerTimer {
     hipEvent_t ev[17][2];
     bool made = false, valid[17] = {};
     int begin() {
-        for (int l = 0; l < 17; ++l)
-            for (int k = 0; k < 2; ++k)
-                if (hipEventCreate(&ev[l][k]) != hipSuccess) { set_error("vgg16_relevance: hipEventCreate failed"); return LRPX_ELAUNCH; }
+        for (auto& pair : ev)
+            for (hipEvent_t& e : pair)
+                if (hipEventCreate(&e) != hipSuccess) { set_error("vgg16_relevance: hipEventCreate failed"); return LRPX_ELAUNCH; }
         made = true;
         return LRPX_OK;
     }
-    int finish(float* ms17) {       // waits for the recorded events, then releases them
+    // the launches of layer l, between the layer's two events where begin() made them
+    template <class F> int timed(int l, hipStream_t st, F launches) {
+        if (made) (void)hipEventRecord(ev[l][0], st);
+        LRPX_TRY(launches());
+        if (made) { (void)hipEventRecord(ev[l][1], st); valid[l] = true; }
+        return LRPX_OK;
+    }
+    // waits for the recorded events.  (Out of line, as it always was: the library's list of exported symbols has it.)
+    __attribute__((noinline)) int finish(float* ms17) {
         int rc = LRPX_OK;
         for (int l = 0; l < 17; ++l) {
             ms17[l] = 0.f;
-            if (valid[l] && (hipEventSynchronize(ev[l][1]) != hipSuccess ||
-                             hipEventElapsedTime(&ms17[l], ev[l][0], ev[l][1]) != hipSuccess)) {
+            if (valid[l] && (hipEventSynchronize(ev[l][1]) != hipSuccess || hipEventElapsedTime(&ms17[l], ev[l][0], ev[l][1]) != hipSuccess)) {
                 set_error("vgg16_relevance: event query failed");
                 rc = LRPX_ELAUNCH;
             }
@@ -578,152 +612,203 @@ struct LayerTimer {
         return rc;
     }
     ~LayerTimer() {
-        if (made)
-            for (int l = 0; l < 17; ++l)
-                for (int k = 0; k < 2; ++k) (void)hipEventDestroy(ev[l][k]);
+        for (auto& pair : ev)
+            for (hipEvent_t e : pair) if (made) (void)hipEventDestroy(e);
     }
 };
 
-int lrpx_vgg16_relevance_ex(const void* packed, const void* trace, int n_img, const float* r_feat_nhwc,
-                            const int32_t* map2img, int n_maps, void* workspace, float* out_nchw,
-                            const lrpx_vgg16_opts* opts, void* stream) {
-    LRPX_CHECK_PTRS("lrpx_vgg16_relevance_ex", {packed, "packed"}, {trace, "trace"}, {r_feat_nhwc, "r_feat_nhwc"}, {map2img, "map2img"}, {workspace, "workspace"}, {out_nchw, "out_nchw"});
-    LRPX_REQUIRE(packed && trace && r_feat_nhwc && workspace && out_nchw && n_maps > 0 && n_img > 0,
-                 "vgg16_relevance: bad arguments");
-    const VggCtx cx = resolve_ctx(opts);
-    const int mode = cx.mode;
-    LayerTimer timer;
-    LRPX_REQUIRE(map2img || n_maps == n_img, "vgg16_relevance: map2img is required when n_maps != n_img");
-    const VggPacked p = vgg_packed_layout();
-    const VggTrace t = vgg_trace_layout(n_img);
-    const float* pk = (const float*)packed;
-    const float* tr = (const float*)trace;
-    float* ws = (float*)workspace;
-    const size_t sbuf = (size_t)224 * 224 * 64 * n_maps;
-    float* S[2] = {ws, ws + sbuf};
-    float* R = ws + 2 * sbuf;
-    int cur = 0;
-    int cur_chunked = 0;   // S[cur] is stored in K-chunks (written so by the pool kernel for the 224^2 / 112^2 layers)
-    // f16x3 mode: amax[l*n_maps + n] = bits of max|S| of map n in the S tensor that conv layer l consumes
-    const bool h3 = mode >= 2;
-    // mode 1 (round 6): the same FUSED flow - REL_MUL epilogues on the precomputed multiplicands, convs under a pool unpool while they stage,
-    // no pool kernels, no unpooled tensors - on the exact bf16 splits (conv_f16x3.h, B6): no operand scales, hence no amax words.
-    // Mode 0 alone keeps round 1's flow: EPI_REL with the division in the epilogue + maxpool_relevance kernels.
-    const bool b6 = mode == 1;
-    const bool fused = h3 || b6;
-    unsigned* amax = h3 ? reinterpret_cast<unsigned*>(R + (size_t)112 * 112 * 64 * n_maps) : nullptr;
-    if (h3) LRPX_TRY(clear_async(amax, (size_t)kNL * n_maps * sizeof(unsigned), (hipStream_t)stream));
-    // mode 3: every S tensor of the chain and the multiplicands are BLOCKED (blocked.h), the kernels accumulate channels x pixels
-    const bool blk = mode == 3;
+// what the backward chains of one call work on
+namespace {
+struct Chain {
+    const ModeRow& m;
+    const VggPacked& p;
+    const VggTrace t;
+    const float *pk, *tr;      // the blob, the trace
+    const int32_t* map2img;
+    int n_img, n_maps;
+    float *buf[2], *R;         // the workspace: two ping-pong buffers for S (the gradient), the R buffer in front of a pool and, behind it,
+    unsigned* amax;            // in the modes with operand scales: amax[l * n_maps + n] = bits of the maximum over map n of the tensor
+    hipStream_t st;            // that conv layer l consumes, recorded by whoever writes that tensor
+    Chain(const lrpx_vgg16_opts* opts, const void* packed, const void* trace, int n_img_, const int32_t* map2img_, int n_maps_, void* workspace, void* stream)
+        : m(kModes[resolve_ctx(opts).mode]), p(vgg_packed_layout()), t(vgg_trace_layout(n_img_)), pk((const float*)packed), tr((const float*)trace),
+          map2img(map2img_), n_img(n_img_), n_maps(n_maps_), st((hipStream_t)stream) {
+        const size_t sbuf = (size_t)224 * 224 * 64 * n_maps;
+        buf[0] = (float*)workspace; buf[1] = buf[0] + sbuf; R = buf[0] + 2 * sbuf;
+        amax = m.amax ? reinterpret_cast<unsigned*>(R + (size_t)112 * 112 * 64 * n_maps) : nullptr;
+    }
+    // the head of the descriptor of conv layer l's transposed conv on `in`.  unpool: under a pool, `in` is the low-resolution tensor that the
+    // conv above the pool wrote, unpooled while staged
+    lrpx_conv_desc desc(int l, const ConvArith& a, const float* in, bool unpool) const {
+        const VggLayer& L = kVgg[l];
+        lrpx_conv_desc d = {};
+        d.in = in; d.wpacked = pk + p.at(a.pack, l); d.f16x3 = a.f16x3; d.bf16x6 = a.bf16x6;
+        d.n_maps = n_maps; d.hw = L.hw; d.cin = L.cout; d.taps = 9; d.map2img = map2img; d.n_oc = L.cin; d.oc_split = L.cin;
+        if (amax) d.in_amax = amax + (size_t)l * n_maps;
+        // the maps of one image (the words of its caption) usually follow each other: tile-order hint for the
+        // multiplicand reuse in L2 (a wrong guess only costs the reuse; the fp32 kernels take none)
+        d.tile_group = (n_maps % n_img == 0) ? n_maps / n_img : 0;
+        if (unpool && l + 1 < kNL && !kVgg[l + 1].conv) d.pool_am = (const uint8_t*)(tr + t.am[l + 1]);
+        return d;
+    }
+    // conv1_1's step of a chain, 3 output channels (first_layer.hip): 16x16x32 MFMAs on the split halves of S in the split-product modes (S comes
+    // with its per-map maximum), the direct fp32 VALU conv otherwise.  S of the fused relevance flow comes in channel chunks
+    int first_layer(const float* S, float* out_nchw, int plain) const {      // plain: the transposed conv with W itself (the image-gradient chains)
+        const int s_layout = (!plain && m.fused) ? 1 : 0;
+        if (m.first_mfma)
+            return first_layer_relevance_mfma(S, pk + p.at(plain ? R_first16p : R_first16), tr + t.act[0], map2img, amax, out_nchw, n_maps, plain, s_layout, st);
+        return first_layer_relevance(S, pk + p.at(plain ? R_first6p : R_first6), tr + t.act[0], map2img, out_nchw, n_maps, kVgg[0].cout, plain, s_layout, st);
+    }
+};
+}  // namespace
+
+// Mode 0 keeps round 1's relevance flow: EPI_REL with the division in the epilogue + maxpool_relevance kernels
+static int relevance_rel(const Chain& c, const float* r_feat_nhwc, float* out_nchw, LayerTimer& timer) {
+    const VggTrace& t = c.t;
+    int cur = 0, cur_chunked = 0;   // S[cur] is stored in K-chunks (written so by the pool kernel for the 224^2 / 112^2 layers)
     // S_16 = R_feat / safe(Z+_16)
-    if (blk)
-        LRPX_TRY(divide_stab_blocked(r_feat_nhwc, tr + t.zpos[16], map2img, S[cur], n_maps, 196, 512, amax + (size_t)16 * n_maps,
-                                     (hipStream_t)stream));
-    else
-        LRPX_TRY(divide_stab_amax(r_feat_nhwc, tr + t.zpos[16], map2img, S[cur], n_maps, (long)196 * 512, fused ? STAB_SAFE0 : STAB_SAFE,
-                                  h3 ? amax + (size_t)16 * n_maps : nullptr, (hipStream_t)stream));
-    const bool timing = cx.layer_ms != nullptr;
-    if (timing) LRPX_TRY(timer.begin());
-#define LRPX_TIMED_DISPATCH(L_, DESC)                                                   \
-    do {                                                                                \
-        if (timing) (void)hipEventRecord(timer.ev[L_][0], (hipStream_t)stream);         \
-        LRPX_TRY(conv_dispatch(DESC, (hipStream_t)stream));                             \
-        if (timing) { (void)hipEventRecord(timer.ev[L_][1], (hipStream_t)stream); timer.valid[L_] = true; } \
-    } while (0)
-    for (int l = kNL - 1; l >= 0; --l) {
+    LRPX_TRY(divide_stab_amax(r_feat_nhwc, c.tr + t.zpos[16], c.map2img, c.buf[cur], c.n_maps, (long)196 * 512, STAB_SAFE, nullptr, c.st));
+    for (int l = kNL - 1; l > 0; --l) {
         const VggLayer& L = kVgg[l];
         if (!L.conv) continue;   // pools are handled together with the conv above them
-        lrpx_conv_desc d = {};
-        d.in = S[cur]; d.wpacked = pk + p.bwd[l];
-        d.n_maps = n_maps; d.hw = L.hw; d.cin = L.cout; d.taps = 9; d.map2img = map2img;
-        d.x = tr + t.act[l];
-        d.in_chunked = cur_chunked;
+        lrpx_conv_desc d = c.desc(l, c.m.rel, c.buf[cur], false);
+        d.epi = EPI_REL; d.x = c.tr + t.act[l]; d.in_chunked = cur_chunked;
         cur_chunked = 0;
-        if (l == 0) {
-            // 3 output channels (first_layer.hip): 16x16x32 MFMAs on the split halves of S in the split-product modes (S
-            // comes with its per-map maximum, in 32-channel chunks), the direct fp32 VALU conv otherwise
-            if (timing) (void)hipEventRecord(timer.ev[0][0], (hipStream_t)stream);
-            if (h3)
-                LRPX_TRY(first_layer_relevance_mfma(S[cur], pk + p.first16, tr + t.act[0], map2img, amax, out_nchw, n_maps,
-                                                    0, 1, (hipStream_t)stream));
-            else
-                LRPX_TRY(first_layer_relevance(S[cur], pk + p.first6, tr + t.act[0], map2img, out_nchw, n_maps, L.cout, 0,
-                                               fused ? 1 : 0, (hipStream_t)stream));
-            if (timing) { (void)hipEventRecord(timer.ev[0][1], (hipStream_t)stream); timer.valid[0] = true; }
-            break;
+        const bool pool_below = !kVgg[l - 1].conv;
+        // ReLU passes relevance through (lrp_modules.py:42-46): fuse the next layer's S = R / safe(Z+)
+        if (!pool_below) { d.out1 = c.buf[cur ^ 1]; d.zdiv = c.tr + t.zpos[l - 1]; d.stab = STAB_SAFE; }
+        // a pool lies below: R at the pool output, then the Pool2d rule + division by Z+ of the conv under it
+        else d.out0 = c.R;
+        LRPX_TRY(timer.timed(l, c.st, [&] { return conv_dispatch(&d, c.st); }));
+        if (pool_below) {
+            // wide maps: hand the conv below its input in K-chunks (32-byte pixel slices would drag every 128-byte
+            // line through the fabric four times: measured L2 hit 36 %, 3x the unique bytes on conv1_2)
+            const int below_hw = 2 * L.hw;
+            const int chunk = below_hw < 112 ? 0 : lrpx_conv_kc(below_hw, 9, L.cin);
+            LRPX_TRY(maxpool_relevance_amax(c.tr + t.act[l - 1], c.R, c.tr + t.zpos[l - 2], c.map2img, nullptr, c.buf[cur ^ 1],
+                                            c.n_maps, L.hw, L.hw, L.cin, chunk, nullptr, c.st));
+            cur_chunked = chunk ? 1 : 0;
         }
-        d.n_oc = L.cin; d.epi = EPI_REL; d.oc_split = L.cin;
-        if (b6) {
-            d.bf16x6 = 1; d.epi = EPI_REL_MUL; d.wpacked = pk + p.bwd6[l];
-            d.tile_group = (n_maps % n_img == 0) ? n_maps / n_img : 0;
-            if (l + 1 < kNL && !kVgg[l + 1].conv) d.pool_am = (const uint8_t*)(tr + t.am[l + 1]);
-            else if (wino_layer(l)) d.wpacked_wino = pk + p.bwdw6[l];      // (used where lrpx_set_b6_wino / LRPX_B6_WINO has the bit of L.hw)
-        } else if (h3) {
-            d.f16x3 = 1; d.epi = EPI_REL_MUL; d.wpacked = pk + p.bwdh[l]; d.in_amax = amax + (size_t)l * n_maps;
-            // the maps of one image (the words of its caption) usually follow each other: tile-order hint for the
-            // multiplicand reuse in L2 (a wrong guess only costs the reuse)
-            d.tile_group = (n_maps % n_img == 0) ? n_maps / n_img : 0;
-            // mode 3: cross products on the fp8 matrix cores
-            const bool pooled_in = l + 1 < kNL && !kVgg[l + 1].conv;
-            if (mode == 3) { d.f16x3 = 2; d.wpacked = pk + p.bwd8[l]; }
-            // under a pool: S[cur] is the low-resolution tensor the conv above the pool wrote, unpooled while staged
-            if (pooled_in) d.pool_am = (const uint8_t*)(tr + t.am[l + 1]);
-            // blocked: in (1), x (2), out (4); conv1_2 (l == 1): blocked input only (see conv_f16x3.h, TR)
-            if (blk) d.blocked = l == 1 ? 1 : 7;
-        }
+        cur ^= 1;
+    }
+    return timer.timed(0, c.st, [&] { return c.first_layer(c.buf[cur], out_nchw, 0); });
+}
+
+// Modes 1 - 3 share the FUSED flow: REL_MUL epilogues on the precomputed multiplicands x / safe(Z+), convs under a pool unpool while they
+// stage, no pool kernels, no unpooled tensors
+static int relevance_fused(const Chain& c, const float* r_feat_nhwc, float* out_nchw, LayerTimer& timer) {
+    const ModeRow& m = c.m;
+    const VggTrace& t = c.t;
+    int cur = 0, cur_chunked = 0;   // S[cur] is stored in K-chunks (conv2_2's output in the NHWC modes)
+    if (c.amax) LRPX_TRY(clear_async(c.amax, (size_t)kNL * c.n_maps * sizeof(unsigned), c.st));
+    // S_16 = R_feat / safe(Z+_16)
+    if (m.blocked)
+        LRPX_TRY(divide_stab_blocked(r_feat_nhwc, c.tr + t.zpos[16], c.map2img, c.buf[cur], c.n_maps, 196, 512, c.amax + (size_t)16 * c.n_maps, c.st));
+    else
+        LRPX_TRY(divide_stab_amax(r_feat_nhwc, c.tr + t.zpos[16], c.map2img, c.buf[cur], c.n_maps, (long)196 * 512, STAB_SAFE0,
+                                  c.amax ? c.amax + (size_t)16 * c.n_maps : nullptr, c.st));
+    for (int l = kNL - 1; l > 0; --l) {
+        const VggLayer& L = kVgg[l];
+        if (!L.conv) continue;   // pools are handled together with the conv above them
+        lrpx_conv_desc d = c.desc(l, m.rel, c.buf[cur], true);
+        d.epi = EPI_REL_MUL; d.in_chunked = cur_chunked;
+        cur_chunked = 0;
+        // x / safe(Z+) precomputed: of the conv below (ReLU passes relevance through, lrp_modules.py:42-46) or, where a pool lies below,
+        // max / safe(Z+ at the winner), which turns the accumulator straight into S of the conv under the pool (at the winners).
+        // blocked: in (1), x (2), out (4); conv1_2 (l == 1): blocked input only (see conv_f16x3.h, TR)
+        d.x = c.tr + ((m.blocked && l != 1) ? t.xzp[l] : t.xz[l]); d.out1 = c.buf[cur ^ 1];
+        if (m.blocked) d.blocked = l == 1 ? 1 : 7;
+        if (c.amax) d.out1_amax = c.amax + (size_t)(kVgg[l - 1].conv ? l - 1 : l - 2) * c.n_maps;
+        if (m.rel.bf16x6 && wino_layer(l)) d.wpacked_wino = c.pk + c.p.at(R_bwdw6, l);      // (used where lrpx_set_b6_wino / LRPX_B6_WINO has the bit of L.hw)
+        // the first-layer kernel walks S in channel chunks (MFMA version: 32 = whole 128-byte lines per pixel; VALU: 16)
+        if (l == 1) d.out_chunk = m.first_mfma ? 32 : 16;
+        // conv2_2 -> conv2_1, NHWC: S in 16-channel chunks, the K-chunk of the consumer (64-byte slices of 512-byte NHWC pixels
+        // drag every 128-byte line through the fabric twice: FETCH 3.1x the tensor; chunked: conv2_1 1.44 -> 1.37 ms)
+        if (l == 4 && !m.blocked) { d.out_chunk = 16; cur_chunked = 1; }
         // (14 x 14 on the Winograd kernel: one launch of 8 x ceil(49 n_maps / 64) workgroups, no K split)
         constexpr int rel_ks = 2;
         static_assert((512 / 16) % rel_ks == 0, "the K ranges must divide the K-chunks of the 14 x 14 layers");
-        if (b6 && L.hw == 14 && !(d.wpacked_wino && (b6_wino_bits() & 4))) {
+        if (m.rel.bf16x6 && L.hw == 14 && !(d.wpacked_wino && (b6_wino_bits() & 4))) {
             // the 14 x 14 relevance layers of mode 1 K-split in two: partial sums into the R buffer (unused in the fused flow), then
             // out = multiplicand * (pairwise sum) in rel_mul_finish.  At 320 maps the layers cost the same (1 120 -> 2 240 workgroups on 512 slots:
             // the shorter tail pays for the extra pass: 3.67 -> 3.64 ms over the three layers); a chain of 20 maps - the drop-in's one image - ran
             // them on 72 workgroups with 288-step K loops: 319 -> 190 us each, 4.24 -> 3.86 ms per chain.  A LAYER property, never the batch's:
             // an image's maps are the same bits in every batch (tests/test_gpu_gridtd.py::test_one_image_alone_equals...).  Four ranges: +0.3 ms at 320 maps.
             lrpx_conv_desc dk = d;
-            dk.epi = EPI_PLAIN; dk.x = nullptr; dk.out0 = R; dk.out1 = nullptr; dk.pool_am = nullptr; dk.map2img = nullptr; dk.tile_group = 0;
-            if (timing) (void)hipEventRecord(timer.ev[l][0], (hipStream_t)stream);
-            LRPX_TRY(conv_dispatch(&dk, (hipStream_t)stream, rel_ks));
-            LRPX_TRY(rel_mul_finish(R, rel_ks, tr + t.xz[l], map2img, S[cur ^ 1], n_maps, (long)196 * L.cin, (hipStream_t)stream));
-            if (timing) { (void)hipEventRecord(timer.ev[l][1], (hipStream_t)stream); timer.valid[l] = true; }
-            cur ^= 1;
-            continue;
-        }
-        if (kVgg[l - 1].conv) {
-            // ReLU passes relevance through (lrp_modules.py:42-46): fuse the next layer's S = R / safe(Z+)
-            d.out1 = S[cur ^ 1];
-            if (fused) { d.x = tr + ((blk && l != 1) ? t.xzp[l] : t.xz[l]); if (h3) d.out1_amax = amax + (size_t)(l - 1) * n_maps; }   // x / safe(Z+) precomputed
-            // the first-layer kernel walks S in channel chunks (MFMA version: 32 = whole 128-byte lines per pixel; VALU: 16)
-            const int fl_chunk = b6 ? 16 : 32;
-            if (fused && l == 1) d.out_chunk = fl_chunk;
-            else if (!blk && !b6) { d.zdiv = tr + t.zpos[l - 1]; d.stab = STAB_SAFE; }
-            // mode 2, conv2_2 -> conv2_1: S in 16-channel chunks, the K-chunk of the consumer (64-byte slices of 512-byte NHWC pixels
-            // drag every 128-byte line through the fabric twice: FETCH 3.1x the tensor; chunked: conv2_1 1.44 -> 1.37 ms)
-            if (fused && !blk && l == 4) { d.out_chunk = 16; cur_chunked = 1; }
-            LRPX_TIMED_DISPATCH(l, &d);
+            dk.epi = EPI_PLAIN; dk.x = nullptr; dk.out0 = c.R; dk.out1 = nullptr; dk.pool_am = nullptr; dk.map2img = nullptr; dk.tile_group = 0;
+            LRPX_TRY(timer.timed(l, c.st, [&] {
+                LRPX_TRY(conv_dispatch(&dk, c.st, rel_ks));
+                return rel_mul_finish(c.R, rel_ks, c.tr + t.xz[l], c.map2img, c.buf[cur ^ 1], c.n_maps, (long)196 * L.cin, c.st);
+            }));
         } else {
-            if (fused) {
-                // a pool lies below: x = max / safe(Z+ at the winner) turns the accumulator straight into S of the conv
-                // under the pool (at the winners); that conv unpools it while staging - no pool kernel, no 4x tensor
-                d.x = tr + (blk ? t.xzp[l] : t.xz[l]); d.out1 = S[cur ^ 1]; if (h3) d.out1_amax = amax + (size_t)(l - 2) * n_maps;
-                LRPX_TIMED_DISPATCH(l, &d);
-                cur ^= 1;
-                continue;
-            }
-            // mode 0, a pool lies below: R at the pool output, then the Pool2d rule + division by Z+ of the conv under it
-            d.out0 = R;
-            LRPX_TIMED_DISPATCH(l, &d);
-            // wide maps: hand the conv below its input in K-chunks (32-byte pixel slices would drag every 128-byte
-            // line through the fabric four times: measured L2 hit 36 %, 3x the unique bytes on conv1_2)
-            const int below_hw = 2 * L.hw;
-            const int chunk = below_hw < 112 ? 0 : lrpx_conv_kc(below_hw, 9, L.cin);
-            LRPX_TRY(maxpool_relevance_amax(tr + t.act[l - 1], R, tr + t.zpos[l - 2], map2img, nullptr, S[cur ^ 1],
-                                            n_maps, L.hw, L.hw, L.cin, chunk, nullptr, (hipStream_t)stream));
-            cur_chunked = chunk ? 1 : 0;
+            LRPX_TRY(timer.timed(l, c.st, [&] { return conv_dispatch(&d, c.st); }));
         }
         cur ^= 1;
     }
-    if (timing) LRPX_TRY(timer.finish(cx.layer_ms));
+    return timer.timed(0, c.st, [&] { return c.first_layer(c.buf[cur], out_nchw, 0); });
+}
+
+// guided backprop (plain = 0) or the plain autograd gradient (plain = 1) of the encoder output w.r.t. the image
+static int vgg16_backprop(const void* packed, const void* trace, int n_img, const float* d_feat_nhwc, const int32_t* map2img, int n_maps,
+                          void* workspace, float* out_nchw, int plain, const lrpx_vgg16_opts* opts, void* stream) {
+    LRPX_REQUIRE(packed && trace && d_feat_nhwc && workspace && out_nchw && n_maps > 0 && n_img > 0, "vgg16_guided_backprop: bad arguments");
+    LRPX_CHECK_PTRS(plain ? "lrpx_vgg16_gradient" : "lrpx_vgg16_guided_backprop", {packed, "packed"}, {trace, "trace"}, {d_feat_nhwc, "d_feat_nhwc"},
+                    {map2img, "map2img"}, {workspace, "workspace"}, {out_nchw, "out_nchw"});
+    LRPX_REQUIRE(map2img || n_maps == n_img, "vgg16_guided_backprop: map2img is required when n_maps != n_img");
+    const Chain c(opts, packed, trace, n_img, map2img, n_maps, workspace, stream);
+    const VggTrace& t = c.t;
+    int cur = 0;
+    // hook of the last ReLU (the encoder ends with one): clamp(d,0) * [features > 0]
+    LRPX_TRY(guided_gate(d_feat_nhwc, c.tr + t.act[kNL], map2img, c.buf[cur], n_maps, (long)196 * 512, plain, c.st));
+    // fp16 split-product kernels: operand scale = per-map maximum of the incoming gradient, recorded by whoever writes that tensor (the
+    // GUIDED epilogue of the conv above, the pool backward kernel); only the first tensor costs a streaming read of its own
+    unsigned* gam = c.amax;
+    if (gam) {
+        LRPX_TRY(clear_async(gam, (size_t)kNL * n_maps * sizeof(unsigned), c.st));
+        LRPX_TRY(lrpx_amax_maps(c.buf[cur], n_maps, (long)196 * 512, gam + (size_t)16 * n_maps, c.st));
+    }
+    for (int l = kNL - 1; l > 0; --l) {
+        const VggLayer& L = kVgg[l];
+        if (!L.conv) continue;
+        lrpx_conv_desc d = c.desc(l, c.m.plain, c.buf[cur], c.m.lowres);
+        const bool hook = kVgg[l - 1].conv || c.m.lowres;
+        if (hook) {
+            // ReLU hook of conv l-1 fused - or a pool lies below and the conv under it routes the gradient, which it receives at the pool's OUTPUT
+            // resolution, to the windows' arg-max while staging (the winner bytes of the trace, as the relevance chain): no pool-backward kernel, no 4x
+            // tensor.  The pool backward's gate [max > 0] (and the guided clamp) is the same hook on the pool's OUTPUT (= this conv's input, act[l])
+            d.epi = EPI_GUIDED; d.x = c.tr + t.act[l]; d.out0 = c.buf[cur ^ 1];
+            d.relu = plain ? 2 : 0;
+            if (gam) d.out0_amax = gam + (size_t)(kVgg[l - 1].conv ? l - 1 : l - 2) * n_maps;
+        } else {
+            d.epi = EPI_PLAIN; d.out0 = c.R;      // ... else the gradient at the pool's output, then the pool backward kernel
+        }
+        LRPX_TRY(conv_dispatch(&d, c.st));
+        if (!hook)
+            LRPX_TRY(maxpool_guided_bwd(c.tr + t.act[l - 1], c.R, map2img, c.buf[cur ^ 1], n_maps, L.hw, L.hw, L.cin, plain,
+                                        gam ? gam + (size_t)(l - 2) * n_maps : nullptr, c.st));
+        cur ^= 1;
+    }
+    return c.first_layer(c.buf[cur], out_nchw, 1);      // (W itself in both chains: conv1_1 has no ReLU below it)
+}
+
+extern "C" {
+
+int lrpx_vgg16_relevance(const void* packed, const void* trace, int n_img, const float* r_feat_nhwc,
+                         const int32_t* map2img, int n_maps, void* workspace, float* out_nchw, void* stream) {
+    lrpx_vgg16_opts o = {-1, -1, tl_ms};       // legacy per-thread profiling switch: this call records and waits for its own events
+    return lrpx_vgg16_relevance_ex(packed, trace, n_img, r_feat_nhwc, map2img, n_maps, workspace, out_nchw, tl_timing ? &o : nullptr, stream);
+}
+
+int lrpx_vgg16_relevance_ex(const void* packed, const void* trace, int n_img, const float* r_feat_nhwc, const int32_t* map2img, int n_maps,
+                            void* workspace, float* out_nchw, const lrpx_vgg16_opts* opts, void* stream) {
+    LRPX_CHECK_PTRS("lrpx_vgg16_relevance_ex", {packed, "packed"}, {trace, "trace"}, {r_feat_nhwc, "r_feat_nhwc"}, {map2img, "map2img"}, {workspace, "workspace"}, {out_nchw, "out_nchw"});
+    LRPX_REQUIRE(packed && trace && r_feat_nhwc && workspace && out_nchw && n_maps > 0 && n_img > 0, "vgg16_relevance: bad arguments");
+    LRPX_REQUIRE(map2img || n_maps == n_img, "vgg16_relevance: map2img is required when n_maps != n_img");
+    const Chain c(opts, packed, trace, n_img, map2img, n_maps, workspace, stream);
+    float* layer_ms = opts ? opts->layer_ms : nullptr;      // host [17]: per-layer HIP-event times of THIS call (events live and die inside the call)
+    LayerTimer timer;
+    if (layer_ms) LRPX_TRY(timer.begin());
+    LRPX_TRY(c.m.fused ? relevance_fused(c, r_feat_nhwc, out_nchw, timer) : relevance_rel(c, r_feat_nhwc, out_nchw, timer));
+    if (layer_ms) LRPX_TRY(timer.finish(layer_ms));
     return LRPX_OK;
 }
 
@@ -738,100 +823,13 @@ int lrpx_vgg16_layer_timing(int enable, float* ms17) {
     return LRPX_OK;
 }
 
-}  // extern "C"
-
-// guided backprop (plain = 0) or the plain autograd gradient (plain = 1) of the encoder output w.r.t. the image
-static int vgg16_backprop(const void* packed, const void* trace, int n_img, const float* d_feat_nhwc,
-                          const int32_t* map2img, int n_maps, void* workspace, float* out_nchw, int plain,
-                          const lrpx_vgg16_opts* opts, void* stream) {
-    LRPX_REQUIRE(packed && trace && d_feat_nhwc && workspace && out_nchw && n_maps > 0 && n_img > 0,
-                 "vgg16_guided_backprop: bad arguments");
-    LRPX_CHECK_PTRS(plain ? "lrpx_vgg16_gradient" : "lrpx_vgg16_guided_backprop", {packed, "packed"}, {trace, "trace"}, {d_feat_nhwc, "d_feat_nhwc"},
-                    {map2img, "map2img"}, {workspace, "workspace"}, {out_nchw, "out_nchw"});
-    const int mode = resolve_ctx(opts).mode;
-    LRPX_REQUIRE(map2img || n_maps == n_img, "vgg16_guided_backprop: map2img is required when n_maps != n_img");
-    const VggPacked p = vgg_packed_layout();
-    const VggTrace t = vgg_trace_layout(n_img);
-    const float* pk = (const float*)packed;
-    const float* tr = (const float*)trace;
-    float* ws = (float*)workspace;
-    const size_t sbuf = (size_t)224 * 224 * 64 * n_maps;
-    float* G[2] = {ws, ws + sbuf};
-    float* R = ws + 2 * sbuf;
-    hipStream_t st = (hipStream_t)stream;
-    int cur = 0;
-    // hook of the last ReLU (the encoder ends with one): clamp(d,0) * [features > 0]
-    LRPX_TRY(guided_gate(d_feat_nhwc, tr + t.act[kNL], map2img, G[cur], n_maps, (long)196 * 512, plain, st));
-    // fp16 split-product kernels: operand scale = per-map maximum of the incoming gradient, gam[l*n_maps + n] for the
-    // tensor conv layer l consumes - recorded by whoever writes that tensor (the GUIDED epilogue of the conv above, the
-    // pool backward kernel); only the first tensor costs a streaming read of its own
-    const bool h3 = mode >= 2;
-    // mode 1 (round 6): exact bf16 splits on the conv_f16x3.h tiling (B6), GUIDED hooks fused, pools folded into the staging as in mode 3
-    const bool b6 = mode == 1;
-    unsigned* gam = reinterpret_cast<unsigned*>(R + (size_t)112 * 112 * 64 * n_maps);
-    if (h3) {
-        LRPX_TRY(clear_async(gam, (size_t)kNL * n_maps * sizeof(unsigned), st));
-        LRPX_TRY(lrpx_amax_maps(G[cur], n_maps, (long)196 * 512, gam + (size_t)16 * n_maps, st));
-    }
-    for (int l = kNL - 1; l >= 0; --l) {
-        const VggLayer& L = kVgg[l];
-        if (!L.conv) continue;
-        if (l == 0) {
-            if (h3)
-                LRPX_TRY(first_layer_relevance_mfma(G[cur], pk + p.first16p, tr + t.act[0], map2img, gam, out_nchw, n_maps, 1, 0, st));
-            else
-                LRPX_TRY(first_layer_relevance(G[cur], pk + p.first6p, tr + t.act[0], map2img, out_nchw, n_maps, L.cout, 1, 0, st));
-            break;
-        }
-        lrpx_conv_desc d = {};
-        d.in = G[cur]; d.wpacked = pk + p.bwdp[l];
-        d.n_maps = n_maps; d.hw = L.hw; d.cin = L.cout; d.taps = 9; d.map2img = map2img;
-        d.n_oc = L.cin; d.oc_split = L.cin;
-        if (h3) {
-            d.f16x3 = 1; d.wpacked = pk + p.bwdph[l]; d.in_amax = gam + (size_t)l * n_maps;
-            d.tile_group = (n_maps % n_img == 0) ? n_maps / n_img : 0;        // (tile-order hint, as in the relevance chain)
-            if (mode == 3) { d.f16x3 = 2; d.wpacked = pk + p.bwdp8[l]; }      // cross products on the fp8 matrix cores
-        } else if (b6) {
-            d.bf16x6 = 1; d.wpacked = pk + p.bwdp6[l];
-            d.tile_group = (n_maps % n_img == 0) ? n_maps / n_img : 0;
-        }
-        // mode 3: a conv under a pool receives the gradient at the pool's OUTPUT resolution and routes it to the windows'
-        // arg-max while staging (the winner bytes of the trace, as the relevance chain): no pool-backward kernel, no 4x tensor
-        const bool lowres_in = (mode == 3 || b6) && l + 1 < kNL && !kVgg[l + 1].conv && l + 2 < kNL;
-        if (lowres_in) d.pool_am = (const uint8_t*)(tr + t.am[l + 1]);
-        if (kVgg[l - 1].conv) {
-            d.epi = EPI_GUIDED; d.x = tr + t.act[l]; d.out0 = G[cur ^ 1];      // ReLU hook of conv l-1 fused
-            d.relu = plain ? 2 : 0;
-            if (h3) d.out0_amax = gam + (size_t)(l - 1) * n_maps;
-            LRPX_TRY(conv_dispatch(&d, st));
-        } else if ((mode == 3 || b6) && l >= 2) {
-            // a pool lies below: the pool backward's gate [max > 0] (and the guided clamp) is the GUIDED hook on the pool's
-            // OUTPUT (= this conv's input, act[l]); the conv under the pool unpools while staging
-            d.epi = EPI_GUIDED; d.x = tr + t.act[l]; d.out0 = G[cur ^ 1];
-            d.relu = plain ? 2 : 0;
-            if (h3) d.out0_amax = gam + (size_t)(l - 2) * n_maps;
-            LRPX_TRY(conv_dispatch(&d, st));
-        } else {
-            d.epi = EPI_PLAIN; d.out0 = R;
-            LRPX_TRY(conv_dispatch(&d, st));
-            LRPX_TRY(maxpool_guided_bwd(tr + t.act[l - 1], R, map2img, G[cur ^ 1], n_maps, L.hw, L.hw, L.cin, plain,
-                                        h3 ? gam + (size_t)(l - 2) * n_maps : nullptr, st));
-        }
-        cur ^= 1;
-    }
-    return LRPX_OK;
-}
-
-extern "C" {
-
 int lrpx_vgg16_guided_backprop(const void* packed, const void* trace, int n_img, const float* d_feat_nhwc,
                                const int32_t* map2img, int n_maps, void* workspace, float* out_nchw, void* stream) {
     return vgg16_backprop(packed, trace, n_img, d_feat_nhwc, map2img, n_maps, workspace, out_nchw, 0, nullptr, stream);
 }
 
-int lrpx_vgg16_guided_backprop_ex(const void* packed, const void* trace, int n_img, const float* d_feat_nhwc,
-                                  const int32_t* map2img, int n_maps, void* workspace, float* out_nchw,
-                                  const lrpx_vgg16_opts* opts, void* stream) {
+int lrpx_vgg16_guided_backprop_ex(const void* packed, const void* trace, int n_img, const float* d_feat_nhwc, const int32_t* map2img,
+                                  int n_maps, void* workspace, float* out_nchw, const lrpx_vgg16_opts* opts, void* stream) {
     return vgg16_backprop(packed, trace, n_img, d_feat_nhwc, map2img, n_maps, workspace, out_nchw, 0, opts, stream);
 }
 
@@ -840,9 +838,8 @@ int lrpx_vgg16_gradient(const void* packed, const void* trace, int n_img, const 
     return vgg16_backprop(packed, trace, n_img, d_feat_nhwc, map2img, n_maps, workspace, out_nchw, 1, nullptr, stream);
 }
 
-int lrpx_vgg16_gradient_ex(const void* packed, const void* trace, int n_img, const float* d_feat_nhwc,
-                           const int32_t* map2img, int n_maps, void* workspace, float* out_nchw,
-                           const lrpx_vgg16_opts* opts, void* stream) {
+int lrpx_vgg16_gradient_ex(const void* packed, const void* trace, int n_img, const float* d_feat_nhwc, const int32_t* map2img,
+                           int n_maps, void* workspace, float* out_nchw, const lrpx_vgg16_opts* opts, void* stream) {
     return vgg16_backprop(packed, trace, n_img, d_feat_nhwc, map2img, n_maps, workspace, out_nchw, 1, opts, stream);
 }
 
